@@ -14,11 +14,13 @@ come from the environment; `bench.py --gpus N` without one starts the N ranks it
 and exits with its status.  A run whose world size is not N exits non-zero instead of
 printing a line.
 
-Also reported: per-stage device time, the roofline of the dominant kernel (HIP events
+A run sets up, warms up, times --steps steps, writes the last timed step's replies if
+--dump-outputs is given, and prints one JSON line.  Everything else runs only with --full,
+after the timed region: per-stage device time, the roofline of the dominant kernel (HIP events
 on the engine stream; for the pipelined engine, over a serial replay of the same timed
-batches, since overlapped stages share the chip), and the CPU baseline (the C
-restatement of the reference script, oracle/tb_ref.c, on a bounded sample of the same
-trace).
+batches, since overlapped stages share the chip), the host-buffer and string-directory
+rates, the batch-size sweep, and the CPU baseline (the C restatement of the reference
+script, oracle/tb_ref.c, on a bounded sample of the same trace).
 """
 from __future__ import annotations
 
@@ -37,8 +39,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from bench_kinds import (cpu_model, gather_floats, mark, pmc_workload, reduce_max,  # noqa: E402
-                         run_fingerprint, write_fingerprint)
+from bench_kinds import (cpu_model, dump_outputs, gather_floats, mark, pmc_workload,  # noqa: E402
+                         reduce_max, run_fingerprint, table_rows, write_fingerprint)
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8.0 TB/s spec
 SEED_B = 0x5EED000B
@@ -54,6 +56,17 @@ def parse():
     # matches profiles/pmc_summary.json's fingerprint and carries its PMC traffic
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg after the timed region: the serial replay (stage "
+                         "times, roofline, PMC bytes), the host-buffer and string-directory rates, the "
+                         "batch-size sweep, config D's draining schedule, config E's other refresh modes "
+                         "and the CPU baselines.  Without it a run sets up, warms up, times --steps steps "
+                         "and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the replies of the last timed step (what the "
+                         "caller of the timed entry point receives) as DIR/<name>.npy in float32, "
+                         "batches above 2^22 requests as a fixed, seeded sample of 2^22 of them; and "
+                         "the first 2^20 rows of the bucket table the steps left (float64)")
     ap.add_argument("--workload", choices=("uniform", "zipf", "queue", "approx", "testapp"),
                     default="uniform",
                     help="uniform: config B (the headline); zipf: config C's per-GPU slice; "
@@ -136,6 +149,10 @@ def parse():
     ap.add_argument("--no-pipeline", action="store_true",
                     help="one stream per batch: no overlap of batch b+1's partition with batch b's fold (A/B)")
     args = ap.parse_args()
+    if args.drain_marked and not args.full:
+        ap.error("--drain-marked marks the draining schedule, which runs only with --full")
+    if args.dump_outputs and args.emulate_world:
+        ap.error("--dump-outputs: the emulation (--emulate-world) times several owners, not one path")
     testapp = args.workload == "testapp"
     if args.batch is None:
         args.batch = 1_000_000 if testapp else 1 << 26
@@ -263,11 +280,11 @@ def main():
     seed = {"zipf": SEED_C, "testapp": SEED_A}.get(args.workload, SEED_B)
     gen_stream = torch.cuda.current_stream(dev).cuda_stream or None
 
-    def gen_batch(s):   # this rank's share of the global stream at step s
+    def gen_batch(s, into=None):   # this rank's share of the global stream at step s
         g0 = (s * world + rank) * n
-        k = torch.empty(n, dtype=torch.int64, device=dev)
-        p = torch.empty(n, dtype=torch.int32, device=dev)
-        t = torch.empty(n, dtype=torch.int64, device=dev)
+        k, p, t = into or (torch.empty(n, dtype=torch.int64, device=dev),
+                           torch.empty(n, dtype=torch.int32, device=dev),
+                           torch.empty(n, dtype=torch.int64, device=dev))
         assert lib.tbe_gen_batch_device(seed, keys_total, g0, n, 1, 1, T0_US + s * args.interval_us,
                                         args.interval_us, k.data_ptr(), p.data_ptr(), t.data_ptr(), gen_stream) == 0
         if args.workload == "zipf":
@@ -286,9 +303,16 @@ def main():
     directory = cluster.DeviceDirectory(keys_local, device=dev.index, strict=args.route != "timed") \
         if routed else None
     bufs, raw = [], []
+    # One GPU: at most RESIDENT_BYTES of inputs live in HBM at a time, so that
+    # --steps may be any number.  A longer run stops the clock every `resident` steps, writes
+    # the next steps' requests into the same buffers and goes on (same requests, same
+    # replies, whatever `resident` is).  The default schedule (25 batches) fits at once.
+    resident = total_steps
+    if world == 1:
+        resident = min(total_steps, max(1, RESIDENT_BYTES // (20 * n)))
     # generated on the current stream: the routing kernels run on it too (a torch stream does
     # not wait for the legacy NULL stream)
-    for s in range(total_steps):
+    for s in range(resident):
         k, p, t = gen_batch(s)
         if routed and args.route == "pre":
             (lk, lp, lt), _ = cluster.route_requests(k, p, t, directory, owner_map=omap)
@@ -317,7 +341,7 @@ def main():
     granted = torch.empty(m_max if not raw else n, dtype=torch.uint8, device=dev)
     remaining = torch.empty(m_max if not raw else n, dtype=torch.int32, device=dev)
     zkeys = [bufs[s][0].cpu().numpy().view(np.uint64) for s in range(min(2, len(bufs)))] \
-        if args.workload == "zipf" and not routed else []
+        if args.full and args.workload == "zipf" and not routed else []   # (the CPU baseline's keys)
     cur = torch.cuda.current_stream(dev).cuda_stream
 
     def decide(lk, lp, lt):   # --route timed: the owner's engine on the routed requests
@@ -332,10 +356,20 @@ def main():
             granted.copy_(g)
             remaining.copy_(r)
         else:
-            m = bufs[s][0].numel()
-            eng.acquire_batch_device(*bufs[s], granted[:m], remaining[:m])
+            b = bufs[s % resident]
+            m = b[0].numel()
+            eng.acquire_batch_device(*b, granted[:m], remaining[:m])
+
+    def refill(s0, e=None):   # steps s0 .. s0 + resident - 1 into the resident buffers (clock stopped)
+        (e or eng).synchronize()
+        torch.cuda.synchronize()
+        for s in range(s0, min(s0 + resident, total_steps)):
+            gen_batch(s, into=bufs[s % resident])
+        torch.cuda.synchronize()
 
     for s in range(args.warmup):
+        if s and s % resident == 0:
+            refill(s)
         step(s)
     eng.synchronize()
     torch.cuda.synchronize()
@@ -345,14 +379,21 @@ def main():
     if dist:
         td.barrier()
     torch.cuda.synchronize()
+    elapsed = 0.0
     t0 = time.perf_counter()
     for s in range(args.warmup, total_steps):
+        if s and s % resident == 0:
+            eng.synchronize()
+            torch.cuda.synchronize()
+            elapsed += time.perf_counter() - t0
+            refill(s)
+            t0 = time.perf_counter()
         step(s)
     eng.synchronize()
     torch.cuda.synchronize()
     if dist:
         td.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed += time.perf_counter() - t0
     mark(lib, 2, dev)
     load = None
     if dist:
@@ -362,14 +403,19 @@ def main():
         ev = gather_floats(float(sum(sizes[args.warmup:])), world, dev)
         load = {"per_rank_requests": ev.tolist(), "max_over_mean": round(float(ev.max() / ev.mean()), 4)}
     stages_overlapped = eng.stage_times()
-    m_last = (raw[-1][0] if raw else bufs[total_steps - 1][0]).numel()
+    last_keys = raw[-1][0] if raw else bufs[(total_steps - 1) % resident][0]
+    m_last = last_keys.numel()
     grant_rate = float(granted[:m_last].float().mean().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"granted": granted[:m_last], "remaining": remaining[:m_last],
+                                         **table_rows(eng)}, rank, world)
     # SURVEY.md §8(d) B_alg of the last timed batch, measured: U = its distinct keys, W =
     # the distinct keys it wrote (granted at least once; a deny writes nothing, TB:225-236)
-    last_keys = raw[-1][0] if raw else bufs[total_steps - 1][0]
-    u_meas = int(torch.unique(last_keys).numel())
-    w_meas = int(torch.unique(last_keys[granted[:m_last].bool()]).numel())
-    step_alg = int(m_last * 25 + u_meas * 16 + w_meas * 16)
+    u_meas = w_meas = step_alg = 0
+    if args.full:
+        u_meas = int(torch.unique(last_keys).numel())
+        w_meas = int(torch.unique(last_keys[granted[:m_last].bool()]).numel())
+        step_alg = int(m_last * 25 + u_meas * 16 + w_meas * 16)
     uw_note = "U and W measured on the last timed batch"
 
     decisions = n * args.steps * world
@@ -383,7 +429,7 @@ def main():
     # right after the timed region; its replies must equal the pipelined run's.
     stages, replay_check = stages_overlapped, None
     line_read = line_written = None
-    if replay and layout.get("pipeline"):
+    if args.full and replay and layout.get("pipeline"):
         eng.close()
         ser = TokenBucketEngine(keys_local, args.token_limit, args.tokens_per_period,
                                 args.period_ticks, device=dev.index, stage_timing=True,
@@ -392,36 +438,62 @@ def main():
                             digit_stream=not args.hist_records, rerank=args.rerank)
         g2 = torch.empty_like(granted)
         r2 = torch.empty_like(remaining)
+        if resident < total_steps:
+            refill(0, ser)
         for s in range(args.warmup):
-            ser.acquire_batch_device(*bufs[s], g2[:sizes[s]], r2[:sizes[s]])
+            if s and s % resident == 0:
+                refill(s, ser)
+            b = bufs[s % resident]
+            ser.acquire_batch_device(*b, g2[:b[0].numel()], r2[:b[0].numel()])
         ser.synchronize()
         ser.stage_times()
-        g_all = [torch.empty(sizes[s], dtype=torch.uint8, device=dev) for s in range(args.warmup, total_steps)]
-        mark(lib, 3, dev)     # profiling marker: the replay's timed batches follow (tools/prof_window.py)
-        for i, s in enumerate(range(args.warmup, total_steps)):
-            ser.acquire_batch_device(*bufs[s], g_all[i], r2[:sizes[s]])
-        mark(lib, 4, dev)
-        ser.synchronize()
-        stages = ser.stage_times()
-        replay_check = bool(torch.equal(g_all[-1][:m_last], granted[:m_last]) and
-                            torch.equal(r2[:m_last], remaining[:m_last]))
-        # U and W of every timed batch (the replay's grants equal the timed run's): the
+        # U and W of the timed batches (the replay's grants equal the timed run's): the
         # step's B_alg is their mean, not just the last batch's (the table ages from
-        # grant- to denial-dominated across the timed batches)
+        # grant- to denial-dominated across the timed batches).  Of every timed batch up to
+        # UW_BATCHES of them; of a longer schedule, of UW_BATCHES batches spread evenly from
+        # the first to the last (four sorts of 2^26 keys per batch)
+        picked = sorted({args.warmup + round(i * (args.steps - 1) / max(1, UW_BATCHES - 1))
+                         for i in range(UW_BATCHES)} if args.steps > UW_BATCHES
+                        else range(args.warmup, total_steps))
+        g_of = {}    # timed step -> the replay's grants, kept until its U and W are counted
         uw = []
         lines = []   # 128-byte table lines (8 rows) touched / holding a written row, per batch
-        for i, s in enumerate(range(args.warmup, total_steps)):
-            k = bufs[s][0]
-            kw = k[g_all[i].bool()]
-            uw.append((int(torch.unique(k).numel()), int(torch.unique(kw).numel())))
-            lines.append((int(torch.unique(k // 8).numel()), int(torch.unique(kw // 8).numel())))
-        del g_all
+        stages = {}
+
+        def count_uw():   # the picked batches still resident; then the chunk's stage times
+            ser.synchronize()
+            for name, ms in ser.stage_times().items():
+                stages[name] = stages.get(name, 0.0) + ms
+            for s in sorted(g_of):
+                k = bufs[s % resident][0]
+                kw = k[g_of[s].bool()]
+                uw.append((s, int(torch.unique(k).numel()), int(torch.unique(kw).numel())))
+                lines.append((int(torch.unique(k // 8).numel()), int(torch.unique(kw // 8).numel())))
+                if s != total_steps - 1:   # (the last batch's grants: compared with the timed run's below)
+                    del g_of[s]
+
+        mark(lib, 3, dev)     # profiling marker: the replay's timed batches follow (tools/prof_window.py)
+        for s in range(args.warmup, total_steps):
+            if s and s % resident == 0:
+                count_uw()
+                refill(s, ser)
+            b = bufs[s % resident]
+            g = g2[:b[0].numel()]
+            if s in picked:   # (always holds the last timed batch)
+                g = g_of[s] = torch.empty(b[0].numel(), dtype=torch.uint8, device=dev)
+            ser.acquire_batch_device(*b, g, r2[:b[0].numel()])
+        mark(lib, 4, dev)
+        count_uw()
+        replay_check = bool(torch.equal(g_of[total_steps - 1][:m_last], granted[:m_last]) and
+                            torch.equal(r2[:m_last], remaining[:m_last]))
+        del g_of
+        uw = [(u, w) for _, u, w in uw]
         line_read = float(np.mean([a for a, _ in lines]))
         line_written = float(np.mean([b for _, b in lines]))
         u_mean = float(np.mean([u for u, _ in uw]))
         w_mean = float(np.mean([w for _, w in uw]))
         step_alg = int(n * 25 + u_mean * 16 + w_mean * 16)
-        uw_note = (f"mean over the {len(uw)} timed batches: U {u_mean:.4g}, W {w_mean:.4g} "
+        uw_note = (f"mean over {len(uw)} of the {args.steps} timed batches: U {u_mean:.4g}, W {w_mean:.4g} "
                    f"(first {uw[0][1]}, last {uw[-1][1]} written keys)")
         u_meas, w_meas = int(round(u_mean)), int(round(w_mean))
         eng = ser
@@ -433,7 +505,7 @@ def main():
     # (records, replies and rows) is kept beside it as kernel_own_*; the stage with the most
     # device time is named too.
     roofline = None
-    if stages and stages.get("fold", 0) > 0:
+    if args.full and stages and stages.get("fold", 0) > 0:
         passes = layout["passes"]
         launches = {"hist": passes, "colscan": passes, "scatter": passes, "bounds": 1, "fold": 1,
                     "unscatter": passes - (1 if layout.get("fold_records") else 0), "hot": 5}   # per step
@@ -501,7 +573,10 @@ def main():
     # Config B gets the same check on three of its batches (pageable host buffers: the
     # PCIe-inclusive rate DESIGN.md §6 discusses).
     host_rate = host_rate_pinned = None
-    if args.workload in ("testapp", "uniform") and rank == 0 and world == 1 and not args.no_host_buffer:
+    if args.full and resident < total_steps:
+        refill(0)   # the legs below read the schedule's first batches: bufs[s] is step s again
+    if args.full and args.workload in ("testapp", "uniform") and rank == 0 and world == 1 \
+            and not args.no_host_buffer:
         timed_bufs = bufs[args.warmup:] if args.workload == "testapp" else bufs[args.warmup:args.warmup + 3]
         host = [tuple(x.cpu().numpy() for x in b) for b in timed_bufs]
         hb = TokenBucketEngine(keys_local, args.token_limit, args.tokens_per_period, args.period_ticks,
@@ -531,20 +606,20 @@ def main():
     # the string-key path: the same batches as key text
     # "user-<key>" through the device string directory, after the timed region
     strdir = None
-    if args.workload == "uniform" and rank == 0 and world == 1 and not args.no_strdir:
+    if args.full and args.workload == "uniform" and rank == 0 and world == 1 and not args.no_strdir:
         strdir = bench_strdir(bufs[:6], keys_local, dev)
 
     # batch sizes 2^14 .. 2^26 on the same key space; "sparse_batch" is
     # its 2^20 point (2^20 requests over 1e8 keys touch ~1% of the table's lines: the sparse
     # buckets go one wave each to k_fold_sparse, which gathers only their rows)
     sparse = sweep = None
-    if args.workload == "uniform" and rank == 0 and world == 1 and not args.no_sparse:
+    if args.full and args.workload == "uniform" and rank == 0 and world == 1 and not args.no_sparse:
         sizes = tuple(int(x) for x in args.sweep_log2.split(",")) if args.sweep_log2 else SWEEP_LOG2
         sweep = bench_batch_sweep(args, lib, keys_local, dev, sizes)
         sparse = next((x for x in sweep if x["batch"] == 1 << 20), None)
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(args, keys_local, zkeys,
                            SEED_A if args.workload == "testapp" else SEED_B)
 
@@ -601,6 +676,8 @@ def main():
 
 
 SWEEP_LOG2 = (14, 16, 18, 20, 22, 24, 26)
+RESIDENT_BYTES = 48 << 30   # request batches resident in HBM on one GPU (20 B per request)
+UW_BATCHES = 32             # timed batches whose distinct and written keys --full counts
 
 
 def bench_batch_sweep(args, lib, n_keys: int, dev, sizes=SWEEP_LOG2):

@@ -213,6 +213,42 @@ def mark(lib, tag: int, dev) -> None:
     lib.tbe_mark_device(tag, _MARK_STREAM[dev].cuda_stream)
 
 
+DUMP_SAMPLE = 1 << 22
+DUMP_SEED = 0x5EED0D0
+
+
+def dump_outputs(path: str, arrays: dict, rank: int = 0, world: int = 1) -> None:
+    """bench.py --dump-outputs: the last timed step's replies as <path>/<name>.npy in float32
+    (<name>_rank<r>.npy with several ranks).  An array above DUMP_SAMPLE elements is
+    written as its elements at DUMP_SAMPLE positions drawn once from a fixed seed (the same
+    positions for every array and every run), 16 MiB per array."""
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        if isinstance(x, np.ndarray):   # host rows (table_rows): float64, written whole
+            np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"),
+                    np.ascontiguousarray(x, dtype=np.float64))
+            continue
+        m = x.numel()
+        if m > DUMP_SAMPLE:
+            idx = np.random.default_rng(DUMP_SEED).integers(0, m, DUMP_SAMPLE)
+            x = x[torch.from_numpy(idx).to(x.device)]
+        out = x.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), out)
+
+
+DUMP_ROWS = 1 << 20
+
+
+def table_rows(eng) -> dict:
+    """The bucket table's first DUMP_ROWS rows after the timed steps, for dump_outputs: the
+    tokens v and the last grant's timestamp (tbe_export_state; a key never granted has
+    INT64_MIN and its v written as 0).  Between two refill waves a whole batch of config B
+    can be denied, its replies all zero; the rows the steps left behind never are."""
+    v, t = eng.export_state(0, min(eng.n_keys, DUMP_ROWS))
+    v = np.where(t != np.iinfo(np.int64).min, v, 0.0)
+    return {"table_tokens": v, "table_last_grant_us": t.astype(np.float64)}
+
+
 def _barrier_time(dist, dev, t0):
     torch.cuda.synchronize()
     if dist:
@@ -224,9 +260,17 @@ def _barrier_time(dist, dev, t0):
     return elapsed
 
 
-def _queue_pass(args, lib, dev, world, dist, kl, period_ticks, seed, marked=False):
+def dist_rank(dist) -> int:
+    if not dist:
+        return 0
+    import torch.distributed as td
+    return td.get_rank()
+
+
+def _queue_pass(args, lib, dev, world, dist, kl, period_ticks, seed, marked=False, dump=None):
     """One config-D schedule (warm-up + timed batches, each with its tick) on a fresh
-    engine; returns the timing, stage times and outcome counts."""
+    engine; returns the timing, stage times and outcome counts.  `dump`: write the last
+    timed batch's replies there (dump_outputs)."""
     from distributedratelimiting.redis_amd import QueueingTokenBucketEngine
 
     n, steps, warm = args.batch, args.steps, args.warmup
@@ -313,7 +357,9 @@ def _queue_pass(args, lib, dev, world, dist, kl, period_ticks, seed, marked=Fals
     q = queued.cpu().numpy()
     granted = float((st == 1).float().mean().item())
     layout = eng.layout()
-    if not args.no_stage_timing and not args.timed_stage_events:
+    if dump:
+        dump_outputs(dump, {"status": st, "remaining": rem, **table_rows(eng)}, dist_rank(dist), world)
+    if args.full and not args.no_stage_timing and not args.timed_stage_events:
         # the replay: a fresh engine with stage events decides the same schedule (same state
         # batch by batch); its replies are the timed run's
         g_timed, r_timed = st.clone(), rem.clone()
@@ -347,7 +393,8 @@ def run_queue(args, lib, dev, world, rank, dist):
     fused = not args.no_fuse_tick
     # the PMC markers go around the headline schedule's timed batches, or with --drain-marked
     # around the draining schedule's (tools/pmc_passes.sh's "queue_draining" run)
-    r = _queue_pass(args, lib, dev, world, dist, kl, args.period_ticks, seed, marked=not args.drain_marked)
+    r = _queue_pass(args, lib, dev, world, dist, kl, args.period_ticks, seed, marked=not args.drain_marked,
+                    dump=args.dump_outputs)
     elapsed, stages, granted, q_last, d_last = r["elapsed"], r["stages"], r["granted"], r["q_last"], r["d_last"]
     fp = run_fingerprint(args, world, kl, r["layout"])
     if rank == 0 and not args.drain_marked:
@@ -388,7 +435,7 @@ def run_queue(args, lib, dev, world, rank, dist):
                               elapsed / steps * 1e3, stages, steps),
         "cpu_baseline": None,
     }
-    if not args.no_drain_variant:
+    if args.full and not args.no_drain_variant:
         # The same schedule with ticks that grant: at 1 token/s a saturated key frees one
         # queue entry per ~1000 ticks, so config D's ticks drain nothing within a run.  With
         # ReplenishmentPeriod = 2 batch intervals every queued key gains half a token per
@@ -419,7 +466,7 @@ def run_queue(args, lib, dev, world, rank, dist):
                                   pmc_key="queue_draining"),
             "note": "config D's schedule with ReplenishmentPeriod = 2 batch intervals: the fused ticks "
                     "drain queued entries every step (tick_grants = entries completed by each timed tick)"}
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         line["cpu_baseline"] = cpu_queue(args, kl)
     return line
 
@@ -529,12 +576,14 @@ def run_approx(args, lib, dev, world, rank, dist):
     stages = eng.stage_times()
     fold_timed = stages.get("fold", 0.0)
     granted = float((st == 1).float().mean().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"status": st, "available": av}, rank, world)
     # the other exchange mode's refresh epoch, timed after the timed region on the same
     # engine (its counts are the last batch's local scores, then zeros)
     alt = "clients" if args.approx_mode == "node" else "node"
     if dist:
         td.barrier()
-    for j in range(min(steps, 5)):
+    for j in range(min(steps, 5) if args.full else 0):
         refresh(total + j, alt, True)
     refresh_ms = {m: round(v[0] / v[1] * 1e3, 4) if v[1] else None for m, v in refresh_s.items()}
     if dist:
@@ -542,11 +591,12 @@ def run_approx(args, lib, dev, world, rank, dist):
     # config E's 8-GPU refresh on this one GPU: the all-gather layout of
     # 8 clients' counts -- 8 consecutive batches' collected local scores stand in for the 8
     # ranks' -- and the client-ordered replay of 8 sync calls per key with staggered times
-    eight = approx_eight_clients(args, eng, bufs, st, av, kshared, n, total + 5, dev) if not dist else None
+    eight = approx_eight_clients(args, eng, bufs, st, av, kshared, n, total + 5, dev) \
+        if args.full and not dist else None
     # bytes each GPU receives per refresh: ring all-reduce 2 (N-1)/N * 4K, all-gather (N-1) * 4K
     xbytes = {"node": int(2 * (world - 1) * kshared * 4 // world), "clients": int((world - 1) * kshared * 4)}
     layout = eng.layout()
-    if not args.no_stage_timing and not args.timed_stage_events:
+    if args.full and not args.no_stage_timing and not args.timed_stage_events:
         # stage times from a replay of the warm-up + timed schedule on an engine that records
         # them (the refresh epochs included, as in the timed steps)
         eng.close()
@@ -590,7 +640,8 @@ def run_approx(args, lib, dev, world, rank, dist):
         "refresh_ms_per_step_wall": refresh_ms[args.approx_mode],
         "refresh_modes": {m: {"ms_per_epoch_wall": refresh_ms[m], "exchange_bytes_per_gpu": xbytes[m],
                               "timed": "in the timed steps" if m == args.approx_mode else
-                                       f"{min(steps, 5)} epochs after the timed region"}
+                                       f"{min(steps, 5)} epochs after the timed region" if args.full else
+                                       "not timed (only with --full)"}
                           for m in ("node", "clients")},
         # 8+4+1 in/out + 8 local-tier state per decision,
         # K_shared * (4 count + 24 v,p,t) per refresh
@@ -600,7 +651,7 @@ def run_approx(args, lib, dev, world, rank, dist):
         "cpu_baseline": None,
     }
     eng.close()
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         line["cpu_baseline"] = cpu_approx(args, kshared)
     return line
 

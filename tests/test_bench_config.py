@@ -38,6 +38,56 @@ def test_explicit_flags_win():
     assert (a.batch, a.token_limit) == (4096, 7)
 
 
+def test_full_is_off_by_default_and_gates_the_draining_markers():
+    assert parse([]).full is False and parse([]).dump_outputs is None
+    a = parse(["--full", "--workload", "queue", "--drain-marked", "--dump-outputs", "out"])
+    assert a.full and a.drain_marked and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):   # the draining schedule runs only with --full
+        parse(["--workload", "queue", "--drain-marked"])
+
+
+def test_dump_outputs_writes_a_fixed_float32_sample(tmp_path):
+    """--dump-outputs: float32 .npy files; an array above DUMP_SAMPLE elements is written as
+    its elements at the same seeded positions in every run, a smaller one whole."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench_kinds as bk
+    big = torch.arange(bk.DUMP_SAMPLE + 12345, dtype=torch.int32)   # (exact in float32: < 2^24)
+    small = torch.tensor([0, 1, 1, 0], dtype=torch.uint8)
+    for d in ("a", "b"):
+        bk.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (bk.DUMP_SAMPLE,) and np.array_equal(a, b)
+    assert a.min() >= 0 and a.max() < big.numel() and len(np.unique(a)) > bk.DUMP_SAMPLE // 2
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.tolist() == [0.0, 1.0, 1.0, 0.0]
+    bk.dump_outputs(str(tmp_path / "r"), {"small": small}, rank=1, world=2)
+    assert (tmp_path / "r" / "small_rank1.npy").exists()
+
+
+def test_dump_outputs_table_rows_are_float64_and_mask_untouched_keys(tmp_path):
+    """The table rows of a dump: v and the last grant's time in float64 (exact for
+    microsecond timestamps), v of a never-granted key (INT64_MIN) written as 0."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench_kinds as bk
+
+    class Eng:
+        n_keys = 3
+
+        def export_state(self, first, count):
+            assert (first, count) == (0, 3)
+            return (np.array([2.5, 123.0, 0.25]),
+                    np.array([1_760_000_000_012_345, np.iinfo(np.int64).min, 1_760_000_000_000_001]))
+    rows = bk.table_rows(Eng())
+    bk.dump_outputs(str(tmp_path), rows)
+    v, t = np.load(tmp_path / "table_tokens.npy"), np.load(tmp_path / "table_last_grant_us.npy")
+    assert v.dtype == t.dtype == np.float64
+    assert v.tolist() == [2.5, 0.0, 0.25]
+    assert t.tolist() == [1_760_000_000_012_345.0, float(np.iinfo(np.int64).min), 1_760_000_000_000_001.0]
+
+
 def test_algorithmic_bytes_model():
     sys.path.insert(0, ROOT)
     import bench
@@ -97,7 +147,7 @@ def test_gpus_2_rehearsal_on_one_gpu(workload):
     rehearsed on the one GPU of the test box: both ranks on cuda:0 over gloo, the HIP
     engine deciding on each, the device path's collectives staged through host memory.
     One JSON line, for two GPUs' worth of work, marked as a rehearsal."""
-    argv = ["--gpus", "2", "--share-device", "--workload", workload, "--keys", "2000000",
+    argv = ["--full", "--gpus", "2", "--share-device", "--workload", workload, "--keys", "2000000",
             "--batch", str(1 << 20), "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
             "--no-host-buffer", "--no-strdir"]
     if workload == "queue":

@@ -332,7 +332,7 @@ def run(rounds: int, steps: int):
         for name, v in VARIANTS.items():
             defs, extra = v[0], v[1]
             env = dict(os.environ, TBE_LIB=lib_path(defs, v[2] if len(v) > 2 else None), **_env_defs(defs))
-            args = ["--steps", str(steps), "--cpu-seconds", "0"] + ([] if "--no-strdir" in extra else ["--no-host-buffer", "--no-strdir"])
+            args = ["--full", "--steps", str(steps), "--cpu-seconds", "0"] + ([] if "--no-strdir" in extra else ["--no-host-buffer", "--no-strdir"])
             if "--warmup" not in extra:
                 args += ["--warmup", "3"]
             out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + extra, env=env,

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out
 TAG=${TAG:-r06g}
-ARGS="--workload uniform --steps 10 --warmup 3 --cpu-seconds 0 --no-host-buffer --no-strdir --no-sparse"
+ARGS="--full --workload uniform --steps 10 --warmup 3 --cpu-seconds 0 --no-host-buffer --no-strdir --no-sparse"
 for i in 1 2; do
   for v in r06pre tree; do
     lib=$ROOT/distributedratelimiting.redis_amd/libtbe.so

@@ -10,7 +10,7 @@
 #   suite                 pytest -m gpu (the driver's command) + smoke()
 #   test:<path>[::<id>]   one GPU test file / test (e.g. test:tests/test_gpu_recreate.py)
 #   smoke                 __graft_entry__.smoke()
-#   bench:<workload>      bench.py --workload <workload> --steps 20 --warmup 5 (BENCH_ARGS appended)
+#   bench:<workload>      bench.py --full --workload <workload> --steps 20 --warmup 5 (BENCH_ARGS appended)
 #   driver                bench.py --steps 20 --warmup 5, as the driver runs it
 #   prof:<workload>       rocprofv3 --kernel-trace --stats of that bench (CSV under gpurun_out/<TAG>_prof_<w>/)
 #   pmc:<w1,w2,...>       rocprofv3 --pmc passes (tools/pmc_passes.sh) + tools/pmc_summary.py
@@ -39,7 +39,7 @@ step() {   # step <name> <seconds> <command string>
 prof() {   # rocprofv3 with the program itself after -- (no launcher hop)
     local w=$1
     ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$OUT/${TAG}_prof_$w" -o run -- python3 "$ROOT/bench.py" --workload "$w" --steps 20 --warmup 5 \
+        -d "$OUT/${TAG}_prof_$w" -o run -- python3 "$ROOT/bench.py" --full --workload "$w" --steps 20 --warmup 5 \
         --cpu-seconds 0 --no-host-buffer --no-strdir ) > "$OUT/${TAG}_prof_$w.log" 2>&1
     local rc=$?
     echo "[prof:$w] rc=$rc"
@@ -63,7 +63,7 @@ for s in "$@"; do
             step "$n" 900 "$PYTEST '$t'" ;;
         bench:*)
             w=${s#bench:}
-            step "bench_$w" 500 "python -u bench.py --workload $w --steps 20 --warmup 5 ${BENCH_ARGS:-}" ;;
+            step "bench_$w" 500 "python -u bench.py --full --workload $w --steps 20 --warmup 5 ${BENCH_ARGS:-}" ;;
         driver)
             step bench_driver 500 "python -u bench.py --steps 20 --warmup 5" ;;
         prof:*)
