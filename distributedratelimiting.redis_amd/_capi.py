@@ -38,7 +38,7 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_refresh_bound", "tbe_refresh_device", "tbe_approx_acquire_batch_device",
             "tbe_import_state", "tbe_queue_cancel", "tbe_alloc_host", "tbe_free_host",
             "tbe_approx_export_state", "tbe_approx_import_state", "tbe_wait_batch_tick_device",
-            "tbe_approx_sync_stream", "tbe_batch_format")
+            "tbe_approx_sync_stream", "tbe_batch_format", "tbe_expired_device")
 TBE_WAIT_FAILED, TBE_WAIT_GRANTED, TBE_WAIT_QUEUED, TBE_WAIT_REJECTED = 0, 1, 2, 3
 
 
@@ -101,6 +101,8 @@ def load(path: str = None) -> ctypes.CDLL:
                               POINTER(c_int32)]
     lib.tbe_export_state.restype = c_int32
     lib.tbe_export_state.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]
+    lib.tbe_expired_device.restype = c_int32
+    lib.tbe_expired_device.argtypes = [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_int32, c_void_p]
     lib.tbe_wait_batch.restype = c_int32
     lib.tbe_wait_batch.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_int64, c_void_p,
                                    c_void_p, POINTER(c_uint64)]
@@ -218,6 +220,10 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_sdir_set_hash_bits.argtypes = [c_void_p, ctypes.c_uint32]
     lib.tbe_sdir_set_mode.restype = c_int32
     lib.tbe_sdir_set_mode.argtypes = [c_void_p, c_int32]
+    lib.tbe_sdir_reclaim_device.restype = c_int32
+    lib.tbe_sdir_reclaim_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]
+    lib.tbe_sdir_reclaim.restype = c_int32
+    lib.tbe_sdir_reclaim.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_uint64, POINTER(c_uint64)]
     lib.tbe_numfmt_device.restype = c_int32
     lib.tbe_numfmt_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
     lib.tbe_layout.restype = c_int32

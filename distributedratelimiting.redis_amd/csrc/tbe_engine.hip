@@ -3663,6 +3663,24 @@ __global__ __launch_bounds__(kBlock) void k_count_queued(uint64_t n_keys, const 
     }
 }
 
+// dead[k - first] = 1 when key k's Redis hash would not exist at the time whose expiry
+// bound is exp_lt (req_time: t_us < exp_lt has lapsed, TB:232-235) and, for the queueing
+// kind, nothing is queued on it.  One 16-byte row per lane, byte flags out.  clear: a
+// lapsed row is rewritten absent, so that a later, earlier timestamp finds a full bucket.
+template <typename HW>
+__global__ __launch_bounds__(kBlock) void k_expired(Slot *__restrict__ table, const HW *__restrict__ qhdr,
+                                                    uint64_t first, uint64_t count, int64_t exp_lt, double cap,
+                                                    int32_t clear, uint8_t *__restrict__ dead) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    const Slot s = table[first + i];
+    const bool absent = s.t_us == kAbsent;
+    const bool gone = absent || s.t_us < exp_lt;
+    if (clear && gone && !absent) table[first + i] = Slot{cap, kAbsent};
+    const bool queued = qhdr && ((qh_widen(qhdr[first + i]) >> 16) & 0xFFFFu) != 0;
+    dead[i] = gone && !queued;
+}
+
 // ----------------------------------------------------------------------------- host side
 enum Stage { ST_HIST = 0, ST_COLSCAN, ST_SCATTER, ST_BOUNDS, ST_FOLD, ST_UNSCATTER, ST_HOT, ST_COUNT };
 
@@ -4883,6 +4901,42 @@ tbe_status tbe_export_state(tbe_engine *e, uint64_t first, uint64_t count, doubl
     for (uint64_t i = 0; i < count; ++i) {
         v[i] = tmp[i].v;
         t_us[i] = tmp[i].t_us;
+    }
+    return TBE_OK;
+}
+
+// The scan runs on the engine's stream, where every kernel that touches the table of a
+// pipelined engine runs and where tbe_export_state reads it; a caller's stream is joined
+// before (its batches, its use of d_dead) and after (the flags are ready for it).
+tbe_status tbe_expired_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, uint8_t *d_dead,
+                              int32_t clear, void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind == TBE_KIND_APPROXIMATE)
+        return fail(e, TBE_EINVAL, "the approximate kind's local tier has no expiry");
+    if (ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+    if (first > e->cfg.n_keys || count > e->cfg.n_keys - first)
+        return fail(e, TBE_EINVAL, "range out of bounds");
+    if (count == 0) return TBE_OK;
+    if (!d_dead) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    hipStream_t st = e->stream, caller = (hipStream_t)stream;
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_in, caller));
+        HIP_TRY(e, hipStreamWaitEvent(st, e->ev_in, 0));
+    }
+    const int64_t exp_lt = (ts_us / 1000 - e->params.ttl_ms) * 1000;
+    const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
+    if (e->cfg.kind == TBE_KIND_QUEUEING)
+        with_qhdr(e, [&](auto *qh) {
+            k_expired<<<blocks, kBlock, 0, st>>>(e->table, qh, first, count, exp_lt, e->params.cap, clear, d_dead);
+        });
+    else
+        k_expired<<<blocks, kBlock, 0, st>>>(e->table, (const uint64_t *)nullptr, first, count, exp_lt,
+                                             e->params.cap, clear, d_dead);
+    HIP_TRY(e, hipGetLastError());
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_out, st));
+        HIP_TRY(e, hipStreamWaitEvent(caller, e->ev_out, 0));
     }
     return TBE_OK;
 }

@@ -9,6 +9,7 @@
 //   sloc[s]   u64  bit 63 | (arena offset << 17) | length of the key's text, once assigned
 //   iloc[id]  u64  the same per id (tbe_sdir_key_of)
 //   arena     key text (resourceID bytes), each key at an 8-byte aligned offset
+//   free_ids  u32  stack of ids a reclaim took back (state[6] of them), popped before fresh counters
 //
 // A string's tag in probe round k (0..3) is (k << 62) | (H_k(string) & hmask), H_k a
 // 64-bit hash seeded from the prefix and k.  Tags are unique in the table: a batch's
@@ -275,15 +276,12 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_count(const uint64_t *__restric
     }
 }
 
-// Exclusive scans of the block counts and bytes (bytes into u64 bbase); state[0] ids
-// assigned, [1] error bits, [2] this batch's id base, [3] arena bytes used, [4] this
-// batch's arena base.
-__global__ __launch_bounds__(kSdScan) void k_sd_scan(uint32_t *__restrict__ bsum, const uint32_t *__restrict__ bbytes,
-                                                     uint64_t *__restrict__ bbase, uint32_t nblk,
-                                                     unsigned long long *__restrict__ state, uint64_t capacity,
-                                                     uint64_t arena_bytes) {
-    __shared__ uint32_t wsum[kSdScan / 64];
-    __shared__ unsigned long long part[kSdScan];
+// Exclusive scans of per-block counts (in place) and bytes (into u64 bbase) by one block of
+// kSdScan threads.  Returns the sum of the counts; thread kSdScan - 1 gets the sum of the
+// bytes in *bytes.
+__device__ __forceinline__ uint32_t sd_scan_blocks(uint32_t *__restrict__ bsum, const uint32_t *__restrict__ bbytes,
+                                                   uint64_t *__restrict__ bbase, uint32_t nblk, uint32_t *wsum,
+                                                   unsigned long long *part, unsigned long long *bytes) {
     const uint32_t t = threadIdx.x;
     const uint32_t per = (nblk + kSdScan - 1) / kSdScan;
     uint32_t sum = 0;
@@ -320,15 +318,37 @@ __global__ __launch_bounds__(kSdScan) void k_sd_scan(uint32_t *__restrict__ bsum
             brun += bbytes[j];
         }
     }
-    if (t == kSdScan - 1) {
-        const unsigned long long before = state[0];
-        state[2] = before;
-        unsigned long long after = before + tot;
-        if (after > capacity) {
-            after = capacity;
+    *bytes = brun;
+    return tot;
+}
+
+// The batch's block scans and the directory's counters.  state[0] new keys ever assigned
+// (only grows: the warm-path choice reads its deltas), [1] error bits, [2] the fresh
+// counter before this batch, [3] arena bytes used, [4] this batch's arena base, [5] fresh
+// counters used, [6] ids on the free stack, [7] the stack's height before this batch.
+// Keys held = [5] - [6]; room for new keys = [6] + capacity - [5].
+__global__ __launch_bounds__(kSdScan) void k_sd_scan(uint32_t *__restrict__ bsum, const uint32_t *__restrict__ bbytes,
+                                                     uint64_t *__restrict__ bbase, uint32_t nblk,
+                                                     unsigned long long *__restrict__ state, uint64_t capacity,
+                                                     uint64_t arena_bytes) {
+    __shared__ uint32_t wsum[kSdScan / 64];
+    __shared__ unsigned long long part[kSdScan];
+    unsigned long long brun;
+    const uint32_t tot = sd_scan_blocks(bsum, bbytes, bbase, nblk, wsum, part, &brun);
+    if (threadIdx.x == kSdScan - 1) {
+        const unsigned long long fresh = state[5], nfree = state[6];
+        const unsigned long long room = nfree + capacity - fresh;
+        unsigned long long take = tot;
+        if (take > room) {
+            take = room;
             state[1] |= kErrRange;
         }
-        state[0] = after;
+        const unsigned long long pop = take < nfree ? take : nfree;   // freed ids go first
+        state[2] = fresh;
+        state[7] = nfree;
+        state[6] = nfree - pop;
+        state[5] = fresh + (take - pop);
+        state[0] += take;
         const unsigned long long abefore = state[3];
         state[4] = abefore;
         unsigned long long aafter = abefore + brun;
@@ -340,8 +360,10 @@ __global__ __launch_bounds__(kSdScan) void k_sd_scan(uint32_t *__restrict__ bsum
     }
 }
 
-// Assign ids (counter = base + rank among the batch's new keys, id = its bijection) and
-// store the new keys' text; beyond capacity or arena, none.
+// Assign ids and store the new keys' text; beyond capacity or arena, none.  Rank r among
+// the batch's new keys takes the free stack's r-th id from the top, and once the stack
+// (nfree ids before the batch) is used up the fresh counter fresh + r - nfree (id = its
+// bijection).
 __global__ __launch_bounds__(kSdBlock) void k_sd_assign(SdBatch B, uint64_t n, const uint32_t *__restrict__ slot_of,
                                                         uint32_t *__restrict__ sid, const uint32_t *__restrict__ sfirst,
                                                         uint64_t *__restrict__ sloc, uint64_t *__restrict__ iloc,
@@ -349,7 +371,8 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_assign(SdBatch B, uint64_t n, c
                                                         const uint64_t *__restrict__ bbase,
                                                         const unsigned long long *__restrict__ state,
                                                         uint64_t capacity, uint64_t arena_bytes, uint64_t imask,
-                                                        uint32_t ish, const uint32_t *__restrict__ list = nullptr,
+                                                        uint32_t ish, const uint32_t *__restrict__ free_ids,
+                                                        const uint32_t *__restrict__ list = nullptr,
                                                         const uint32_t *__restrict__ list_n = nullptr) {
     __shared__ uint32_t wsum[kSdBlock / 64];
     constexpr int PER = kSdTile / kSdBlock;
@@ -369,13 +392,16 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_assign(SdBatch B, uint64_t n, c
     uint32_t r = block_excl_scan<kSdBlock>(c, wsum, &tc);   // every thread has read sid before it returns
     __syncthreads();
     uint32_t rb = block_excl_scan<kSdBlock>(nb, wsum, &tb);
-    const uint64_t c0 = (uint64_t)state[2] + bsum[blockIdx.x];
+    const uint64_t fresh = state[2], nfree = state[7];
+    const uint64_t r0 = bsum[blockIdx.x];
     const uint64_t a0 = (uint64_t)state[4] + bbase[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         if (!nw[k]) continue;
         const uint64_t i = iv[k];
-        const uint64_t counter = c0 + r++;
+        const uint64_t rank = r0 + r++;
+        const bool reuse = rank < nfree;
+        const uint64_t counter = reuse ? 0 : fresh + (rank - nfree);
         const uint64_t off = B.offs[i];
         const uint32_t len = (uint32_t)(B.offs[i + 1] - off);
         const uint64_t aoff = a0 + rb;
@@ -383,7 +409,7 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_assign(SdBatch B, uint64_t n, c
         if (counter >= capacity || aoff + ((len + 7) & ~7u) > arena_bytes) continue;
         for (uint32_t w = 0; 8u * w < len; ++w)
             *reinterpret_cast<uint64_t *>(arena + aoff + 8ull * w) = sd_word(B.bytes, B.safe, off, len, w);
-        const uint32_t id = (uint32_t)scramble_walk(counter, capacity, imask, ish);
+        const uint32_t id = reuse ? free_ids[nfree - 1 - rank] : (uint32_t)scramble_walk(counter, capacity, imask, ish);
         const uint64_t loc = kLocValid | (aoff << 17) | len;
         sloc[slot_of[i]] = loc;
         iloc[id] = loc;
@@ -557,6 +583,260 @@ __global__ void k_sd_init(uint64_t *__restrict__ stag, uint32_t *__restrict__ si
     }
 }
 
+// ---------------------------------------------------------------- reclaim
+// Removing a key in place would break the probe rounds: a key sits in round k because its
+// earlier rounds' tags were taken, so an emptied slot ends other keys' lookups early, and a
+// slot left tagged without an id is claimed again by the first string that hashes to it.
+// A reclaim therefore rebuilds the table from its survivors (tbe_sdir_reclaim_device):
+//   1. vict[id] = assigned, flagged dead and not kept; the victims, in ascending id
+//      order (block counts + scan), go onto the free stack and lose their iloc;
+//   2. the surviving slots are compacted in slot order: their text moves to the second
+//      arena at offsets from a scan of the rounded lengths, their {tag, id, new loc} to a
+//      record list, and the ones that sat in a round > 0 to the list of movers;
+//   3. the slot table is reset and the survivors are put back.  A survivor may always
+//      return to its own tag (tags were unique), and a mover first tries the earlier
+//      rounds' tags, which removals may have freed: it takes the first round whose tag no
+//      one holds, exactly the rule an assign places a new string by.  Round 0's owners
+//      go in first (k_rc_place0); k_rc_place(j) then lets every unplaced mover try round
+//      j and, failing that, puts round j + 1's owners back, so a try at round j + 1 (the
+//      next launch) finds all of them.  No survivor ends in a later round than before.
+__global__ void k_rc_flag(uint64_t capacity, const uint64_t *__restrict__ iloc, const uint8_t *__restrict__ dead,
+                          uint8_t *__restrict__ vict) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; id < capacity; id += stride)
+        vict[id] = (iloc[id] & kLocValid) && dead[id];
+}
+
+__global__ void k_rc_keep(const uint64_t *__restrict__ keep, uint64_t n_keep, uint64_t capacity,
+                          uint8_t *__restrict__ vict) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_keep; j += stride)
+        if (keep[j] < capacity) vict[keep[j]] = 0;
+}
+
+// Victims per block of kSdTile ids (thread-contiguous, as k_sd_count).
+__global__ __launch_bounds__(kSdBlock) void k_rc_vcount(uint64_t capacity, const uint8_t *__restrict__ vict,
+                                                        uint32_t *__restrict__ bv) {
+    __shared__ uint32_t wsum[kSdBlock / 64];
+    constexpr int PER = kSdTile / kSdBlock;
+    const uint64_t base = (uint64_t)blockIdx.x * kSdTile + (uint64_t)threadIdx.x * PER;
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) c += base + k < capacity && vict[base + k];
+    uint32_t tot;
+    (void)block_excl_scan<kSdBlock>(c, wsum, &tot);
+    if (threadIdx.x == 0) bv[blockIdx.x] = tot;
+}
+
+// The victims onto the free stack in ascending id order (bv scanned); their ids read as
+// never assigned from here on.
+__global__ __launch_bounds__(kSdBlock) void k_rc_vpush(uint64_t capacity, const uint8_t *__restrict__ vict,
+                                                       const uint32_t *__restrict__ bv,
+                                                       const unsigned long long *__restrict__ state,
+                                                       uint32_t *__restrict__ free_ids, uint64_t *__restrict__ iloc) {
+    __shared__ uint32_t wsum[kSdBlock / 64];
+    constexpr int PER = kSdTile / kSdBlock;
+    const uint64_t base = (uint64_t)blockIdx.x * kSdTile + (uint64_t)threadIdx.x * PER;
+    bool v[PER];
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        v[k] = base + k < capacity && vict[base + k];
+        c += v[k];
+    }
+    uint32_t tot;
+    uint64_t at = (uint64_t)state[6] + bv[blockIdx.x] + block_excl_scan<kSdBlock>(c, wsum, &tot);
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+        if (v[k]) {
+            free_ids[at++] = (uint32_t)(base + k);
+            iloc[base + k] = 0;
+        }
+}
+
+__device__ __forceinline__ bool rc_survives(const uint32_t *__restrict__ sid, const uint8_t *__restrict__ vict,
+                                            uint64_t s, uint64_t nslots) {
+    if (s >= nslots) return false;
+    const uint32_t id = sid[s];
+    return id != kNoId && !vict[id];
+}
+
+// Surviving keys and their arena bytes per block of kSdTile slots.
+__global__ __launch_bounds__(kSdBlock) void k_rc_scount(uint64_t nslots, const uint32_t *__restrict__ sid,
+                                                        const uint64_t *__restrict__ sloc,
+                                                        const uint8_t *__restrict__ vict, uint32_t *__restrict__ bs,
+                                                        uint32_t *__restrict__ bb) {
+    __shared__ uint32_t wsum[kSdBlock / 64];
+    constexpr int PER = kSdTile / kSdBlock;
+    const uint64_t base = (uint64_t)blockIdx.x * kSdTile + (uint64_t)threadIdx.x * PER;
+    uint32_t c = 0, nb = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+        if (rc_survives(sid, vict, base + k, nslots)) {
+            ++c;
+            nb += (loc_len(sloc[base + k]) + 7) & ~7u;
+        }
+    uint32_t tc, tb;
+    (void)block_excl_scan<kSdBlock>(c, wsum, &tc);
+    __syncthreads();
+    (void)block_excl_scan<kSdBlock>(nb, wsum, &tb);
+    if (threadIdx.x == 0) {
+        bs[blockIdx.x] = tc;
+        bb[blockIdx.x] = tb;
+    }
+}
+
+// Scans of the survivors' block counts and bytes, and the counters after the reclaim:
+// rc_n[0] victims (k_sd_xscan), [1] survivors, [2] movers listed so far.
+__global__ __launch_bounds__(kSdScan) void k_rc_scan(uint32_t *__restrict__ bs, const uint32_t *__restrict__ bb,
+                                                     uint64_t *__restrict__ base, uint32_t nblk,
+                                                     unsigned long long *__restrict__ state,
+                                                     uint32_t *__restrict__ rc_n, uint64_t *__restrict__ n_reclaimed) {
+    __shared__ uint32_t wsum[kSdScan / 64];
+    __shared__ unsigned long long part[kSdScan];
+    unsigned long long bytes;
+    const uint32_t tot = sd_scan_blocks(bs, bb, base, nblk, wsum, part, &bytes);
+    if (threadIdx.x == kSdScan - 1) {
+        rc_n[1] = tot;
+        rc_n[2] = 0;
+        state[3] = bytes;          // the arena holds the survivors' text only
+        state[6] += rc_n[0];
+        if (n_reclaimed) *n_reclaimed = rc_n[0];
+    }
+}
+
+// The survivors, in slot order: text to the second arena, {tag, id, new loc} to the record
+// list (rank = bs[block] + rank in block), the new loc to iloc; a survivor of a round > 0
+// is listed as a mover (wave-aggregated appends).
+__global__ __launch_bounds__(kSdBlock) void k_rc_move(uint64_t nslots, const uint64_t *__restrict__ stag,
+                                                      const uint32_t *__restrict__ sid,
+                                                      const uint64_t *__restrict__ sloc,
+                                                      const uint8_t *__restrict__ vict,
+                                                      const uint32_t *__restrict__ bs,
+                                                      const uint64_t *__restrict__ bbase,
+                                                      const uint8_t *__restrict__ arena, uint8_t *__restrict__ arena2,
+                                                      uint64_t *__restrict__ sv_tag, uint32_t *__restrict__ sv_id,
+                                                      uint64_t *__restrict__ sv_loc, uint64_t *__restrict__ iloc,
+                                                      uint32_t *__restrict__ movers, uint32_t *__restrict__ rc_n) {
+    __shared__ uint32_t wsum[kSdBlock / 64];
+    constexpr int PER = kSdTile / kSdBlock;
+    const uint64_t base = (uint64_t)blockIdx.x * kSdTile + (uint64_t)threadIdx.x * PER;
+    bool sv[PER];
+    uint32_t c = 0, nb = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        sv[k] = rc_survives(sid, vict, base + k, nslots);
+        c += sv[k];
+        nb += sv[k] ? (loc_len(sloc[base + k]) + 7) & ~7u : 0u;
+    }
+    uint32_t tc, tb;
+    uint32_t r = bs[blockIdx.x] + block_excl_scan<kSdBlock>(c, wsum, &tc);
+    __syncthreads();
+    uint64_t at = bbase[blockIdx.x] + block_excl_scan<kSdBlock>(nb, wsum, &tb);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        bool mover = false;
+        uint32_t rank = 0;
+        if (sv[k]) {
+            const uint64_t s = base + k;
+            const uint64_t loc = sloc[s], tag = stag[s];
+            const uint32_t id = sid[s], len = loc_len(loc);
+            const uint64_t from = loc_off(loc);
+            for (uint32_t w = 0; 8u * w < len; ++w)
+                *reinterpret_cast<uint64_t *>(arena2 + at + 8ull * w) =
+                    *reinterpret_cast<const uint64_t *>(arena + from + 8ull * w);
+            const uint64_t nloc = kLocValid | (at << 17) | len;
+            at += (len + 7) & ~7u;
+            rank = r++;
+            sv_tag[rank] = tag;
+            sv_id[rank] = id;
+            sv_loc[rank] = nloc;
+            iloc[id] = nloc;
+            mover = (tag >> 62) != 0;
+        }
+        const uint64_t m = __ballot(mover);
+        if (m) {
+            const int leader = __ffsll((long long)m) - 1;
+            uint32_t mb = 0;
+            if ((int)(threadIdx.x & 63) == leader) mb = atomicAdd(&rc_n[2], (uint32_t)__popcll(m));
+            mb = __shfl(mb, leader, 64);
+            if (mover) movers[mb + __popcll(m & lanemask_lt())] = rank;
+        }
+    }
+}
+
+// Claim the slot of a tag no one holds: the slot, or kNoId when the tag is in the table.
+__device__ __forceinline__ uint32_t rc_insert(uint64_t tag, uint64_t *__restrict__ stag, uint64_t smask) {
+    uint64_t h = mix64(tag) & smask;
+    for (uint64_t probe = 0; probe <= smask; ++probe) {
+        const uint64_t cur = stag[h];
+        if (cur == tag) return kNoId;
+        if (cur == kEmptyTag) {
+            const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&stag[h]), kEmptyTag, tag);
+            if (prev == kEmptyTag) return (uint32_t)h;
+            if (prev == tag) return kNoId;
+        }
+        h = (h + 1) & smask;
+    }
+    return kNoId;
+}
+
+// Round 0's owners back to their tags.
+__global__ __launch_bounds__(kSdBlock) void k_rc_place0(const uint32_t *__restrict__ rc_n,
+                                                        const uint64_t *__restrict__ sv_tag,
+                                                        const uint32_t *__restrict__ sv_id,
+                                                        const uint64_t *__restrict__ sv_loc,
+                                                        uint64_t *__restrict__ stag, uint32_t *__restrict__ sid,
+                                                        uint64_t *__restrict__ sloc, uint64_t smask,
+                                                        unsigned long long *__restrict__ err) {
+    const uint64_t count = rc_n[1];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < count; r += stride) {
+        const uint64_t tag = sv_tag[r];
+        if (tag >> 62) continue;
+        const uint32_t h = rc_insert(tag, stag, smask);
+        if (h == kNoId) {
+            atomicOr(err, kErrRounds);
+            continue;
+        }
+        sloc[h] = sv_loc[r];
+        sid[h] = sv_id[r];
+    }
+}
+
+// Every unplaced mover tries round j's tag of its string; one that fails and owned a tag
+// of round j + 1 returns to it.  A placed mover's record tag is set to kEmptyTag.
+__global__ __launch_bounds__(kSdBlock) void k_rc_place(uint32_t j, const uint32_t *__restrict__ rc_n,
+                                                       const uint32_t *__restrict__ movers,
+                                                       uint64_t *__restrict__ sv_tag,
+                                                       const uint32_t *__restrict__ sv_id,
+                                                       const uint64_t *__restrict__ sv_loc, SdArena A, SdParams P,
+                                                       uint64_t *__restrict__ stag, uint32_t *__restrict__ sid,
+                                                       uint64_t *__restrict__ sloc, uint64_t smask,
+                                                       unsigned long long *__restrict__ err) {
+    const uint64_t count = rc_n[2];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += stride) {
+        const uint32_t r = movers[t];
+        const uint64_t own = sv_tag[r];
+        if (own == kEmptyTag) continue;
+        const uint64_t loc = sv_loc[r];
+        const uint64_t tag = sd_tag(j, sd_hash(A.bytes, A.safe, loc_off(loc), loc_len(loc), P.seed[j]), P.hmask);
+        uint32_t h = rc_insert(tag, stag, smask);
+        if (h == kNoId) {
+            if ((own >> 62) != j + 1) continue;
+            h = rc_insert(own, stag, smask);
+            if (h == kNoId) {
+                atomicOr(err, kErrRounds);
+                continue;
+            }
+        }
+        sloc[h] = loc;
+        sid[h] = sv_id[r];
+        sv_tag[r] = kEmptyTag;
+    }
+}
+
 unsigned sd_grid(uint64_t n, unsigned block, unsigned cap = 8192) {
     const uint64_t g = (n + block - 1) / block;
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
@@ -589,6 +869,17 @@ struct tbe_string_directory {
     uint64_t *iloc = nullptr;
     uint8_t *arena = nullptr;
     unsigned long long *state = nullptr;   // see k_sd_scan
+    // reclaim (allocated by the first one, sd_reclaim_scratch)
+    uint32_t *free_ids = nullptr;          // the free stack, capacity ids
+    uint8_t *arena2 = nullptr;             // the arena the next reclaim compacts into
+    uint8_t *vict = nullptr;               // [capacity]
+    uint64_t *sv_tag = nullptr, *sv_loc = nullptr;
+    uint32_t *sv_id = nullptr, *movers = nullptr;   // survivor records / movers, capacity each
+    uint32_t *rc_bv = nullptr, *rc_bs = nullptr, *rc_bb = nullptr, *rc_n = nullptr;
+    uint64_t *rc_base = nullptr;
+    uint8_t *rc_dead = nullptr;            // tbe_sdir_reclaim: the engine's flags, its keep list, its count
+    uint64_t *rc_keep = nullptr, *rc_count = nullptr;
+    uint64_t rc_keep_cap = 0;
     // per-batch scratch
     uint64_t tmp_cap = 0;
     uint32_t *slot_of = nullptr;
@@ -642,6 +933,35 @@ tbe_status sd_scratch(tbe_string_directory *d, uint64_t n) {
         return TBE_ENOMEM;
     }
     d->tmp_cap = cap;
+    return TBE_OK;
+}
+
+tbe_status sd_reclaim_scratch(tbe_string_directory *d) {
+    if (d->free_ids) return TBE_OK;
+    const uint64_t cap = d->capacity;
+    const uint64_t nbi = (cap + kSdTile - 1) / kSdTile, nbs = (d->nslots + kSdTile - 1) / kSdTile;
+    const bool ok = hipMalloc(&d->arena2, d->arena_alloc) == hipSuccess &&
+                    hipMalloc(&d->vict, cap) == hipSuccess &&
+                    hipMalloc(&d->sv_tag, cap * sizeof(uint64_t)) == hipSuccess &&
+                    hipMalloc(&d->sv_loc, cap * sizeof(uint64_t)) == hipSuccess &&
+                    hipMalloc(&d->sv_id, cap * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&d->movers, cap * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&d->rc_bv, nbi * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&d->rc_bs, nbs * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&d->rc_bb, nbs * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&d->rc_base, nbs * sizeof(uint64_t)) == hipSuccess &&
+                    hipMalloc(&d->rc_n, 4 * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&d->free_ids, cap * sizeof(uint32_t)) == hipSuccess;   // last: marks the set complete
+    if (!ok || hipMemset(d->arena2, 0, d->arena_alloc) != hipSuccess) {
+        for (void *p : {(void *)d->arena2, (void *)d->vict, (void *)d->sv_tag, (void *)d->sv_loc, (void *)d->sv_id,
+                        (void *)d->movers, (void *)d->rc_bv, (void *)d->rc_bs, (void *)d->rc_bb, (void *)d->rc_base,
+                        (void *)d->rc_n, (void *)d->free_ids})
+            if (p) (void)hipFree(p);
+        d->arena2 = d->vict = nullptr;
+        d->sv_tag = d->sv_loc = d->rc_base = nullptr;
+        d->sv_id = d->movers = d->rc_bv = d->rc_bs = d->rc_bb = d->rc_n = d->free_ids = nullptr;
+        return TBE_ENOMEM;
+    }
     return TBE_OK;
 }
 
@@ -714,7 +1034,10 @@ void tbe_sdir_destroy(tbe_string_directory *d) {
     if (d->ev_state) (void)hipEventDestroy(d->ev_state);
     for (void *p : {(void *)d->stag, (void *)d->sid, (void *)d->sfirst, (void *)d->sloc, (void *)d->iloc,
                     (void *)d->arena, (void *)d->state, (void *)d->list_n, (void *)d->d_bytes, (void *)d->d_offs,
-                    (void *)d->d_ids})
+                    (void *)d->d_ids, (void *)d->arena2, (void *)d->vict, (void *)d->sv_tag, (void *)d->sv_loc,
+                    (void *)d->sv_id, (void *)d->movers, (void *)d->rc_bv, (void *)d->rc_bs, (void *)d->rc_bb,
+                    (void *)d->rc_base, (void *)d->rc_n, (void *)d->free_ids, (void *)d->rc_dead, (void *)d->rc_keep,
+                    (void *)d->rc_count})
         if (p) (void)hipFree(p);
     delete d;
 }
@@ -782,8 +1105,8 @@ tbe_status tbe_sdir_assign_device(tbe_string_directory *d, const uint8_t *d_byte
                                           miss_n);
     k_sd_scan<<<1, kSdScan, 0, st>>>(d->bsum, d->bbytes, d->bbase, nblk, d->state, d->capacity, d->arena_bytes);
     k_sd_assign<<<nblk, kSdBlock, 0, st>>>(B, n, d->slot_of, d->sid, d->sfirst, d->sloc, d->iloc, d->arena, d->bsum,
-                                           d->bbase, d->state, d->capacity, d->arena_bytes, d->imask, d->ish, miss,
-                                           miss_n);
+                                           d->bbase, d->state, d->capacity, d->arena_bytes, d->imask, d->ish,
+                                           d->free_ids, miss, miss_n);
     k_sd_gather<<<sd_grid(n, 256), 256, 0, st>>>(d->slot_of, n, d->sid, d_ids, miss, miss_n);
     d->since_n += n;
     if (!d->state_pending) {
@@ -848,11 +1171,71 @@ tbe_status tbe_sdir_assign(tbe_string_directory *d, const uint8_t *bytes, uint64
 tbe_status tbe_sdir_size(tbe_string_directory *d, uint64_t *n_ids) {
     if (!d || !n_ids) return TBE_EINVAL;
     if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TBE_EDEVICE;
-    unsigned long long st[2] = {0, 0};
+    unsigned long long st[8] = {0};
     if (hipMemcpy(st, d->state, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) return TBE_EDEVICE;
-    *n_ids = st[0];
+    *n_ids = st[5] - st[6];   // counters handed out less the ids waiting on the free stack
     if (st[1] & (kErrRange | kErrRounds | kErrArena | kErrFull)) return TBE_ERANGE;
     return (st[1] & kErrBatch) ? TBE_EINVAL : TBE_OK;
+}
+
+tbe_status tbe_sdir_reclaim_device(tbe_string_directory *d, const uint8_t *d_dead, const uint64_t *d_keep_ids,
+                                   uint64_t n_keep, uint64_t *d_n_reclaimed, void *stream) {
+    if (!d || !d_dead || (n_keep && !d_keep_ids)) return TBE_EINVAL;
+    if (hipSetDevice(d->device) != hipSuccess) return TBE_EDEVICE;
+    const tbe_status rc = sd_reclaim_scratch(d);
+    if (rc != TBE_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t cap = d->capacity, ns = d->nslots, smask = ns - 1;
+    const uint32_t nbi = (uint32_t)((cap + kSdTile - 1) / kSdTile), nbs = (uint32_t)((ns + kSdTile - 1) / kSdTile);
+    unsigned long long *err = d->state + 1;
+    k_rc_flag<<<sd_grid(cap, 256), 256, 0, st>>>(cap, d->iloc, d_dead, d->vict);
+    if (n_keep) k_rc_keep<<<sd_grid(n_keep, 256), 256, 0, st>>>(d_keep_ids, n_keep, cap, d->vict);
+    k_rc_vcount<<<nbi, kSdBlock, 0, st>>>(cap, d->vict, d->rc_bv);
+    k_sd_xscan<<<1, kSdScan, 0, st>>>(d->rc_bv, nbi, d->rc_n);
+    k_rc_vpush<<<nbi, kSdBlock, 0, st>>>(cap, d->vict, d->rc_bv, d->state, d->free_ids, d->iloc);
+    k_rc_scount<<<nbs, kSdBlock, 0, st>>>(ns, d->sid, d->sloc, d->vict, d->rc_bs, d->rc_bb);
+    k_rc_scan<<<1, kSdScan, 0, st>>>(d->rc_bs, d->rc_bb, d->rc_base, nbs, d->state, d->rc_n, d_n_reclaimed);
+    k_rc_move<<<nbs, kSdBlock, 0, st>>>(ns, d->stag, d->sid, d->sloc, d->vict, d->rc_bs, d->rc_base, d->arena,
+                                        d->arena2, d->sv_tag, d->sv_id, d->sv_loc, d->iloc, d->movers, d->rc_n);
+    k_sd_init<<<sd_grid(ns, 256), 256, 0, st>>>(d->stag, d->sid, d->sfirst, ns);
+    std::swap(d->arena, d->arena2);   // every later call reads the compacted arena
+    const SdArena A{d->arena, d->arena_alloc & ~7ull};
+    k_rc_place0<<<sd_grid(cap, kSdBlock), kSdBlock, 0, st>>>(d->rc_n, d->sv_tag, d->sv_id, d->sv_loc, d->stag, d->sid,
+                                                            d->sloc, smask, err);
+    for (uint32_t j = 0; j + 1 < (uint32_t)kRounds; ++j)
+        k_rc_place<<<kListGrid, kSdBlock, 0, st>>>(j, d->rc_n, d->movers, d->sv_tag, d->sv_id, d->sv_loc, A, d->P,
+                                                   d->stag, d->sid, d->sloc, smask, err);
+    return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
+}
+
+tbe_status tbe_sdir_reclaim(tbe_string_directory *d, tbe_engine *engine, int64_t ts_us, const uint64_t *keep_ids,
+                            uint64_t n_keep, uint64_t *n_reclaimed) {
+    if (!d || !engine || !n_reclaimed || (n_keep && !keep_ids)) return TBE_EINVAL;
+    *n_reclaimed = 0;
+    // after every assign and engine batch, whatever its stream
+    if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TBE_EDEVICE;
+    if ((!d->rc_dead && hipMalloc(&d->rc_dead, d->capacity) != hipSuccess) ||
+        (!d->rc_count && hipMalloc(&d->rc_count, sizeof(uint64_t)) != hipSuccess))
+        return TBE_ENOMEM;
+    if (n_keep > d->rc_keep_cap) {
+        if (d->rc_keep) (void)hipFree(d->rc_keep);
+        d->rc_keep = nullptr;
+        d->rc_keep_cap = 0;
+        if (hipMalloc(&d->rc_keep, n_keep * sizeof(uint64_t)) != hipSuccess) return TBE_ENOMEM;
+        d->rc_keep_cap = n_keep;
+    }
+    if (n_keep && hipMemcpy(d->rc_keep, keep_ids, n_keep * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        return TBE_EDEVICE;
+    // the engine must hold a row for every id of the directory (TBE_EINVAL otherwise)
+    tbe_status rc = tbe_expired_device(engine, ts_us, 0, d->capacity, d->rc_dead, 1, nullptr);
+    if (rc != TBE_OK) return rc;
+    if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TBE_EDEVICE;
+    rc = tbe_sdir_reclaim_device(d, d->rc_dead, d->rc_keep, n_keep, d->rc_count, nullptr);
+    if (rc != TBE_OK) return rc;
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(n_reclaimed, d->rc_count, sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return TBE_EDEVICE;
+    return TBE_OK;
 }
 
 tbe_status tbe_sdir_key_of(tbe_string_directory *d, uint64_t id, uint8_t *buf, uint64_t cap, uint64_t *len) {

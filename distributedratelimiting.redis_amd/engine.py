@@ -177,6 +177,15 @@ class TokenBucketEngine:
         self._check(self._lib.tbe_import_state(self.handle, first, v.shape[0], v.ctypes.data,
                                                t_us.ctypes.data))
 
+    def expired_device(self, ts_us: int, d_dead, first: int = 0, clear: bool = False,
+                       stream: Optional[int] = None) -> None:
+        """d_dead (uint8 device tensor): d_dead[k - first] = 1 for every key of [first, first +
+        len) whose Redis hash would not exist at ts_us (tbe_expired_device); clear=True also
+        rewrites the lapsed rows absent.  Enqueued, not synchronised; stream as in
+        ``acquire_batch_device``."""
+        self._check(self._lib.tbe_expired_device(self.handle, ts_us, first, d_dead.numel(), d_dead.data_ptr(),
+                                                 1 if clear else 0, stream))
+
     def layout(self) -> dict:
         """{passes, r_bits, packed, hot, pipeline, narrow, medium, fold_records, digit_stream, rerank,
         narrow_pass0, queue_header_32} of this engine's

@@ -185,6 +185,22 @@ tbe_status tbe_export_state(tbe_engine *engine, uint64_t first, uint64_t count, 
 tbe_status tbe_import_state(tbe_engine *engine, uint64_t first, uint64_t count, const double *v,
                             const int64_t *t_us);
 
+/* Which keys of [first, first + count) no longer exist in the store: the device-side
+ * counterpart of Redis dropping a bucket key at its EXPIRE (TB:232-235).  d_dead (device
+ * memory, count bytes) gets d_dead[k - first] = 1 when key k's hash would not exist at
+ * ts_us, else 0: its row is absent, or has lapsed by the rule tbe_query and the script
+ * replay use, t_us < 1000 * (ts_us / 1000 - ttl_ms).  Queueing kind: a key with queued
+ * requests is never dead.  Approximate kind: TBE_EINVAL (its local tier is in-process
+ * state without an expiry).  clear != 0 also rewrites every lapsed row of the range
+ * absent, which decides identically at ts_us and later but keeps a reused key id on a
+ * full bucket even if a later timestamp steps back before the lapse.
+ * Ordered after every batch already enqueued on the engine (pipelined ones included),
+ * as tbe_export_state is; `stream` as in tbe_acquire_batch_device: the scan waits for
+ * work enqueued on it and it waits for the flags.  ts_us < 0 or a range past n_keys:
+ * TBE_EINVAL, nothing written. */
+tbe_status tbe_expired_device(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                              uint8_t *d_dead, int32_t clear, void *stream);
+
 /* ---------------------------------------------------------------- TokenBucketWithQueue
  * Engines created with kind = TBE_KIND_QUEUEING.  The reference limiter
  * (TokenBucketWithQueue/RedisTokenBucketRateLimiter.cs, "Q") is commented out and does
