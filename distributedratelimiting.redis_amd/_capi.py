@@ -38,7 +38,8 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_refresh_bound", "tbe_refresh_device", "tbe_approx_acquire_batch_device",
             "tbe_import_state", "tbe_queue_cancel", "tbe_alloc_host", "tbe_free_host",
             "tbe_approx_export_state", "tbe_approx_import_state", "tbe_wait_batch_tick_device",
-            "tbe_approx_sync_stream", "tbe_batch_format", "tbe_expired_device")
+            "tbe_approx_sync_stream", "tbe_batch_format", "tbe_expired_device",
+            "tbe_export_live_device", "tbe_export_live", "tbe_import_rows_device", "tbe_import_rows")
 TBE_WAIT_FAILED, TBE_WAIT_GRANTED, TBE_WAIT_QUEUED, TBE_WAIT_REJECTED = 0, 1, 2, 3
 
 
@@ -103,6 +104,16 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_export_state.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]
     lib.tbe_expired_device.restype = c_int32
     lib.tbe_expired_device.argtypes = [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_int32, c_void_p]
+    lib.tbe_export_live_device.restype = c_int32
+    lib.tbe_export_live_device.argtypes = [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p,
+                                           c_uint64, c_void_p, c_void_p]
+    lib.tbe_export_live.restype = c_int32
+    lib.tbe_export_live.argtypes = [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p,
+                                    c_uint64, POINTER(c_uint64)]
+    lib.tbe_import_rows_device.restype = c_int32
+    lib.tbe_import_rows_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]
+    lib.tbe_import_rows.restype = c_int32
+    lib.tbe_import_rows.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
     lib.tbe_wait_batch.restype = c_int32
     lib.tbe_wait_batch.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_int64, c_void_p,
                                    c_void_p, POINTER(c_uint64)]
@@ -193,6 +204,8 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_dir_assign_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]
     lib.tbe_dir_lookup_device.restype = c_int32
     lib.tbe_dir_lookup_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]
+    lib.tbe_dir_keys_of_device.restype = c_int32
+    lib.tbe_dir_keys_of_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]
     lib.tbe_dir_size.restype = c_int32
     lib.tbe_dir_size.argtypes = [c_void_p, POINTER(c_uint64)]
     lib.tbe_dir_state_async.restype = c_int32
@@ -216,6 +229,10 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_sdir_size.argtypes = [c_void_p, POINTER(c_uint64)]
     lib.tbe_sdir_key_of.restype = c_int32
     lib.tbe_sdir_key_of.argtypes = [c_void_p, c_uint64, c_void_p, c_uint64, POINTER(c_uint64)]
+    lib.tbe_sdir_text_lengths_device.restype = c_int32
+    lib.tbe_sdir_text_lengths_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]
+    lib.tbe_sdir_text_device.restype = c_int32
+    lib.tbe_sdir_text_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]
     lib.tbe_sdir_set_hash_bits.restype = c_int32
     lib.tbe_sdir_set_hash_bits.argtypes = [c_void_p, ctypes.c_uint32]
     lib.tbe_sdir_set_mode.restype = c_int32

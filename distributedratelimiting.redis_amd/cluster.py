@@ -328,6 +328,11 @@ class DeviceDirectory:
         """ids of known keys, -1 (UINT64_MAX) for others; assigns nothing."""
         return self._run(self._lib.tbe_dir_lookup_device, d_keys)
 
+    def keys_of(self, d_ids):
+        """int64 device tensor of ids -> int64 device tensor of the keys holding them, -1
+        (UINT64_MAX) for an id no key holds (tbe_dir_keys_of_device)."""
+        return self._run(self._lib.tbe_dir_keys_of_device, d_ids)
+
     def size(self) -> int:
         import ctypes
         from . import _capi

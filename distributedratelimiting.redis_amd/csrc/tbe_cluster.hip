@@ -359,6 +359,33 @@ __global__ void k_dir_init(uint64_t *__restrict__ skey, uint32_t *__restrict__ s
     }
 }
 
+// Reverse lookup (tbe_dir_keys_of_device): rev[id] = the key holding id, built from the
+// slots whenever ids have been assigned since the last build (state[3] = the id count
+// the table covers).  Ids are never taken back, so a rebuild only adds entries to the
+// table, which starts as all UINT64_MAX.
+__global__ void k_dir_rev_build(const uint64_t *__restrict__ skey, const uint32_t *__restrict__ sid,
+                                uint64_t nslots, const unsigned long long *__restrict__ state, uint64_t capacity,
+                                uint64_t *__restrict__ rev) {
+    if (state[3] == state[0]) return;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nslots; j += stride) {
+        const uint32_t id = sid[j];
+        if (id != kNoId && id < capacity) rev[id] = skey[j];
+    }
+}
+
+// (runs after k_dir_rev_build on the same stream, so it also records what the table covers)
+__global__ void k_dir_keys_of(const uint64_t *__restrict__ ids, uint64_t n, const uint64_t *__restrict__ rev,
+                              uint64_t capacity, unsigned long long *__restrict__ state,
+                              uint64_t *__restrict__ keys) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) state[3] = state[0];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t id = ids[i];
+        keys[i] = id < capacity ? rev[id] : kEmptyKey;
+    }
+}
+
 unsigned grid_for(uint64_t n, unsigned block, unsigned cap = 8192) {
     const uint64_t g = (n + block - 1) / block;
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
@@ -375,7 +402,8 @@ struct tbe_directory {
     uint64_t *skey = nullptr;
     uint32_t *sid = nullptr;
     uint32_t *sfirst = nullptr;
-    unsigned long long *state = nullptr;   // [0] ids assigned, [1] error bits, [2] batch base
+    unsigned long long *state = nullptr;   // [0] ids assigned, [1] error bits, [2] batch base, [3] ids rev covers
+    uint64_t *rev = nullptr;               // id -> key, capacity entries (the first tbe_dir_keys_of_device allocates it)
     uint32_t *slot_of = nullptr;           // per-request slot of the current batch
     uint32_t *bsum = nullptr;
     uint64_t tmp_cap = 0;
@@ -480,7 +508,7 @@ void tbe_dir_destroy(tbe_directory *d) {
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
     for (void *p : {(void *)d->skey, (void *)d->sid, (void *)d->sfirst, (void *)d->state, (void *)d->slot_of,
-                    (void *)d->bsum})
+                    (void *)d->bsum, (void *)d->rev})
         if (p) (void)hipFree(p);
     delete d;
 }
@@ -523,6 +551,26 @@ tbe_status tbe_dir_lookup_device(tbe_directory *d, const uint64_t *d_keys, uint6
     if (hipSetDevice(d->device) != hipSuccess) return TBE_EDEVICE;
     k_dir_lookup<<<grid_for(n, kDirBlock), kDirBlock, 0, (hipStream_t)stream>>>(d_keys, n, d->skey, d->sid,
                                                                                d->nslots - 1, d_ids);
+    return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
+}
+
+tbe_status tbe_dir_keys_of_device(tbe_directory *d, const uint64_t *d_ids, uint64_t n, uint64_t *d_keys,
+                                  void *stream) {
+    if (!d) return TBE_EINVAL;
+    if (n == 0) return TBE_OK;
+    if (!d_ids || !d_keys) return TBE_EINVAL;
+    if (hipSetDevice(d->device) != hipSuccess) return TBE_EDEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    if (!d->rev) {
+        if (hipMalloc(&d->rev, d->capacity * sizeof(uint64_t)) != hipSuccess) return TBE_ENOMEM;
+        // every entry UINT64_MAX, and state[3] = 0: the first build fills in every id held
+        if (hipMemsetAsync(d->rev, 0xFF, d->capacity * sizeof(uint64_t), st) != hipSuccess ||
+            hipMemsetAsync(d->state + 3, 0, sizeof(unsigned long long), st) != hipSuccess)
+            return TBE_EDEVICE;
+    }
+    k_dir_rev_build<<<grid_for(d->nslots, 256), 256, 0, st>>>(d->skey, d->sid, d->nslots, d->state, d->capacity,
+                                                             d->rev);
+    k_dir_keys_of<<<grid_for(n, 256), 256, 0, st>>>(d_ids, n, d->rev, d->capacity, d->state, d_keys);
     return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
 }
 

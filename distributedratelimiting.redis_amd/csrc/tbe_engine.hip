@@ -1208,6 +1208,12 @@ __device__ __forceinline__ void slot_store_nt(Slot *p, const Slot &s) {
     __builtin_memcpy(&v, &s, sizeof v);
     __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
 }
+__device__ __forceinline__ Slot slot_load_nt(const Slot *p) {
+    const u32x4 v = ld_nt(reinterpret_cast<const u32x4 *>(p));
+    Slot s;
+    __builtin_memcpy(&s, &v, sizeof s);
+    return s;
+}
 
 // 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4, nt):
 // the LDS destination is the wave-uniform `lds_wave` + 16 * lane.  A barrier alone does
@@ -3681,6 +3687,120 @@ __global__ __launch_bounds__(kBlock) void k_expired(Slot *__restrict__ table, co
     dead[i] = gone && !queued;
 }
 
+// ---- portable snapshots (tbe_export_live_device / tbe_import_rows_device)
+// Export: the live rows of [first, first + count), compacted in ascending id order, as
+// three kernels and no spinning between workgroups:
+//   k_live_count  live rows of each tile of kLiveTile rows (first read of the table)
+//   k_live_scan   one workgroup turns the tile counts into tile starts and the total
+//   k_live_write  each tile ranks its live rows and stores them from its start (second
+//                 read; tiles that start at or past `capacity` read nothing)
+// A row is live when it is neither absent nor lapsed: the complement of k_expired's row
+// rule.  Element e = k * kBlock + thread of a tile, so loads coalesce; tile order is e order.
+constexpr int kLiveItems = 8;
+constexpr int kLiveTile = kBlock * kLiveItems;   // 2048 rows per workgroup
+constexpr int kLiveScan = 1024;                  // tile counts one k_live_scan round covers
+
+__device__ __forceinline__ bool row_live(int64_t t_us, int64_t exp_lt) { return t_us != kAbsent && !(t_us < exp_lt); }
+
+__global__ __launch_bounds__(kBlock) void k_live_count(const Slot *__restrict__ table, uint64_t first, uint64_t count,
+                                                       int64_t exp_lt, unsigned long long *__restrict__ tile_n) {
+    __shared__ uint32_t wsum[kWaves];
+    const uint64_t base = (uint64_t)blockIdx.x * kLiveTile;
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < kLiveItems; ++k) {
+        const uint64_t i = base + (uint64_t)k * kBlock + threadIdx.x;
+        if (i < count && row_live(ld_nt(&table[first + i].t_us), exp_lt)) ++c;
+    }
+    uint32_t tot;
+    (void)block_excl_scan<kBlock>(c, wsum, &tot);
+    if (threadIdx.x == 0) tile_n[blockIdx.x] = tot;
+}
+
+// In place: tile_n[j] becomes the number of live rows in the tiles before j; *n_live the total.
+__global__ __launch_bounds__(kLiveScan) void k_live_scan(unsigned long long *__restrict__ tile_n, uint64_t ntiles,
+                                                         unsigned long long *__restrict__ n_live) {
+    __shared__ uint32_t wsum[kLiveScan / 64];
+    unsigned long long carry = 0;
+    for (uint64_t j0 = 0; j0 < ntiles; j0 += kLiveScan) {
+        const uint64_t j = j0 + threadIdx.x;
+        const uint32_t c = j < ntiles ? (uint32_t)tile_n[j] : 0u;   // <= kLiveTile each
+        uint32_t tot;
+        const uint32_t pre = block_excl_scan<kLiveScan>(c, wsum, &tot);
+        if (j < ntiles) tile_n[j] = carry + pre;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) *n_live = carry;
+}
+
+__global__ __launch_bounds__(kBlock) void k_live_write(const Slot *__restrict__ table, uint64_t first, uint64_t count,
+                                                       int64_t exp_lt, const unsigned long long *__restrict__ tile_at,
+                                                       uint64_t capacity, uint64_t *__restrict__ ids,
+                                                       double *__restrict__ v, int64_t *__restrict__ t_us) {
+    __shared__ uint32_t cnt[kLiveItems * kWaves];
+    const uint64_t at = tile_at[blockIdx.x];
+    if (at >= capacity) return;   // (the whole workgroup: nothing of this tile fits)
+    const uint64_t base = (uint64_t)blockIdx.x * kLiveTile;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    Slot s[kLiveItems];
+    bool live[kLiveItems];
+    uint32_t rank[kLiveItems];
+#pragma unroll
+    for (int k = 0; k < kLiveItems; ++k) {
+        const uint64_t i = base + (uint64_t)k * kBlock + threadIdx.x;
+        live[k] = false;
+        if (i < count) {
+            s[k] = slot_load_nt(&table[first + i]);
+            live[k] = row_live(s[k].t_us, exp_lt);
+        }
+        const uint64_t bal = __ballot(live[k]);
+        rank[k] = (uint32_t)__popcll(bal & lanemask_lt());
+        if (lane == 0) cnt[k * kWaves + w] = (uint32_t)__popcll(bal);
+    }
+    __syncthreads();
+    uint32_t run = 0;
+#pragma unroll
+    for (int k = 0; k < kLiveItems; ++k) {
+#pragma unroll
+        for (int w2 = 0; w2 < kWaves; ++w2) {
+            if (w2 == w && live[k]) {
+                const uint64_t pos = at + run + rank[k];
+                if (pos < capacity) {
+                    ids[pos] = first + base + (uint64_t)k * kBlock + threadIdx.x;
+                    v[pos] = s[k].v;
+                    t_us[pos] = s[k].t_us;
+                }
+            }
+            run += cnt[k * kWaves + w2];
+        }
+    }
+}
+
+// Import by id.  k_rows_check sets *bad when any row is invalid; k_rows_write then writes
+// nothing and raises the engine's sticky flag, as a skipped batch does.
+__global__ void k_rows_check(const uint64_t *__restrict__ ids, const int64_t *__restrict__ t_us, uint64_t n,
+                             uint64_t n_keys, uint32_t *__restrict__ bad) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int64_t t = t_us[i];
+        if (ids[i] >= n_keys || (t < 0 && t != kAbsent)) *bad = 1u;
+    }
+}
+
+__global__ void k_rows_write(Slot *__restrict__ table, const uint64_t *__restrict__ ids, const double *__restrict__ v,
+                             const int64_t *__restrict__ t_us, uint64_t n, double cap,
+                             const uint32_t *__restrict__ bad, uint32_t *__restrict__ sticky) {
+    if (*bad) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) *sticky = 1u;
+        return;
+    }
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int64_t t = t_us[i];
+        table[ids[i]] = t == kAbsent ? Slot{cap, kAbsent} : Slot{v[i], t};
+    }
+}
+
 // ----------------------------------------------------------------------------- host side
 enum Stage { ST_HIST = 0, ST_COLSCAN, ST_SCATTER, ST_BOUNDS, ST_FOLD, ST_UNSCATTER, ST_HOT, ST_COUNT };
 
@@ -3813,6 +3933,10 @@ struct tbe_engine {
     hipEvent_t ev_in = nullptr, ev_part = nullptr, ev_out = nullptr, ev_hot = nullptr;
     uint32_t *sticky = nullptr;      // set by any skipped batch until tbe_synchronize reads it
     uint32_t *last_err = nullptr;    // the error flag of the last enqueued batch
+    // portable snapshots: k_live_* tile counts (one u64 per kLiveTile rows of the table,
+    // allocated by the first export) and k_rows_check's flag
+    unsigned long long *live_tiles = nullptr;
+    uint32_t *rows_bad = nullptr;
     // host-buffer path staging
     hipStream_t cin = nullptr, cout = nullptr;   // chunked pinned path: copy-in / copy-out streams
     hipStream_t cin2 = nullptr;                  // second copy-in stream (TBE_CIN_STREAMS == 2)
@@ -4669,6 +4793,8 @@ void tbe_destroy(tbe_engine *e) {
     dfree(e->log_id);
     dfree(e->log_rem);
     dfree(e->sticky);
+    dfree(e->live_tiles);
+    dfree(e->rows_bad);
     for (auto &hs : e->hot) dfree(hs);
     for (auto &ev : e->ev_pool)
         if (ev) (void)hipEventDestroy(ev);
@@ -4938,6 +5064,134 @@ tbe_status tbe_expired_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint
         HIP_TRY(e, hipEventRecord(e->ev_out, st));
         HIP_TRY(e, hipStreamWaitEvent(caller, e->ev_out, 0));
     }
+    return TBE_OK;
+}
+
+// Stream ordering of both snapshot calls is tbe_expired_device's: the kernels run on the
+// engine's stream, a caller's stream is joined before and after.
+tbe_status tbe_export_live_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, uint64_t *d_ids,
+                                  double *d_v, int64_t *d_t_us, uint64_t capacity, uint64_t *d_n_live,
+                                  void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind == TBE_KIND_APPROXIMATE)
+        return fail(e, TBE_EINVAL, "the approximate kind's tiers are not part of a snapshot");
+    if (first > e->cfg.n_keys || count > e->cfg.n_keys - first)
+        return fail(e, TBE_EINVAL, "range out of bounds");
+    if (!d_n_live || (capacity && (!d_ids || !d_v || !d_t_us))) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (!e->live_tiles)
+        HIP_TRY(e, hipMalloc(&e->live_tiles,
+                             ((e->cfg.n_keys + kLiveTile - 1) / kLiveTile) * sizeof(unsigned long long)));
+    hipStream_t st = e->stream, caller = (hipStream_t)stream;
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_in, caller));
+        HIP_TRY(e, hipStreamWaitEvent(st, e->ev_in, 0));
+    }
+    if (count == 0) {
+        HIP_TRY(e, hipMemsetAsync(d_n_live, 0, sizeof(uint64_t), st));
+    } else {
+        const int64_t exp_lt = ts_us < 0 ? kAbsent : (ts_us / 1000 - e->params.ttl_ms) * 1000;   // < 0: no row lapses
+        const uint64_t ntiles = (count + kLiveTile - 1) / kLiveTile;
+        k_live_count<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, exp_lt, e->live_tiles);
+        k_live_scan<<<1, kLiveScan, 0, st>>>(e->live_tiles, ntiles, reinterpret_cast<unsigned long long *>(d_n_live));
+        if (capacity)
+            k_live_write<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, exp_lt, e->live_tiles, capacity,
+                                                              d_ids, d_v, d_t_us);
+        HIP_TRY(e, hipGetLastError());
+    }
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_out, st));
+        HIP_TRY(e, hipStreamWaitEvent(caller, e->ev_out, 0));
+    }
+    return TBE_OK;
+}
+
+tbe_status tbe_export_live(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, uint64_t *ids, double *v,
+                           int64_t *t_us, uint64_t capacity, uint64_t *n_live) {
+    if (!e || !n_live) return TBE_EINVAL;
+    if (e->cfg.kind == TBE_KIND_APPROXIMATE)
+        return fail(e, TBE_EINVAL, "the approximate kind's tiers are not part of a snapshot");
+    if (first > e->cfg.n_keys || count > e->cfg.n_keys - first)
+        return fail(e, TBE_EINVAL, "range out of bounds");
+    if (capacity && (!ids || !v || !t_us)) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch, whatever its stream
+    const uint64_t cap = std::min(capacity, count);   // no more rows than the range holds
+    void *buf = nullptr;
+    HIP_TRY(e, hipMalloc(&buf, 8 + cap * 24));
+    uint64_t *d_n = static_cast<uint64_t *>(buf), *d_ids = d_n + 1;
+    double *d_v = reinterpret_cast<double *>(d_ids + cap);
+    int64_t *d_t = reinterpret_cast<int64_t *>(d_v + cap);
+    tbe_status rc = tbe_export_live_device(e, ts_us, first, count, cap ? d_ids : nullptr, cap ? d_v : nullptr,
+                                           cap ? d_t : nullptr, cap, d_n, nullptr);
+    hipError_t hrc = hipSuccess;
+    if (rc == TBE_OK) {
+        hrc = hipMemcpyAsync(n_live, d_n, sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream);
+        if (hrc == hipSuccess) hrc = hipStreamSynchronize(e->stream);
+        const uint64_t m = hrc == hipSuccess ? std::min<uint64_t>(*n_live, cap) : 0;
+        if (m && hrc == hipSuccess) hrc = hipMemcpy(ids, d_ids, m * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        if (m && hrc == hipSuccess) hrc = hipMemcpy(v, d_v, m * sizeof(double), hipMemcpyDeviceToHost);
+        if (m && hrc == hipSuccess) hrc = hipMemcpy(t_us, d_t, m * sizeof(int64_t), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
+    return TBE_OK;
+}
+
+tbe_status tbe_import_rows_device(tbe_engine *e, const uint64_t *d_ids, const double *d_v, const int64_t *d_t_us,
+                                  uint64_t n, void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind == TBE_KIND_APPROXIMATE)
+        return fail(e, TBE_EINVAL, "the approximate kind's tiers are not part of a snapshot");
+    if (n == 0) return TBE_OK;
+    if (!d_ids || !d_v || !d_t_us) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (!e->rows_bad) HIP_TRY(e, hipMalloc(&e->rows_bad, sizeof(uint32_t)));
+    hipStream_t st = e->stream, caller = (hipStream_t)stream;
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_in, caller));
+        HIP_TRY(e, hipStreamWaitEvent(st, e->ev_in, 0));
+    }
+    HIP_TRY(e, hipMemsetAsync(e->rows_bad, 0, sizeof(uint32_t), st));
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192);
+    // the validating pass ends before the first row is written (one stream)
+    k_rows_check<<<blocks, kBlock, 0, st>>>(d_ids, d_t_us, n, e->cfg.n_keys, e->rows_bad);
+    k_rows_write<<<blocks, kBlock, 0, st>>>(e->table, d_ids, d_v, d_t_us, n, e->params.cap, e->rows_bad, e->sticky);
+    HIP_TRY(e, hipGetLastError());
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_out, st));
+        HIP_TRY(e, hipStreamWaitEvent(caller, e->ev_out, 0));
+    }
+    return TBE_OK;
+}
+
+tbe_status tbe_import_rows(tbe_engine *e, const uint64_t *ids, const double *v, const int64_t *t_us, uint64_t n) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind == TBE_KIND_APPROXIMATE)
+        return fail(e, TBE_EINVAL, "the approximate kind's tiers are not part of a snapshot");
+    if (n == 0) return TBE_OK;
+    if (!ids || !v || !t_us) return fail(e, TBE_EINVAL, "null buffer");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (ids[i] >= e->cfg.n_keys) return fail(e, TBE_EINVAL, "id out of range");
+        if (t_us[i] != kAbsent && t_us[i] < 0) return fail(e, TBE_EINVAL, "t_us < 0");
+    }
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch, whatever its stream
+    void *buf = nullptr;
+    HIP_TRY(e, hipMalloc(&buf, n * 24));
+    uint64_t *d_ids = static_cast<uint64_t *>(buf);
+    double *d_v = reinterpret_cast<double *>(d_ids + n);
+    int64_t *d_t = reinterpret_cast<int64_t *>(d_v + n);
+    hipError_t hrc = hipMemcpy(d_ids, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (hrc == hipSuccess) hrc = hipMemcpy(d_v, v, n * sizeof(double), hipMemcpyHostToDevice);
+    if (hrc == hipSuccess) hrc = hipMemcpy(d_t, t_us, n * sizeof(int64_t), hipMemcpyHostToDevice);
+    tbe_status rc = TBE_OK;
+    if (hrc == hipSuccess) rc = tbe_import_rows_device(e, d_ids, d_v, d_t, n, nullptr);
+    if (hrc == hipSuccess && rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
     return TBE_OK;
 }
 

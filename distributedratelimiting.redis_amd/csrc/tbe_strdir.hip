@@ -842,6 +842,37 @@ unsigned sd_grid(uint64_t n, unsigned block, unsigned cap = 8192) {
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
 }
 
+// Key text by id (tbe_sdir_text_lengths_device / tbe_sdir_text_device): the length from
+// iloc, 0 for an id that is not held; then the bytes out of the arena into the caller's
+// Arrow layout, never more than the span its offsets give the string.
+__global__ void k_sd_text_len(const uint64_t *__restrict__ ids, uint64_t n, const uint64_t *__restrict__ iloc,
+                              uint64_t capacity, uint64_t *__restrict__ lens,
+                              unsigned long long *__restrict__ n_missing) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t id = ids[i];
+        const uint64_t loc = id < capacity ? iloc[id] : 0ull;
+        const bool held = (loc & kLocValid) != 0;
+        lens[i] = held ? loc_len(loc) : 0u;
+        if (!held && n_missing) atomicAdd(n_missing, 1ull);
+    }
+}
+
+__global__ void k_sd_text(const uint64_t *__restrict__ ids, uint64_t n, const uint64_t *__restrict__ iloc,
+                          uint64_t capacity, const uint8_t *__restrict__ arena, const uint64_t *__restrict__ offs,
+                          uint8_t *__restrict__ bytes) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t id = ids[i];
+        const uint64_t loc = id < capacity ? iloc[id] : 0ull;
+        const uint64_t a = offs[i], b = offs[i + 1];
+        if (!(loc & kLocValid) || b <= a) continue;
+        const uint64_t len = min((uint64_t)loc_len(loc), b - a);
+        const uint8_t *src = arena + loc_off(loc);
+        for (uint64_t j = 0; j < len; ++j) bytes[a + j] = src[j];
+    }
+}
+
 // Host hash of the prefix (the seeds of the four rounds derive from it).
 uint64_t host_hash(const uint8_t *p, uint32_t len) {
     uint64_t h = mix64(0x243F6A8885A308D3ull ^ ((uint64_t)len * 0x9E3779B97F4A7C15ull));
@@ -1236,6 +1267,30 @@ tbe_status tbe_sdir_reclaim(tbe_string_directory *d, tbe_engine *engine, int64_t
         hipMemcpy(n_reclaimed, d->rc_count, sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
         return TBE_EDEVICE;
     return TBE_OK;
+}
+
+tbe_status tbe_sdir_text_lengths_device(tbe_string_directory *d, const uint64_t *d_ids, uint64_t n, uint64_t *d_lens,
+                                        uint64_t *d_n_missing, void *stream) {
+    if (!d) return TBE_EINVAL;
+    if (n && (!d_ids || !d_lens)) return TBE_EINVAL;
+    if (hipSetDevice(d->device) != hipSuccess) return TBE_EDEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    if (d_n_missing && hipMemsetAsync(d_n_missing, 0, sizeof(uint64_t), st) != hipSuccess) return TBE_EDEVICE;
+    if (n == 0) return TBE_OK;
+    k_sd_text_len<<<sd_grid(n, 256), 256, 0, st>>>(d_ids, n, d->iloc, d->capacity, d_lens,
+                                                   reinterpret_cast<unsigned long long *>(d_n_missing));
+    return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
+}
+
+tbe_status tbe_sdir_text_device(tbe_string_directory *d, const uint64_t *d_ids, uint64_t n, const uint64_t *d_offs,
+                                uint8_t *d_bytes, void *stream) {
+    if (!d) return TBE_EINVAL;
+    if (n == 0) return TBE_OK;
+    if (!d_ids || !d_offs || !d_bytes) return TBE_EINVAL;
+    if (hipSetDevice(d->device) != hipSuccess) return TBE_EDEVICE;
+    k_sd_text<<<sd_grid(n, 256), 256, 0, (hipStream_t)stream>>>(d_ids, n, d->iloc, d->capacity, d->arena, d_offs,
+                                                                d_bytes);
+    return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
 }
 
 tbe_status tbe_sdir_key_of(tbe_string_directory *d, uint64_t id, uint8_t *buf, uint64_t cap, uint64_t *len) {

@@ -186,6 +186,58 @@ class TokenBucketEngine:
         self._check(self._lib.tbe_expired_device(self.handle, ts_us, first, d_dead.numel(), d_dead.data_ptr(),
                                                  1 if clear else 0, stream))
 
+    def export_live_device(self, ts_us: int, d_ids, d_v, d_t_us, d_n_live, first: int = 0,
+                           count: Optional[int] = None, capacity: Optional[int] = None,
+                           stream: Optional[int] = None) -> None:
+        """One tbe_export_live_device call into caller tensors (int64 ids, float64 v, int64
+        t_us, one-element int64 count); capacity defaults to d_ids.numel(), and capacity 0
+        with d_ids = d_v = d_t_us = None only counts.  Enqueued, not synchronised."""
+        if count is None:
+            count = self.n_keys - first
+        if capacity is None:
+            capacity = 0 if d_ids is None else d_ids.numel()
+        if capacity and min(d_ids.numel(), d_v.numel(), d_t_us.numel()) < capacity:
+            raise ValueError("capacity exceeds the output tensors")
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        self._check(self._lib.tbe_export_live_device(self.handle, ts_us, first, count, ptr(d_ids), ptr(d_v),
+                                                     ptr(d_t_us), capacity, d_n_live.data_ptr(), stream))
+
+    def export_live(self, ts_us: int, first: int = 0, count: Optional[int] = None, stream: Optional[int] = None):
+        """The live rows of [first, first + count) at ts_us as int64 ids, float64 v and int64
+        t_us device tensors, ascending ids (tbe_export_live_device; ts_us < 0: every present
+        row).  A counting call, one read-back of the count (the device is synchronised for
+        it), then the filling call: ordered on `stream` when one is given, complete on return
+        otherwise."""
+        import torch
+        if count is None:
+            count = self.n_keys - first
+        dev = torch.device("cuda", self.config.device if self.config.device >= 0 else torch.cuda.current_device())
+        d_n = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._check(self._lib.tbe_export_live_device(self.handle, ts_us, first, count, None, None, None, 0,
+                                                     d_n.data_ptr(), stream))
+        torch.cuda.synchronize(dev)
+        n = int(d_n.item())
+        d_ids = torch.empty(n, dtype=torch.int64, device=dev)
+        d_v = torch.empty(n, dtype=torch.float64, device=dev)
+        d_t = torch.empty(n, dtype=torch.int64, device=dev)
+        if n:
+            self._check(self._lib.tbe_export_live_device(self.handle, ts_us, first, count, d_ids.data_ptr(),
+                                                         d_v.data_ptr(), d_t.data_ptr(), n, d_n.data_ptr(), stream))
+            if not stream:
+                torch.cuda.synchronize(dev)
+        return d_ids, d_v, d_t
+
+    def import_rows(self, d_ids, d_v, d_t_us, stream: Optional[int] = None) -> None:
+        """table[d_ids[i]] = {d_v[i], d_t_us[i]} from device tensors (tbe_import_rows_device);
+        enqueued, an invalid row voids the call and raises at ``synchronize()``."""
+        n = d_ids.numel()
+        if d_v.numel() != n or d_t_us.numel() != n:
+            raise ValueError("d_ids, d_v and d_t_us must have the same length")
+        d_ids, d_v, d_t_us = d_ids.contiguous(), d_v.contiguous(), d_t_us.contiguous()
+        self._check(self._lib.tbe_import_rows_device(self.handle, d_ids.data_ptr(), d_v.data_ptr(),
+                                                     d_t_us.data_ptr(), n, stream))
+        self._rows_in_flight = (d_ids, d_v, d_t_us)   # read by the enqueued kernels
+
     def layout(self) -> dict:
         """{passes, r_bits, packed, hot, pipeline, narrow, medium, fold_records, digit_stream, rerank,
         narrow_pass0, queue_header_32} of this engine's

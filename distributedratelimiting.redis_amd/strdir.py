@@ -210,6 +210,34 @@ class StringDirectory:
             raise _capi.TbeError(st, "tbe_sdir_reclaim failed")
         return n.value
 
+    def text_of(self, d_ids, return_missing: bool = False):
+        """Key text of an int64 device tensor of ids, on the device: (uint8 bytes, int64 offsets
+        [n + 1]), the layout ``assign`` takes (tbe_sdir_text_lengths_device, a scan,
+        tbe_sdir_text_device).  An id that is not held gets an empty string;
+        return_missing=True appends their number."""
+        import torch
+        from . import _capi
+        from .cluster import device_stream
+        dev = d_ids.device
+        st = device_stream(dev)
+        d_ids = d_ids.contiguous()
+        n = d_ids.numel()
+        lens = torch.empty(n, dtype=torch.int64, device=dev)
+        missing = torch.zeros(1, dtype=torch.int64, device=dev)
+        rc = self._lib.tbe_sdir_text_lengths_device(self._h, d_ids.data_ptr(), n, lens.data_ptr(),
+                                                    missing.data_ptr(), st)
+        if rc != _capi.TBE_OK:
+            raise _capi.TbeError(rc, "tbe_sdir_text_lengths_device failed")
+        offs = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        if n:
+            torch.cumsum(lens, 0, out=offs[1:])
+        n_bytes = int(offs[-1].item())
+        buf = torch.zeros((n_bytes + 7) // 8 * 8 + 8, dtype=torch.uint8, device=dev)
+        rc = self._lib.tbe_sdir_text_device(self._h, d_ids.data_ptr(), n, offs.data_ptr(), buf.data_ptr(), st)
+        if rc != _capi.TBE_OK:
+            raise _capi.TbeError(rc, "tbe_sdir_text_device failed")
+        return (buf, offs, int(missing.item())) if return_missing else (buf, offs)
+
     def key_of(self, key_id: int) -> bytes:
         import ctypes
         from . import _capi

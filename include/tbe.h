@@ -201,8 +201,40 @@ tbe_status tbe_import_state(tbe_engine *engine, uint64_t first, uint64_t count, 
 tbe_status tbe_expired_device(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
                               uint8_t *d_dead, int32_t clear, void *stream);
 
+/* Portable snapshots: the live bucket rows as (id, v, t_us) lists, so that
+ * saved state can be put back behind a directory that hands out other ids, or split over
+ * another number of owners.  Token-bucket and queueing kinds (their bucket rows, the state
+ * tbe_import_state covers; queues are not part of it); approximate kind: TBE_EINVAL.
+ *
+ * Export: a row of [first, first + count) is live at ts_us when t_us != INT64_MIN and not
+ * t_us < 1000 * (ts_us / 1000 - ttl_ms), the complement of tbe_expired_device's row rule
+ * (queue headers play no part); ts_us < 0 skips the lapse test, as in tbe_query.  The live
+ * rows are written compacted, in ascending id order: d_ids[j], d_v[j], d_t_us[j] for the
+ * j-th live row, j < capacity.  *d_n_live (device u64) always gets the total number of
+ * live rows; rows at positions >= capacity are not written and nothing past capacity is
+ * touched.  capacity == 0 (the buffers may be NULL) only counts.  Ordered after every
+ * batch already enqueued on the engine, `stream` as in tbe_expired_device. */
+tbe_status tbe_export_live_device(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                                  uint64_t *d_ids, double *d_v, int64_t *d_t_us, uint64_t capacity,
+                                  uint64_t *d_n_live, void *stream);
+/* The same into host buffers; synchronous. */
+tbe_status tbe_export_live(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                           uint64_t *ids, double *v, int64_t *t_us, uint64_t capacity, uint64_t *n_live);
+
+/* Import by id: table[d_ids[i]] = {d_v[i], d_t_us[i]}; t_us = INT64_MIN makes the row absent
+ * ({TokenLimit, absent}).  Ids must be unique: the result for an id given twice is
+ * unspecified.  An id >= n_keys, or a t_us < 0 other than INT64_MIN, makes the whole call
+ * a no-op (every row is validated before any is written), reported like an invalid device
+ * batch: by tbe_synchronize.  Ordered after every batch enqueued before the call and
+ * before every batch enqueued after it; `stream` as in tbe_expired_device. */
+tbe_status tbe_import_rows_device(tbe_engine *engine, const uint64_t *d_ids, const double *d_v,
+                                  const int64_t *d_t_us, uint64_t n, void *stream);
+/* The same from host buffers; synchronous, invalid rows: TBE_EINVAL, nothing written. */
+tbe_status tbe_import_rows(tbe_engine *engine, const uint64_t *ids, const double *v, const int64_t *t_us,
+                           uint64_t n);
+
 /* ---------------------------------------------------------------- TokenBucketWithQueue
- * Engines created with kind = TBE_KIND_QUEUEING.  The reference limiter
+ * Engines created with kind = TBE_KIND_QUEUEING. The reference limiter
  * (TokenBucketWithQueue/RedisTokenBucketRateLimiter.cs, "Q") is commented out and does
  * not compile; its semantics are fixed in DESIGN.md §2b (a lease is one TB script call;
  * queue order follows System.Collections.Generic/Deque.cs).  Per-key queues hold at most

@@ -49,7 +49,10 @@ tbe_status tbe_route_plan_device(const uint64_t *d_keys, uint64_t n, uint32_t n_
  * v -> (v * n_owners) >> 12 is the hash partition above for a power-of-two n_owners; a
  * balanced map gives the virtual nodes of hot keys' owners fewer others, so a Zipf
  * stream's owner loads even out (SURVEY.md §7 hard part iii).  A key still has exactly
- * one owner; the map must not change while any owner holds state. */
+ * one owner.  Owners hold their buckets by dense id, so a live table cannot follow a map that
+ * changes under it; a map (or the number of owners) changes through a snapshot: every owner
+ * saves its live buckets by key (tbe_export_live_device, tbe_dir_keys_of_device) and each
+ * new owner loads the keys the new map gives it (DESIGN.md §8 "Portable snapshots"). */
 #define TBE_OWNER_MAP_BITS 12
 #define TBE_OWNER_MAP_SIZE 4096
 uint32_t tbe_key_vnode(uint64_t key);
@@ -93,6 +96,12 @@ tbe_status tbe_dir_assign_device(tbe_directory *dir, const uint64_t *d_keys, uin
 /* d_ids[i] = id of d_keys[i], UINT64_MAX for a key never assigned (nothing changes). */
 tbe_status tbe_dir_lookup_device(tbe_directory *dir, const uint64_t *d_keys, uint64_t n, uint64_t *d_ids,
                                  void *stream);
+/* Reverse lookup: d_keys[i] = the key that holds id d_ids[i]; UINT64_MAX when no key holds
+ * it or the id is >= capacity.  The id -> key table (capacity u64, allocated by the first
+ * call) is built from the slots by one pass, again whenever ids have been assigned since;
+ * like a lookup it must not run concurrently with an assign on another stream. */
+tbe_status tbe_dir_keys_of_device(tbe_directory *dir, const uint64_t *d_ids, uint64_t n, uint64_t *d_keys,
+                                  void *stream);
 /* Ids assigned so far (synchronises the directory's device). */
 tbe_status tbe_dir_size(tbe_directory *dir, uint64_t *n_ids);
 /* The same without synchronising: enqueues on `stream` a copy of {ids assigned, error

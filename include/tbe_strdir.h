@@ -77,6 +77,19 @@ tbe_status tbe_sdir_size(tbe_string_directory *dir, uint64_t *n_ids);
  * min(len, cap) bytes to buf.  TBE_EINVAL for an id never assigned.  Synchronises. */
 tbe_status tbe_sdir_key_of(tbe_string_directory *dir, uint64_t id, uint8_t *buf, uint64_t cap, uint64_t *len);
 
+/* Key text of many ids, on the device (bulk tbe_sdir_key_of; mirrors tbe_key_text_lengths_device
+ * / tbe_key_text_device of tbe_tools.h).  First call: d_lens[i] = length of the resourceID
+ * (without the prefix) held by id d_ids[i]; an id that is not held (never assigned,
+ * reclaimed, or >= capacity) gets 0 and is counted in *d_n_missing (device u64, may be
+ * NULL).  The caller scans the lengths into n + 1 offsets; the second call copies the text
+ * of id d_ids[i] to d_bytes[d_offs[i], d_offs[i+1]), which must hold d_offs[n] bytes.  The
+ * result is the batch layout tbe_sdir_assign_device takes.  Contract as for a lookup: no
+ * assign or reclaim may be in flight on another stream, nor run between the two calls. */
+tbe_status tbe_sdir_text_lengths_device(tbe_string_directory *dir, const uint64_t *d_ids, uint64_t n,
+                                        uint64_t *d_lens, uint64_t *d_n_missing, void *stream);
+tbe_status tbe_sdir_text_device(tbe_string_directory *dir, const uint64_t *d_ids, uint64_t n,
+                                const uint64_t *d_offs, uint8_t *d_bytes, void *stream);
+
 /* Remove the keys flagged dead and reuse what they held.  d_dead: `capacity` bytes of
  * device memory indexed by id (tbe_expired_device over [0, capacity) writes them);
  * d_keep_ids: n_keep ids (device memory) that are never removed.  For every id that is
