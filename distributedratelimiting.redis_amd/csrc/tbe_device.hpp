@@ -234,6 +234,43 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t *wsum, 
     return pre + v - x;
 }
 
+// Wave match: the mask of the lanes in `vmask` whose 8-bit digit (key >> shift) & 255
+// equals this lane's.  Per digit bit, sb is the lane's bit sign-extended to 0 / -1 (one
+// signed bit-field extract of the digit) and m the ballot of the lanes that have it set;
+// m ^ sb then marks the lanes whose bit differs from this lane's, and the eight rounds OR
+// those into one differ-mask (two 32-bit halves): 5 vector instructions per round
+// (bfe, cmp, 2 xor, and two 3-input ORs per two rounds) against 9 for TBE_WAVE_MATCH=0 (peers &= bit ? m : ~m, which
+// costs a select and two ANDs per half on top of the compare).  Same mask either way.
+#ifndef TBE_WAVE_MATCH
+#define TBE_WAVE_MATCH 1                     // 0: the select form, as before (A/B)
+#endif
+__device__ __forceinline__ uint64_t digit_peers(uint32_t key, int shift, uint64_t vmask) {
+#if TBE_WAVE_MATCH
+    // (the digit first: a last pass's shift + b can pass bit 31, where the digit's bits are 0
+    // and a bit-field extract of the key itself would wrap around)
+    const uint32_t dg = (key >> shift) & (kDigits - 1);
+    uint32_t dlo = 0, dhi = 0;
+#pragma unroll
+    for (int b = 0; b < kDigitBits; ++b) {
+        const uint32_t sb = (uint32_t)__builtin_amdgcn_sbfe((int)dg, (uint32_t)b, 1u);
+        const uint64_t m = __builtin_amdgcn_uicmp(sb, 0u, 33);   // ballot(sb != 0), compared on sb itself
+        dlo |= (uint32_t)m ^ sb;
+        dhi |= (uint32_t)(m >> 32) ^ sb;
+    }
+    return vmask & ~(((uint64_t)dhi << 32) | dlo);
+#else
+    const uint32_t dg = (key >> shift) & (kDigits - 1);
+    uint64_t peers = vmask;
+#pragma unroll
+    for (int b = 0; b < kDigitBits; ++b) {
+        const bool bit = (dg >> b) & 1u;
+        const uint64_t m = __ballot(bit);
+        peers &= bit ? m : ~m;
+    }
+    return peers;
+#endif
+}
+
 // Stable local ranking of a tile of BLOCK*ITEMS elements by an 8-bit digit.
 // Element e = it*BLOCK + threadIdx.x (striped, so global loads coalesce); tile order is
 // e order.
@@ -275,13 +312,7 @@ __device__ __forceinline__ void rank_tile(const uint32_t (&key)[ITEMS], int shif
         const int e = it * BLOCK + tid;
         const bool valid = e < nvalid;
         const uint32_t dg = TBE_DIG(it);
-        uint64_t peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < kDigitBits; ++b) {
-            const bool bit = (dg >> b) & 1u;
-            const uint64_t m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
+        const uint64_t peers = digit_peers(key[it], shift, __ballot(valid));
         lpos[it] = (uint32_t)__popcll(peers & lt);   // in-wave rank for now
         if (valid && lpos[it] == 0) cnt[(it * W + w) * kDigits + dg] = (uint16_t)__popcll(peers);
     }
@@ -340,13 +371,14 @@ __device__ __forceinline__ void rank_tile(const uint32_t (&key)[ITEMS], int shif
 //      scan of the digit totals gives lstart[digit];
 //   C. lpos = lstart[d] + wave offset + in-wave rank.
 // LDS: W*256 words (callers alias it with their staging buffer) plus RankLds.  Three
-// barriers plus the block scan's two.
+// barriers plus the block scan's two.  FULL: the caller's tile has all BLOCK*ITEMS
+// elements (nvalid is ignored), so no lane is masked and a digit group is never empty.
 template <int BLOCK, int ITEMS>
 __device__ __forceinline__ int wb_elem(int it) {
     return (int)((threadIdx.x >> 6) * (64 * ITEMS) + it * 64 + (threadIdx.x & 63));
 }
 
-template <int BLOCK, int ITEMS>
+template <int BLOCK, int ITEMS, bool FULL = false>
 __device__ __forceinline__ void rank_tile_wb(const uint32_t (&key)[ITEMS], int shift, int nvalid,
                                              RankLds<BLOCK> &L, uint32_t *wcnt, uint32_t (&lpos)[ITEMS]) {
     constexpr int W = BLOCK / 64;
@@ -359,16 +391,10 @@ __device__ __forceinline__ void rank_tile_wb(const uint32_t (&key)[ITEMS], int s
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
         const int e = wb_elem<BLOCK, ITEMS>(it);
-        const bool valid = e < nvalid;
+        const bool valid = FULL || e < nvalid;
         const uint32_t dg = (key[it] >> shift) & (kDigits - 1);
-        uint64_t peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < kDigitBits; ++b) {
-            const bool bit = (dg >> b) & 1u;
-            const uint64_t m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
-        const int leader = peers ? __ffsll((long long)peers) - 1 : lane;
+        const uint64_t peers = digit_peers(key[it], shift, FULL ? ~0ull : __ballot(valid));
+        const int leader = (FULL || peers) ? __ffsll((long long)peers) - 1 : lane;
         uint32_t old = 0;
         if (valid && leader == lane) old = atomicAdd(&mine[dg], (uint32_t)__popcll(peers));
         old = __shfl(old, leader, 64);

@@ -37,6 +37,7 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/tbe.h"
@@ -91,6 +92,9 @@ constexpr int kTile = kPartBlock * kPartItems;         // 4096 requests per part
 constexpr int kUnBlock = TBE_UN_BLOCK;
 constexpr int kUnItems = TBE_UN_ITEMS;
 constexpr int kUnTile = kUnBlock * kUnItems;
+#ifndef TBE_FULL_TILE
+#define TBE_FULL_TILE 1                      // partition passes: unmasked body for full tiles; 0: A/B
+#endif
 #ifndef TBE_HIST_BLOCKS
 #define TBE_HIST_BLOCKS 1024
 #endif
@@ -452,17 +456,31 @@ __global__ __launch_bounds__(kHBlock, TBE_HIST_WAVES) void k_hist_dig(
             }
         }
         __syncthreads();
+        if (TBE_FULL_TILE && base + kTile <= n) {
+            // a full tile: no lane is masked, and the wave-uniform test reads lane 0's digit
 #pragma unroll
-        for (int u = 0; u < kHItems; ++u) {
-            const uint64_t i = base + (uint64_t)tid * kHItems + u;
-            const bool valid = i < n;
-            const uint32_t d = (uint32_t)(vw[u >> 3] >> (8 * (u & 7))) & (kDigits - 1);
-            const uint64_t vmask = __ballot(valid);
-            const uint32_t dw = __shfl(d, vmask ? __ffsll((long long)vmask) - 1 : 0, 64);
-            if (__all(!valid || d == dw)) {
-                if (vmask && (vmask & lanemask_lt()) == 0 && valid) atomicAdd(&h8[dw * 8], (uint32_t)__popcll(vmask));
-            } else if (valid) {
-                atomicAdd(&h8[d * 8 + (tid & 7)], 1u);
+            for (int u = 0; u < kHItems; ++u) {
+                const uint32_t d = (uint32_t)(vw[u >> 3] >> (8 * (u & 7))) & (kDigits - 1);
+                const uint32_t dw = (uint32_t)__builtin_amdgcn_readfirstlane((int)d);
+                if (__all(d == dw)) {
+                    if ((tid & 63) == 0) atomicAdd(&h8[dw * 8], 64u);
+                } else {
+                    atomicAdd(&h8[d * 8 + (tid & 7)], 1u);
+                }
+            }
+        } else {
+            const uint32_t nv = (uint32_t)(n - base);    // (a batch has < 2^32 requests)
+#pragma unroll
+            for (int u = 0; u < kHItems; ++u) {
+                const bool valid = (uint32_t)(tid * kHItems + u) < nv;
+                const uint32_t d = (uint32_t)(vw[u >> 3] >> (8 * (u & 7))) & (kDigits - 1);
+                const uint64_t vmask = __ballot(valid);
+                const uint32_t dw = __shfl(d, vmask ? __ffsll((long long)vmask) - 1 : 0, 64);
+                if (__all(!valid || d == dw)) {
+                    if (vmask && (vmask & lanemask_lt()) == 0 && valid) atomicAdd(&h8[dw * 8], (uint32_t)__popcll(vmask));
+                } else if (valid) {
+                    atomicAdd(&h8[d * 8 + (tid & 7)], 1u);
+                }
             }
         }
         __syncthreads();
@@ -1043,146 +1061,156 @@ __global__ __launch_bounds__(kPartBlock, FIRST ? TBE_SCATTER0_WAVES : 1) void k_
     const int tid = threadIdx.x;
     const uint32_t tile = xcd_swizzle(blockIdx.x, gridDim.x);
     const uint64_t base = (uint64_t)tile * kTile;
-    const int nvalid = (int)min<uint64_t>(kTile, n - base);
+    const int nv = (int)min((uint32_t)kTile, (uint32_t)(n - base));   // (a batch has < 2^32 requests)
 
-    uint64_t rec[kPartItems];
-    uint32_t key[kPartItems], lpos[kPartItems];
-    bool bad = false;
-    bool any_hot = false;
-    int64_t tv_keep[FIRST ? kPartItems : 1];   // narrow records: escaped times go to ts0
-    if (FIRST) {
-        uint64_t kv[kPartItems];
-        int32_t pv[kPartItems];
-        int64_t tv[kPartItems];
+    // The tile body, compiled twice: every tile but a batch's last one is full, and FULL
+    // drops the per-element `e < nvalid` masking (TBE_FULL_TILE=0: the masked body only, A/B)
+    auto body = [&](auto full) {
+        constexpr bool FULL = decltype(full)::value;
+        const int nvalid = nv;
+        uint64_t rec[kPartItems];
+        uint32_t key[kPartItems], lpos[kPartItems];
+        bool bad = false;
+        bool any_hot = false;
+        int64_t tv_keep[FIRST ? kPartItems : 1];   // narrow records: escaped times go to ts0
+        if (FIRST) {
+            uint64_t kv[kPartItems];
+            int32_t pv[kPartItems];
+            int64_t tv[kPartItems];
 #pragma unroll
-        for (int it = 0; it < kPartItems; ++it) {
-            const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
-            const bool v = e < nvalid;
-            kv[it] = v ? LD_P(kin + base + e) : 0ull;
-            pv[it] = v ? LD_P(pin + base + e) : 0;
-            tv[it] = NOTS ? -1 : (v ? LD_P(tin + base + e) : 0);
-        }
-        // the table fill overlaps the tile loads above
-        any_hot = HOT && hot_load<kPartBlock>(hot, hs);
-        const int64_t tbase = NOTS ? 0 : (n0 ? pack_base32(tin, F) : pack_base(tin, F));
-        uint32_t skv[kPartItems];
-        if (HOT && any_hot) {
-            hot_sortkeys<kPartItems>(kv, hot_table(hot, hs), nb, r_bits, skv);
-        } else {
-#pragma unroll
-            for (int it = 0; it < kPartItems; ++it) skv[it] = (uint32_t)(kv[it] & F.kmask);
-        }
-#pragma unroll
-        for (int it = 0; it < kPartItems; ++it) {
-            const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
-            bad |= (e < nvalid) && (pv[it] < 0 || (!NOTS && tv[it] < 0));
-            if (n0) {
-                bool esc = false;
-                const uint32_t r32 =
-                    NOTS ? (skv[it] & ((1u << F.rb) - 1u)) |
-                               ((uint32_t)(pv[it] < 0 ? 0 : (pv[it] > F.pc_max ? F.pc_max : pv[it])) << F.rb)
-                         : pack_rec32(skv[it], pv[it], tv[it], tbase, F, esc);
-                // stage: record | pass-0 digit << 32 | pass-1 digit << 40; escape flag in bit 48
-                rec[it] = (uint64_t)r32 | ((uint64_t)((skv[it] >> shift) & (kDigits - 1)) << 32) |
-                          ((uint64_t)((skv[it] >> (shift + kDigitBits)) & (kDigits - 1)) << 40) |
-                          ((uint64_t)esc << 48);
+            for (int it = 0; it < kPartItems; ++it) {
+                const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
+                const bool v = (FULL || e < nvalid);
+                kv[it] = v ? LD_P(kin + base + e) : 0ull;
+                pv[it] = v ? LD_P(pin + base + e) : 0;
+                tv[it] = NOTS ? -1 : (v ? LD_P(tin + base + e) : 0);
+            }
+            // the table fill overlaps the tile loads above
+            any_hot = HOT && hot_load<kPartBlock>(hot, hs);
+            const int64_t tbase = NOTS ? 0 : (n0 ? pack_base32(tin, F) : pack_base(tin, F));
+            uint32_t skv[kPartItems];
+            if (HOT && any_hot) {
+                hot_sortkeys<kPartItems>(kv, hot_table(hot, hs), nb, r_bits, skv);
             } else {
-                rec[it] = pack_rec(skv[it], pv[it], tv[it], base + e, tbase, F);
+#pragma unroll
+                for (int it = 0; it < kPartItems; ++it) skv[it] = (uint32_t)(kv[it] & F.kmask);
             }
-            key[it] = skv[it];
-            tv_keep[FIRST ? it : 0] = tv[it];
-        }
-    } else {
-        if (n0) {
-            const uint32_t *rin32 = reinterpret_cast<const uint32_t *>(rin);
-            uint8_t dv[kPartItems];
 #pragma unroll
             for (int it = 0; it < kPartItems; ++it) {
                 const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
-                rec[it] = (e < nvalid) ? (uint64_t)LD_P(rin32 + base + e) : 0ull;
-                dv[it] = (e < nvalid) ? din[base + e] : (uint8_t)0;
-            }
-#pragma unroll
-            for (int it = 0; it < kPartItems; ++it) {
-                key[it] = (uint32_t)dv[it] << shift;
-                rec[it] |= (uint64_t)dv[it] << 32;
+                bad |= (FULL || e < nvalid) && (pv[it] < 0 || (!NOTS && tv[it] < 0));
+                if (n0) {
+                    bool esc = false;
+                    const uint32_t r32 =
+                        NOTS ? (skv[it] & ((1u << F.rb) - 1u)) |
+                                   ((uint32_t)(pv[it] < 0 ? 0 : (pv[it] > F.pc_max ? F.pc_max : pv[it])) << F.rb)
+                             : pack_rec32(skv[it], pv[it], tv[it], tbase, F, esc);
+                    // stage: record | pass-0 digit << 32 | pass-1 digit << 40; escape flag in bit 48
+                    rec[it] = (uint64_t)r32 | ((uint64_t)((skv[it] >> shift) & (kDigits - 1)) << 32) |
+                              ((uint64_t)((skv[it] >> (shift + kDigitBits)) & (kDigits - 1)) << 40) |
+                              ((uint64_t)esc << 48);
+                } else {
+                    rec[it] = pack_rec(skv[it], pv[it], tv[it], base + e, tbase, F);
+                }
+                key[it] = skv[it];
+                tv_keep[FIRST ? it : 0] = tv[it];
             }
         } else {
+            if (n0) {
+                const uint32_t *rin32 = reinterpret_cast<const uint32_t *>(rin);
+                uint8_t dv[kPartItems];
 #pragma unroll
-            for (int it = 0; it < kPartItems; ++it) {
-                const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
-                rec[it] = (e < nvalid) ? LD_P(rin + base + e) : 0ull;
-                key[it] = (uint32_t)(rec[it] & F.kmask);
+                for (int it = 0; it < kPartItems; ++it) {
+                    const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
+                    rec[it] = (FULL || e < nvalid) ? (uint64_t)LD_P(rin32 + base + e) : 0ull;
+                    dv[it] = (FULL || e < nvalid) ? din[base + e] : (uint8_t)0;
+                }
+#pragma unroll
+                for (int it = 0; it < kPartItems; ++it) {
+                    key[it] = (uint32_t)dv[it] << shift;
+                    rec[it] |= (uint64_t)dv[it] << 32;
+                }
+            } else {
+#pragma unroll
+                for (int it = 0; it < kPartItems; ++it) {
+                    const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
+                    rec[it] = (FULL || e < nvalid) ? LD_P(rin + base + e) : 0ull;
+                    key[it] = (uint32_t)(rec[it] & F.kmask);
+                }
             }
         }
-    }
-    tile_offsets<kPartBlock>(tile, tiles_per_blk, tileprefix, blockprefix, digit_total, goff, L.wsum);
-    rank_tile_wb<kPartBlock, kPartItems>(key, shift, nvalid, L, reinterpret_cast<uint32_t *>(stage), lpos);
-    int64_t tbase0 = 0, tbase1 = 0;
-    if (LAST && tin) {   // (the approximate kind has no timestamps: its records all escape)
-        tbase0 = n0 ? pack_base32(tin, F) : pack_base(tin, F);
-        tbase1 = fold_base(tin, G);
-    }
-    __syncthreads();   // the counts in `stage` are dead from here on
-#pragma unroll
-    for (int it = 0; it < kPartItems; ++it) {
-        const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
-        if (e < nvalid) {
-            const uint32_t d = (key[it] >> shift) & (kDigits - 1);
-            stage[lpos[it]] = n0 ? (rec[it] & 0x0000FFFFFFFFFFFFull) : rec[it];
-            if (LAST)
-                stage_e[lpos[it]] = (uint16_t)e;
-            else if (perm)   // (null: k_unrank recomputes the positions)
-                ST_PERM(perm + base + e, goff[d] + lpos[it] - L.lstart[d]);
-            if (FIRST && n0 && ((rec[it] >> 48) & 1u))   // escaped: its time beside its position
-                ts0[goff[d] + lpos[it] - L.lstart[d]] = tv_keep[FIRST ? it : 0];
+        tile_offsets<kPartBlock>(tile, tiles_per_blk, tileprefix, blockprefix, digit_total, goff, L.wsum);
+        rank_tile_wb<kPartBlock, kPartItems, FULL>(key, shift, nvalid, L, reinterpret_cast<uint32_t *>(stage), lpos);
+        int64_t tbase0 = 0, tbase1 = 0;
+        if (LAST && tin) {   // (the approximate kind has no timestamps: its records all escape)
+            tbase0 = n0 ? pack_base32(tin, F) : pack_base(tin, F);
+            tbase1 = fold_base(tin, G);
         }
-    }
-    __syncthreads();
-    uint32_t gpos[kPartItems];
-#pragma unroll
-    for (int it = 0; it < kPartItems; ++it) {
-        const int j = it * kPartBlock + tid;
-        if (j < nvalid) {
-            const uint64_t s = stage[j];
-            const uint32_t d = n0 ? (uint32_t)(s >> 32) & (kDigits - 1)
-                                  : ((uint32_t)(s & F.kmask) >> shift) & (kDigits - 1);
-            gpos[it] = goff[d] + (uint32_t)j - L.lstart[d];
-            // runs merge in L2: keep cached
-            if (n0 && !LAST)
-                reinterpret_cast<uint32_t *>(rout)[gpos[it]] = (uint32_t)s;
-            else if (n0)
-                rout[gpos[it]] = fold_rec32((uint32_t)s, (uint32_t)(base + stage_e[j]), tbase0, tbase1, F, G);
-            else
-                rout[gpos[it]] = LAST ? fold_rec(s, (uint32_t)(base + stage_e[j]), tbase0, tbase1, F, G) : s;
-            // the next pass's digit, one byte beside the record (k_hist_dig reads these)
-            if (!LAST && dig_next)
-                dig_next[gpos[it]] = n0 ? (uint8_t)(s >> 40)
-                                        : (uint8_t)(((uint32_t)(s & F.kmask) >> (shift + kDigitBits)) & (kDigits - 1));
-        }
-    }
-    if (IDX) {
-        uint32_t *stage32 = reinterpret_cast<uint32_t *>(stage);
-        uint32_t iv[kPartItems];
+        __syncthreads();   // the counts in `stage` are dead from here on
 #pragma unroll
         for (int it = 0; it < kPartItems; ++it) {
             const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
-            iv[it] = (e < nvalid) ? (FIRST ? (uint32_t)(base + e) : iin[base + e]) : 0u;
+            if (FULL || e < nvalid) {
+                const uint32_t d = (key[it] >> shift) & (kDigits - 1);
+                stage[lpos[it]] = n0 ? (rec[it] & 0x0000FFFFFFFFFFFFull) : rec[it];
+                if (LAST)
+                    stage_e[lpos[it]] = (uint16_t)e;
+                else if (perm)   // (null: k_unrank recomputes the positions)
+                    ST_PERM(perm + base + e, goff[d] + lpos[it] - L.lstart[d]);
+                if (FIRST && n0 && ((rec[it] >> 48) & 1u))   // escaped: its time beside its position
+                    ts0[goff[d] + lpos[it] - L.lstart[d]] = tv_keep[FIRST ? it : 0];
+            }
         }
         __syncthreads();
-#pragma unroll
-        for (int it = 0; it < kPartItems; ++it) {
-            const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
-            if (e < nvalid) stage32[lpos[it]] = iv[it];
-        }
-        __syncthreads();
+        uint32_t gpos[kPartItems];
 #pragma unroll
         for (int it = 0; it < kPartItems; ++it) {
             const int j = it * kPartBlock + tid;
-            if (j < nvalid) iout[gpos[it]] = stage32[j];
+            if (FULL || j < nvalid) {
+                const uint64_t s = stage[j];
+                const uint32_t d = n0 ? (uint32_t)(s >> 32) & (kDigits - 1)
+                                      : ((uint32_t)(s & F.kmask) >> shift) & (kDigits - 1);
+                gpos[it] = goff[d] + (uint32_t)j - L.lstart[d];
+                // runs merge in L2: keep cached
+                if (n0 && !LAST)
+                    reinterpret_cast<uint32_t *>(rout)[gpos[it]] = (uint32_t)s;
+                else if (n0)
+                    rout[gpos[it]] = fold_rec32((uint32_t)s, (uint32_t)(base + stage_e[j]), tbase0, tbase1, F, G);
+                else
+                    rout[gpos[it]] = LAST ? fold_rec(s, (uint32_t)(base + stage_e[j]), tbase0, tbase1, F, G) : s;
+                // the next pass's digit, one byte beside the record (k_hist_dig reads these)
+                if (!LAST && dig_next)
+                    dig_next[gpos[it]] = n0 ? (uint8_t)(s >> 40)
+                                            : (uint8_t)(((uint32_t)(s & F.kmask) >> (shift + kDigitBits)) & (kDigits - 1));
+            }
         }
-    }
-    if (FIRST && __any(bad) && (tid & 63) == 0) atomicOr(err, 1u);
+        if (IDX) {
+            uint32_t *stage32 = reinterpret_cast<uint32_t *>(stage);
+            uint32_t iv[kPartItems];
+#pragma unroll
+            for (int it = 0; it < kPartItems; ++it) {
+                const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
+                iv[it] = (FULL || e < nvalid) ? (FIRST ? (uint32_t)(base + e) : iin[base + e]) : 0u;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < kPartItems; ++it) {
+                const int e = wb_elem<kPartBlock, kPartItems>(it);   // wave-blocked tile order
+                if (FULL || e < nvalid) stage32[lpos[it]] = iv[it];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < kPartItems; ++it) {
+                const int j = it * kPartBlock + tid;
+                if (FULL || j < nvalid) iout[gpos[it]] = stage32[j];
+            }
+        }
+        if (FIRST && __any(bad) && (tid & 63) == 0) atomicOr(err, 1u);
+    };
+    if (TBE_FULL_TILE && nv == kTile)
+        body(std::true_type{});
+    else
+        body(std::false_type{});
 }
 
 // Decide every request of one bucket (see file header).  res[q] is the packed reply of

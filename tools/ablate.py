@@ -264,6 +264,16 @@ VARIANT_SETS = {
         "base_q": ([], ["--workload", "queue", "--no-host-buffer", "--no-strdir", "--no-drain-variant"]),
         "nopipe_q": ([], ["--workload", "queue", "--no-host-buffer", "--no-strdir", "--no-drain-variant", "--no-pipeline"]),
     },
+    "partition": {   # the partition kernels' wave match, full-tile bodies, each against the form before it (run with --plain)
+        "base_u": ([], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "before_u": (["TBE_WAVE_MATCH=0", "TBE_FULL_TILE=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "match0_u": (["TBE_WAVE_MATCH=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "full0_u": (["TBE_FULL_TILE=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+    },
+    "partition_z": {
+        "base_z": ([], ["--workload", "zipf", "--steps", "20", "--warmup", "5"]),
+        "before_z": (["TBE_WAVE_MATCH=0", "TBE_FULL_TILE=0"], ["--workload", "zipf", "--steps", "20", "--warmup", "5"]),
+    },
     "uniform": {
         "base_u": ([], ["--workload", "uniform"]),
         "hist2_u": (["TBE_HIST_AHEAD=2"], ["--workload", "uniform"]),
@@ -326,14 +336,16 @@ def build():
         print("built", name)
 
 
-def run(rounds: int, steps: int):
+def run(rounds: int, steps: int, plain: bool = False):
     results = {}
     for r in range(rounds):
         for name, v in VARIANTS.items():
             defs, extra = v[0], v[1]
             env = dict(os.environ, TBE_LIB=lib_path(defs, v[2] if len(v) > 2 else None), **_env_defs(defs))
             args = ["--full", "--steps", str(steps), "--cpu-seconds", "0"] + ([] if "--no-strdir" in extra else ["--no-host-buffer", "--no-strdir"])
-            if "--warmup" not in extra:
+            if plain:   # bench.py as it runs without flags: the timed steps only (extra may set --steps / --warmup)
+                args = []
+            elif "--warmup" not in extra:
                 args += ["--warmup", "3"]
             out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + extra, env=env,
                                  capture_output=True, text=True, timeout=300)
@@ -342,8 +354,8 @@ def run(rounds: int, steps: int):
                 print(name, "FAILED", out.stderr[-2000:])
                 continue
             d = json.loads(line[0])
-            results.setdefault(name, []).append(d["stage_ms_per_step"])
-            print(r, name, d["ms_per_step"], d["stage_ms_per_step"],
+            results.setdefault(name, []).append(d["ms_per_step"] if plain else d["stage_ms_per_step"])
+            print(r, name, d["ms_per_step"], d.get("stage_ms_per_step"),
                   (d.get("roofline") or {}).get("avg_launch_ms"), d.get("host_buffer_decisions_per_s"),
                   d.get("host_buffer_pinned_decisions_per_s"), flush=True)
             for b in d.get("batch_sweep") or []:
@@ -358,8 +370,9 @@ if __name__ == "__main__":
     ap.add_argument("--run", action="store_true")
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--plain", action="store_true", help="plain bench.py runs (no --full legs): ms_per_step only")
     a = ap.parse_args()
     if a.build:
         build()
     if a.run:
-        run(a.rounds, a.steps)
+        run(a.rounds, a.steps, a.plain)
