@@ -138,6 +138,15 @@ __device__ __forceinline__ ReqTime req_time_rel(int64_t ts_us, const TimeBase &B
     rt.ts = ts_us;
     return rt;
 }
+// What stands in for the stored time of an absent row where a row's field t is derived
+// through req_time_rel: tb_step_ft never reads the field t of an absent row, so any value
+// gives the same decision, and the base keeps the lane on the 32-bit path.  With 0 (below
+// every batch's base) a single absent row sent its whole wave through req_time's 64-bit path:
+// every first touch of a key and every key reclaimed by expiry.
+#ifndef TBE_ABSENT_BASE
+#define TBE_ABSENT_BASE 1                    // 0: pass 0, as before (A/B)
+#endif
+__device__ __forceinline__ int64_t absent_t(const TimeBase &B) { return TBE_ABSENT_BASE ? B.tbase : 0; }
 
 // One evaluation of the acquire script (TB:202-238) on a key's stored row {v, t_us}
 // (the Redis hash {v, t}), with the row's field t supplied by the caller as ft =

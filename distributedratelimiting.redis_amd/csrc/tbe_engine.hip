@@ -42,6 +42,7 @@
 
 #include "../../include/tbe.h"
 #include "tbe_device.hpp"
+#include "tbe_codec.hpp"
 #include "tbe_numfmt.hpp"
 
 #pragma clang fp contract(off)
@@ -831,51 +832,10 @@ __global__ __launch_bounds__(1024) void k_bscan_lb(const uint32_t *__restrict__ 
     if (blk == gridDim.x - 1 && t == 0) bstart[nbt] = excl + total;
 }
 
-// Packed request records (token-bucket kind).  When the key, a permit code and a
-// 32-bit time offset fit one u64, the partition passes and the fold move one 8-byte
-// record per request instead of {key u32, permits i32, ts i64}:
-//
-//   bits [0, kb)            key (< n_keys <= 2^kb)
-//   bits [kb, kb+pb)        permit code min(permits, TokenLimit + 1): x <= TokenLimit
-//                           always (TB:221), so every larger request is decided, and
-//                           leaves the state, exactly like TokenLimit + 1 (TB:224)
-//   bit  kb+pb              escape
-//   bits [kb+pb+1, 64)      ts - base  (base = ts[0] of the batch - 2^(wb-1)), or, with
-//                           the escape bit, the arrival index: the fold then reads the
-//                           request's timestamp from the caller's array
-//
-// wb = 64 - kb - pb - 1 >= 32, so a batch whose timestamps lie within +-35 minutes of
-// its first one never escapes.
-struct PackFmt {
-    uint64_t kmask;     // (1 << kb) - 1
-    int32_t kb;
-    int32_t pb;
-    int32_t pc_max;     // TokenLimit + 1
-    int32_t wb;
-    // Narrow pass-0 records (round 5; token bucket, two passes, fold records, digit stream):
-    // pass 0 writes a u32 per request -- row within the bucket (rb bits), permit code,
-    // escape, ts - base0 (w0 = 32 - rb - pb - 1 bits, base0 = ts[0] - 2^(w0-1)) -- beside
-    // the one-byte digit stream that already carries the pass-1 digit; the pass-0 digit is
-    // the record's position.  An escaped request (time outside the window) also writes its
-    // timestamp to a side array at its pass-0 output position, where the fold finds it.
-    // 4 + 1 bytes instead of 8 + 1 written by pass 0 and read by pass 1.
-    int32_t n0;         // 1: pass 0 writes narrow records
-    int32_t rb;         // row bits (r_bits) of a narrow record
-    int32_t w0;         // time-offset bits of a narrow record
-};
+// PackFmt (packed request records, narrow pass-0 records) and FoldFmt (fold records), their bit
+// layouts and the narrow-record packers: tbe_codec.hpp
 __device__ __forceinline__ int64_t pack_base32(const int64_t *__restrict__ ts, const PackFmt &F) {
     return ts[0] - ((int64_t)1 << (F.w0 - 1));
-}
-// A narrow pass-0 record from the partition key (row = its low rb bits); *esc: the time did
-// not fit and goes to the side array.
-__device__ __forceinline__ uint32_t pack_rec32(uint32_t pkey, int32_t p, int64_t ts, int64_t tbase, const PackFmt &F,
-                                               bool &esc) {
-    const uint32_t pc = (uint32_t)(p < 0 ? 0 : (p > F.pc_max ? F.pc_max : p));
-    const uint64_t d = (uint64_t)ts - (uint64_t)tbase;
-    const bool fits = ts >= tbase && (d >> F.w0) == 0;
-    esc = !fits;
-    return (pkey & ((1u << F.rb) - 1u)) | (pc << F.rb) | ((uint32_t)!fits << (F.rb + F.pb)) |
-           (fits ? (uint32_t)d << (F.rb + F.pb + 1) : 0u);
 }
 __device__ __forceinline__ int64_t pack_base(const int64_t *__restrict__ ts, const PackFmt &F) {
     return ts[0] - ((int64_t)1 << (F.wb - 1));
@@ -915,29 +875,6 @@ __device__ __forceinline__ void unpack_rec(uint64_t rec, const int64_t *__restri
     ts = ((rec >> (F.kb + F.pb)) & 1) ? ts_orig[pay] : (int64_t)((uint64_t)tbase + pay);
 }
 
-// Fold records (token-bucket kind, packed, >= 2 partition passes).  The last pass writes,
-// instead of a PackFmt record and its permutation, what the fold and the hot runs need:
-//
-//   bits [0, rb)              row within the bucket (the key field's low r_bits)
-//   bits [rb, rb+pb)          permit code (as PackFmt)
-//   bit  rb+pb                escape
-//   bits [rb+pb+1, +pw)       the request's position in the last pass's INPUT (the previous
-//                             pass's output): its reply goes there, so the last pass needs
-//                             no permutation and no un-partition pass of its own
-//   bits [rb+pb+1+pw, 64)     ts - base1 (tw bits, base1 = ts[0] - 2^(tw-1)); with the
-//                             escape bit: unused, and the fold takes the request's time from
-//                             the previous pass's record at that position
-//
-// pw = ceil_log2(batch), tw = 64 - rb - pb - 1 - pw (config B: 22 bits, +-2.1 s around the
-// batch's first request; the batch spans 10 ms).  Used when tw >= 8.
-struct FoldFmt {
-    int32_t on;
-    int32_t n0;             // pass 0 wrote narrow records: an escaped record's time is rec0[pos] itself
-    int32_t rb, pb, pw, tw;
-    uint32_t nb;            // ordinary buckets
-    uint32_t region_bits;   // 8 * (passes - 1): buckets with equal low region_bits share a reply region
-    uint32_t n_hi;          // ceil(nb / 2^region_bits)
-};
 __device__ __forceinline__ int64_t fold_base(const int64_t *__restrict__ ts, const FoldFmt &G) {
     return ts[0] - ((int64_t)1 << (G.tw - 1));
 }
@@ -947,17 +884,6 @@ __device__ __forceinline__ uint64_t fold_rec(uint64_t rec0, uint32_t pos, int64_
     const uint64_t pc = (rec0 >> F.kb) & ((1ull << F.pb) - 1);
     const bool esc0 = (rec0 >> (F.kb + F.pb)) & 1;
     const int64_t ts = (int64_t)((uint64_t)tbase0 + (rec0 >> (F.kb + F.pb + 1)));
-    const uint64_t d = (uint64_t)ts - (uint64_t)tbase1;
-    const bool fits = !esc0 && ts >= tbase1 && (d >> G.tw) == 0;
-    return row | (pc << G.rb) | ((uint64_t)!fits << (G.rb + G.pb)) | ((uint64_t)pos << (G.rb + G.pb + 1)) |
-           ((fits ? d : 0ull) << (G.rb + G.pb + 1 + G.pw));
-}
-__device__ __forceinline__ uint64_t fold_rec32(uint32_t r32, uint32_t pos, int64_t tbase0, int64_t tbase1,
-                                               const PackFmt &F, const FoldFmt &G) {
-    const uint64_t row = r32 & ((1u << F.rb) - 1u);
-    const uint64_t pc = (r32 >> F.rb) & ((1u << F.pb) - 1u);
-    const bool esc0 = (r32 >> (F.rb + F.pb)) & 1u;
-    const int64_t ts = (int64_t)((uint64_t)tbase0 + (uint64_t)(r32 >> (F.rb + F.pb + 1)));
     const uint64_t d = (uint64_t)ts - (uint64_t)tbase1;
     const bool fits = !esc0 && ts >= tbase1 && (d >> G.tw) == 0;
     return row | (pc << G.rb) | ((uint64_t)!fits << (G.rb + G.pb)) | ((uint64_t)pos << (G.rb + G.pb + 1)) |
@@ -1011,6 +937,43 @@ __device__ __forceinline__ void fold_input(uint64_t rec, uint32_t q, const FoldF
     }
 }
 
+// The same with the record family fixed at compile time (k_fold_wide's FAM): 0 plain records
+// (G.on == 0), 1 fold records over narrow pass-0 records, 2 fold records over 8-byte pass-0
+// records; -1: G decides per launch.  A kernel instance then holds its own decoder alone.
+#ifndef TBE_FOLD_FAM
+#define TBE_FOLD_FAM 1                       // 0: the run-time form, as before (A/B)
+#endif
+template <int FAM>
+__device__ __forceinline__ void fold_input_fam(uint64_t rec, uint32_t q, const FoldFmt &G, int64_t tbase1,
+                                               const uint64_t *__restrict__ rec0,
+                                               const int64_t *__restrict__ ts_orig, int64_t tbase0,
+                                               const PackFmt &F, uint32_t rmask, uint32_t &row, int32_t &p,
+                                               int64_t &ts, uint32_t &pos) {
+    if (FAM < 0) {
+        fold_input(rec, q, G, tbase1, rec0, ts_orig, tbase0, F, rmask, row, p, ts, pos);
+    } else if (FAM == 0) {
+        uint32_t k;
+        unpack_rec(rec, ts_orig, tbase0, F, k, p, ts);
+        row = k & rmask;
+        pos = q;
+    } else {
+        row = (uint32_t)(rec & ((1ull << G.rb) - 1));
+        p = (int32_t)((rec >> G.rb) & ((1ull << G.pb) - 1));
+        pos = (uint32_t)((rec >> (G.rb + G.pb + 1)) & ((1ull << G.pw) - 1));
+        if ((rec >> (G.rb + G.pb)) & 1) {
+            if (FAM == 1) {
+                ts = (int64_t)rec0[pos];   // the side array of narrow pass-0 records' escaped times
+            } else {
+                uint32_t k;
+                int32_t p0;
+                unpack_rec(rec0[pos], ts_orig, tbase0, F, k, p0, ts);
+            }
+        } else {
+            ts = (int64_t)((uint64_t)tbase1 + (rec >> (G.rb + G.pb + 1 + G.pw)));
+        }
+    }
+}
+
 // Stable partition pass over packed records (see k_scatter; one 8-byte LDS staging
 // round instead of two).  FIRST: read the caller's arrays, validate permits and
 // timestamps, and pack; otherwise read the previous pass's records.
@@ -1034,8 +997,18 @@ __device__ __forceinline__ void fold_input(uint64_t rec, uint32_t q, const FoldF
 #ifndef TBE_SCATTER0_WAVES
 #define TBE_SCATTER0_WAVES 1
 #endif
-template <bool FIRST, bool HOT = false, bool IDX = false, bool NOTS = false, bool LAST = false>
-__global__ __launch_bounds__(kPartBlock, FIRST ? TBE_SCATTER0_WAVES : 1) void k_scatter_rec(
+// FAM (LAST, kinds with timestamps): the record family fixed at compile time -- 1: narrow pass-0
+// records, packed into fold records by the batch's Pass1Codec `C` (tbe_codec.hpp); 0: 8-byte
+// pass-0 records; -1: F.n0 decides per launch, with the generic packers (the approximate kind,
+// and TBE_PASS1_CODEC=0, A/B)
+#ifndef TBE_PASS1_CODEC
+#define TBE_PASS1_CODEC 1
+#endif
+// The last pass's 45 KB of LDS let three workgroups share a CU; its FAM instances keep the
+// registers for that many waves per SIMD (at most 80 VGPRs at 512 threads)
+constexpr int kLastWaves = 3 * (kPartBlock / 64) / 4;
+template <bool FIRST, bool HOT = false, bool IDX = false, bool NOTS = false, bool LAST = false, int FAM = -1>
+__global__ __launch_bounds__(kPartBlock, FIRST ? TBE_SCATTER0_WAVES : (FAM >= 0 ? kLastWaves : 1)) void k_scatter_rec(
     const uint64_t *__restrict__ kin, const int32_t *__restrict__ pin, const int64_t *__restrict__ tin,
     const uint64_t *__restrict__ rin, uint64_t n, int shift, PackFmt F,
     const uint32_t *__restrict__ tileprefix, const uint32_t *__restrict__ blockprefix,
@@ -1043,14 +1016,15 @@ __global__ __launch_bounds__(kPartBlock, FIRST ? TBE_SCATTER0_WAVES : 1) void k_
     uint32_t *__restrict__ perm, uint32_t *__restrict__ err, const HotSet *__restrict__ hot = nullptr,
     uint32_t nb = 0, int r_bits = 0, const uint32_t *__restrict__ iin = nullptr,
     uint32_t *__restrict__ iout = nullptr, FoldFmt G = FoldFmt{}, uint8_t *__restrict__ dig_next = nullptr,
-    const uint8_t *__restrict__ din = nullptr, int64_t *__restrict__ ts0 = nullptr) {
+    const uint8_t *__restrict__ din = nullptr, int64_t *__restrict__ ts0 = nullptr, Pass1Codec C = Pass1Codec{}) {
     static_assert(!(FIRST && LAST), "fold records come from a pass after the first");
+    static_assert(FAM < 0 || LAST, "the record family is fixed only for the last pass");
     // narrow pass-0 records (F.n0): FIRST writes u32 records (+ escaped times to ts0), LAST
     // reads them with the pass-1 digit from the digit stream `din`; the LDS stage then holds
     // record | digit(s) << 32, since the record no longer carries the key.  The queueing
     // kind (IDX) keeps its arrival index beside them; the approximate kind (NOTS) has no
     // time: its narrow record is row | permit code (round 6)
-    const bool n0 = F.n0 != 0;
+    const bool n0 = FAM < 0 ? F.n0 != 0 : FAM == 1;
     __shared__ RankLds<kPartBlock> L;
     __shared__ uint32_t goff[kDigits];
     __shared__ uint64_t stage[kTile];
@@ -1142,7 +1116,7 @@ __global__ __launch_bounds__(kPartBlock, FIRST ? TBE_SCATTER0_WAVES : 1) void k_
         tile_offsets<kPartBlock>(tile, tiles_per_blk, tileprefix, blockprefix, digit_total, goff, L.wsum);
         rank_tile_wb<kPartBlock, kPartItems, FULL>(key, shift, nvalid, L, reinterpret_cast<uint32_t *>(stage), lpos);
         int64_t tbase0 = 0, tbase1 = 0;
-        if (LAST && tin) {   // (the approximate kind has no timestamps: its records all escape)
+        if (LAST && FAM != 1 && tin) {   // (the approximate kind has no timestamps: its records all escape)
             tbase0 = n0 ? pack_base32(tin, F) : pack_base(tin, F);
             tbase1 = fold_base(tin, G);
         }
@@ -1175,7 +1149,8 @@ __global__ __launch_bounds__(kPartBlock, FIRST ? TBE_SCATTER0_WAVES : 1) void k_
                 if (n0 && !LAST)
                     reinterpret_cast<uint32_t *>(rout)[gpos[it]] = (uint32_t)s;
                 else if (n0)
-                    rout[gpos[it]] = fold_rec32((uint32_t)s, (uint32_t)(base + stage_e[j]), tbase0, tbase1, F, G);
+                    rout[gpos[it]] = FAM == 1 ? fold_rec32_codec((uint32_t)s, (uint32_t)(base + stage_e[j]), C)
+                                              : fold_rec32((uint32_t)s, (uint32_t)(base + stage_e[j]), tbase0, tbase1, F, G);
                 else
                     rout[gpos[it]] = LAST ? fold_rec(s, (uint32_t)(base + stage_e[j]), tbase0, tbase1, F, G) : s;
                 // the next pass's digit, one byte beside the record (k_hist_dig reads these)
@@ -1343,12 +1318,12 @@ constexpr int kWideMinShift = TBE_WIDE_MIN_SHIFT;
 static_assert(kWideChunk <= 4096 && kWideTail <= kWideBlock, "election tags and tail list");
 // The rows' field t (TB:203 of the stored t_us), derived per evaluation (a copy cached in
 // LDS cost occupancy and was slower, profiles/r02_ablate_wide*.log)
-#define WIDE_FT_GET(j, srow) req_time_rel((srow).t_us == kAbsent ? 0 : (srow).t_us, TB, 0).new_t
+#define WIDE_FT_GET(j, srow) req_time_rel((srow).t_us == kAbsent ? absent_t(TB) : (srow).t_us, TB, 0).new_t
 #define WIDE_FT_SET(j, v) ((void)0)
 
 // Buckets of >= wide_min requests (every nonempty bucket of a dense batch), shaped as above
 // (three workgroups per CU, chunks of 1536 requests).  k_fold_sparse takes the other buckets.
-template <bool PACKED>
+template <bool PACKED, int FAM = -1>
 __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
     const uint32_t *__restrict__ skeys, const int32_t *__restrict__ sperm,
     const int64_t *__restrict__ sts, const uint64_t *__restrict__ srec,
@@ -1371,7 +1346,6 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
     uint32_t *t_pos = reinterpret_cast<uint32_t *>(aux + kWideTail * 2);   // reply positions
     static_assert(kWideTail * 2 * 8 >= kMaxRows * 4, "hcnt fits in aux");
     __shared__ uint32_t own[kMaxRows];
-    __shared__ uint32_t loaded[kMaxRows / 32];
     __shared__ uint32_t dirty[kMaxRows / 32];
 
     const int tid = threadIdx.x;
@@ -1405,8 +1379,8 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
     // is pulled in (LDS-DMA) and only its dirty lines are written back.
     if (e - s < wide_min) return;
     const bool dense = true;
-    const int64_t tbase = PACKED ? pack_base(ts_orig, F) : 0;
-    const int64_t tbase1 = G.on ? fold_base(ts_orig, G) : 0;
+    const int64_t tbase = (PACKED && FAM != 1) ? pack_base(ts_orig, F) : 0;   // (narrow pass-0 records: unused)
+    const int64_t tbase1 = (FAM < 0 ? G.on != 0 : FAM >= 1) ? fold_base(ts_orig, G) : 0;
     const TimeBase TB = time_base(PACKED ? rel_base(ts_orig, F) : 0, P.ttl_ms);   // fast request times (req_time_rel)
     const bool count_hot = hot_next != nullptr && (e - s) >= kHotMin;
 
@@ -1426,8 +1400,8 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
             pos[r] = q;
             if (q < e) {
                 if (PACKED) {
-                    fold_input(LD_F(srec + q), q, G, tbase1, rec0, ts_orig, tbase, F, rmask, kl[r], pm[r],
-                               tsv[r], pos[r]);
+                    fold_input_fam<FAM>(LD_F(srec + q), q, G, tbase1, rec0, ts_orig, tbase, F, rmask, kl[r], pm[r],
+                                        tsv[r], pos[r]);
                 } else {
                     kl[r] = skeys[q] & rmask;
                     pm[r] = sperm[q];
@@ -1443,10 +1417,7 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
 #endif
     load_chunk(s);   // in flight together with the dense slice
     if (dense) slice_dma();
-    for (uint32_t j = tid; j < (R + 31) / 32; j += kWideBlock) {
-        loaded[j] = 0;
-        dirty[j] = 0;
-    }
+    for (uint32_t j = tid; j < (R + 31) / 32; j += kWideBlock) dirty[j] = 0;
 #ifdef TBE_FOLD_COPY_ONLY
     // A/B floor (not a decision path): the fold's memory traffic without its rounds --
     // records and slice in, the whole slice and one reply per request out
@@ -1751,7 +1722,7 @@ constexpr int64_t kRowWindow = (int64_t)1 << 31;          // k_drain's time base
 
 // Field t of a stored row (TB:203 applied to t_us; only used while the key is present).
 __device__ __forceinline__ double field_t(int64_t t_us, const TimeBase &B) {
-    return req_time_rel(t_us == kAbsent ? 0 : t_us, B, 0).new_t;
+    return req_time_rel(t_us == kAbsent ? absent_t(B) : t_us, B, 0).new_t;
 }
 
 // Sparse buckets of a sparse batch (fewer than wide_min requests; 2^20 requests over 1e8
@@ -2623,7 +2594,7 @@ __device__ __forceinline__ void q_step(Slot &st, uint64_t &hdr, bool &smod, bool
     bool granted = false;
     if (p == 0 || !(cnt > 0 && Q.order == 0)) {                // Q:153
         bool m;
-        const double ft = req_time_rel(st.t_us == kAbsent ? 0 : st.t_us, TB, 0).new_t;   // the row's field t
+        const double ft = req_time_rel(st.t_us == kAbsent ? absent_t(TB) : st.t_us, TB, 0).new_t;   // the row's field t
         const uint32_t reply = tb_step_ft(st, ft, p, rq, P, m);
         smod |= m;
         evaluated = true;
@@ -2700,7 +2671,7 @@ struct DrainLog {
 __device__ __forceinline__ uint32_t tick_step(Slot &row, int32_t permits, const ReqTime &rq, const TimeBase &TB,
                                               const TbParams &P, bool &modified) {
 #if TBE_TICK_FT
-    return tb_step_ft(row, req_time_rel(row.t_us == kAbsent ? 0 : row.t_us, TB, 0).new_t, permits, rq, P, modified);
+    return tb_step_ft(row, req_time_rel(row.t_us == kAbsent ? absent_t(TB) : row.t_us, TB, 0).new_t, permits, rq, P, modified);
 #else
     (void)TB;
     return tb_step(row, permits, rq, P, modified);
@@ -4307,6 +4278,21 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
         k_colscan<<<kDigits, kBlock, 0, sp>>>(w.blocksum, nblk, out.blockprefix, out.digit_total);
         stage_end(e, ST_COLSCAN, sp);
         stage_begin(e, ST_SCATTER, sp);
+        // the last pass of a batch with timestamps, per record family (k_scatter_rec's FAM)
+#define LAUNCH_LAST_FAM(IDXK, FAMK, iin_, iout_)                                                               \
+    k_scatter_rec<false, false, IDXK, false, true, FAMK><<<ntiles, kPartBlock, 0, sp>>>(                       \
+        nullptr, nullptr, ts, w.pass[p - 1].rec, n, shift, pf, out.tileprefix, out.blockprefix,                \
+        out.digit_total, tpb, out.rec, nullptr, w.err, nullptr, 0, 0, iin_, iout_, G, nullptr, w.dig1, nullptr, \
+        pass1_codec(pf, G, true))
+#define LAUNCH_LAST(IDXK, iin_, iout_)                                                     \
+    do {                                                                                   \
+        if (TBE_PASS1_CODEC && G.n0 && pass1_codec_ok(pf, G))                              \
+            LAUNCH_LAST_FAM(IDXK, 1, iin_, iout_);                                         \
+        else if (TBE_PASS1_CODEC && !G.n0)                                                 \
+            LAUNCH_LAST_FAM(IDXK, 0, iin_, iout_);                                         \
+        else                                                                               \
+            LAUNCH_LAST_FAM(IDXK, -1, iin_, iout_);                                        \
+    } while (0)
         if (e->packed && approx && p == 0)
             k_scatter_rec<true, false, false, true><<<ntiles, kPartBlock, 0, sp>>>(
                 keys, permits, nullptr, nullptr, n, shift, pf, out.tileprefix, out.blockprefix,
@@ -4327,10 +4313,7 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
                 out.digit_total, tpb, out.rec, unrank ? nullptr : out.perm, w.err, nullptr, 0, 0, nullptr, out.idx,
                 FoldFmt{}, dnext, nullptr, w.ts0);
         else if (e->packed && wait && G.on && p == e->passes - 1)
-            k_scatter_rec<false, false, true, false, true><<<ntiles, kPartBlock, 0, sp>>>(
-                nullptr, nullptr, ts, w.pass[p - 1].rec, n, shift, pf, out.tileprefix,
-                out.blockprefix, out.digit_total, tpb, out.rec, nullptr, w.err, nullptr, 0, 0,
-                w.pass[p - 1].idx, out.idx, G, nullptr, w.dig1);
+            LAUNCH_LAST_FAM(true, -1, w.pass[p - 1].idx, out.idx);   // (queueing kind: FAM 1 would need scratch)
         else if (e->packed && wait)
             k_scatter_rec<false, false, true><<<ntiles, kPartBlock, 0, sp>>>(
                 nullptr, nullptr, nullptr, w.pass[p - 1].rec, n, shift, e->pf, out.tileprefix,
@@ -4347,10 +4330,7 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
                 out.digit_total, tpb, out.rec, unrank ? nullptr : out.perm, w.err, nullptr, 0, 0, nullptr,
                 nullptr, FoldFmt{}, dnext, nullptr, w.ts0);
         else if (e->packed && G.on && p == e->passes - 1)
-            k_scatter_rec<false, false, false, false, true><<<ntiles, kPartBlock, 0, sp>>>(
-                nullptr, nullptr, ts, w.pass[p - 1].rec, n, shift, pf, out.tileprefix,
-                out.blockprefix, out.digit_total, tpb, out.rec, nullptr, w.err, nullptr, 0, 0, nullptr,
-                nullptr, G, nullptr, w.dig1, nullptr);
+            LAUNCH_LAST(false, nullptr, nullptr);
         else if (e->packed)
             k_scatter_rec<false><<<ntiles, kPartBlock, 0, sp>>>(
                 nullptr, nullptr, nullptr, w.pass[p - 1].rec, n, shift, e->pf, out.tileprefix,
@@ -4407,6 +4387,22 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
         HIP_TRY(e, hipStreamWaitEvent(sf, e->ev_part, 0));
     }
     // hot_next->n_cand was reset by the k_hot_update that consumed its last nominations
+    // the packed wide fold, per record family (k_fold_wide's FAM, fold_input_fam)
+#define LAUNCH_WIDE_FAM(FAMK, grid_, dlist_)                                                              \
+    k_fold_wide<true, FAMK><<<grid_, kWideBlock, 0, sf>>>(                                                \
+        nullptr, nullptr, nullptr, sorted.rec, ts, e->pf, w.bstart, e->r_bits, e->cfg.n_keys, e->table,   \
+        e->params, w.res[0], w.err, hot_next, e->narrow ? 1u : 0u, tb_wmin, G, rec0, dlist_)
+#define LAUNCH_WIDE(grid_, dlist_)                      \
+    do {                                                \
+        if (!TBE_FOLD_FAM)                              \
+            LAUNCH_WIDE_FAM(-1, grid_, dlist_);         \
+        else if (!G.on)                                 \
+            LAUNCH_WIDE_FAM(0, grid_, dlist_);          \
+        else if (G.n0)                                  \
+            LAUNCH_WIDE_FAM(1, grid_, dlist_);          \
+        else                                            \
+            LAUNCH_WIDE_FAM(2, grid_, dlist_);          \
+    } while (0)
     stage_begin(e, ST_FOLD, sf);
     if (approx) {
         AParams a = e->ap;
@@ -4450,9 +4446,7 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
         const uint32_t walk = e->packed ? fold_grid : e->nbuckets;
         const unsigned sgrid = (unsigned)std::min<uint64_t>((walk + kSpWaves - 1) / kSpWaves, 2048);
         if (e->packed) {
-            k_fold_wide<true><<<dgrid, kWideBlock, 0, sf>>>(
-                nullptr, nullptr, nullptr, sorted.rec, ts, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
-                e->table, e->params, w.res[0], w.err, hot_next, e->narrow ? 1u : 0u, tb_wmin, G, rec0, w.dlist);
+            LAUNCH_WIDE(dgrid, w.dlist);
             k_fold_sparse<true><<<sgrid, kSpBlock, 0, sf>>>(
                 nullptr, nullptr, nullptr, sorted.rec, ts, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
                 e->table, e->params, w.res[0], w.err, e->narrow ? 1u : 0u, tb_wmin, G, rec0, walk);
@@ -4465,9 +4459,7 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
                 e->cfg.n_keys, e->table, e->params, w.res[0], w.err, 0u, tb_wmin, G, rec0, walk);
         }
     } else if (e->packed) {   // a dense batch: k_fold_wide takes every bucket
-        k_fold_wide<true><<<fold_grid, kWideBlock, 0, sf>>>(
-            nullptr, nullptr, nullptr, sorted.rec, ts, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
-            e->table, e->params, w.res[0], w.err, hot_next, e->narrow ? 1u : 0u, tb_wmin, G, rec0);
+        LAUNCH_WIDE(fold_grid, nullptr);
     } else {
         k_fold_wide<false><<<e->nbuckets, kWideBlock, 0, sf>>>(
             sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,

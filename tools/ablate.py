@@ -274,6 +274,13 @@ VARIANT_SETS = {
         "base_z": ([], ["--workload", "zipf", "--steps", "20", "--warmup", "5"]),
         "before_z": (["TBE_WAVE_MATCH=0", "TBE_FULL_TILE=0"], ["--workload", "zipf", "--steps", "20", "--warmup", "5"]),
     },
+    "codec": {   # record families at compile time, the last pass's codec, absent rows on the 32-bit time path (run with --plain)
+        "base_u": ([], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "before_u": (["TBE_PASS1_CODEC=0", "TBE_FOLD_FAM=0", "TBE_ABSENT_BASE=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "pass1codec0_u": (["TBE_PASS1_CODEC=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "foldfam0_u": (["TBE_FOLD_FAM=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "absent0_u": (["TBE_ABSENT_BASE=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+    },
     "uniform": {
         "base_u": ([], ["--workload", "uniform"]),
         "hist2_u": (["TBE_HIST_AHEAD=2"], ["--workload", "uniform"]),
