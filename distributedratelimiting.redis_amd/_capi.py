@@ -39,8 +39,10 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_import_state", "tbe_queue_cancel", "tbe_alloc_host", "tbe_free_host",
             "tbe_approx_export_state", "tbe_approx_import_state", "tbe_wait_batch_tick_device",
             "tbe_approx_sync_stream", "tbe_batch_format", "tbe_expired_device",
-            "tbe_export_live_device", "tbe_export_live", "tbe_import_rows_device", "tbe_import_rows")
+            "tbe_export_live_device", "tbe_export_live", "tbe_import_rows_device", "tbe_import_rows",
+            "tbe_approx_acquire_batch_retry", "tbe_approx_acquire_batch_retry_device")
 TBE_WAIT_FAILED, TBE_WAIT_GRANTED, TBE_WAIT_QUEUED, TBE_WAIT_REJECTED = 0, 1, 2, 3
+TBE_RETRY_NONE, TBE_RETRY_OVERFLOW = -1, 2**63 - 1   # retry_after_ticks of the approximate kind
 
 
 class TbeConfig(Structure):
@@ -167,6 +169,12 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_approx_acquire_batch_device.restype = c_int32
     lib.tbe_approx_acquire_batch_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_int32,
                                                     c_int64, c_void_p, c_void_p, c_void_p]
+    lib.tbe_approx_acquire_batch_retry.restype = c_int32
+    lib.tbe_approx_acquire_batch_retry.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_int32, c_int64,
+                                                   c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]
+    lib.tbe_approx_acquire_batch_retry_device.restype = c_int32
+    lib.tbe_approx_acquire_batch_retry_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_int32,
+                                                          c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.tbe_import_state.restype = c_int32
     lib.tbe_import_state.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]
     lib.tbe_approx_export_state.restype = c_int32

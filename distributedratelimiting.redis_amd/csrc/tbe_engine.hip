@@ -44,6 +44,7 @@
 #include "tbe_device.hpp"
 #include "tbe_codec.hpp"
 #include "tbe_numfmt.hpp"
+#include "tbe_retry.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1857,14 +1858,28 @@ __device__ __forceinline__ uint16_t wait16(uint32_t v) {
     return (uint16_t)(((v >> 30) << 14) | (rem == kRemNone ? kRemNone16 : (rem & kRemNone16)));
 }
 
-template <bool FINAL, bool WAIT, int W = 4>
+// The status of a wait reply of width W.
+template <int W>
+__device__ __forceinline__ uint32_t wait_status(uint32_t v) {
+    return W == 1 ? v >> 6 : W == 2 ? v >> 14 : v >> 30;
+}
+
+// RETRY (approximate kind, tbe_approx_acquire_batch_retry): the 32-bit deficit of each
+// FAILED request travels with its reply -- def_out[i] = def_in[perm[i]] for the lanes whose
+// gathered status is FAILED -- and the final pass stores retry[i] in arrival order: the
+// ticks of that deficit (retry_ticks, tbe_retry.hpp), TBE_RETRY_NONE for every other status.
+template <bool FINAL, bool WAIT, int W = 4, bool RETRY = false>
 __global__ __launch_bounds__(kUnBlock) void k_unscatter(uint64_t n, const uint32_t *__restrict__ perm,
                                                           const uint32_t *__restrict__ res_in,
                                                           uint32_t *__restrict__ res_out,
                                                           uint8_t *__restrict__ granted,
                                                           int32_t *__restrict__ remaining,
                                                           const uint32_t *__restrict__ err = nullptr,
-                                                          uint32_t *__restrict__ sticky = nullptr) {
+                                                          uint32_t *__restrict__ sticky = nullptr,
+                                                          const uint32_t *__restrict__ def_in = nullptr,
+                                                          uint32_t *__restrict__ def_out = nullptr,
+                                                          int64_t *__restrict__ retry = nullptr,
+                                                          double rate = 0.0) {
     // One workgroup per 8192 positions, XCD-aware like k_scatter: the tile's gathers land
     // in the digit runs of the partition tiles it covers, which stay in this XCD's L2.
     const int tid = threadIdx.x;
@@ -1886,6 +1901,22 @@ __global__ __launch_bounds__(kUnBlock) void k_unscatter(uint64_t n, const uint32
                                 : W == 2 ? (uint32_t)reinterpret_cast<const uint16_t *>(res_in)[pv[it]]
                                          : res_in[pv[it]])
                              : 0u;
+    }
+    if constexpr (RETRY) {
+        uint32_t df[kUnItems];
+#pragma unroll
+        for (int it = 0; it < kUnItems; ++it) {
+            const int e = it * kUnBlock + tid;
+            df[it] = (e < nvalid && wait_status<W>(r[it]) == TBE_WAIT_FAILED) ? def_in[pv[it]] : 0u;
+        }
+#pragma unroll
+        for (int it = 0; it < kUnItems; ++it) {
+            const int e = it * kUnBlock + tid;
+            if (e >= nvalid) continue;
+            const bool failed = wait_status<W>(r[it]) == TBE_WAIT_FAILED;
+            if (FINAL) ST_U(retry + base + e, failed ? retry_ticks(df[it], rate) : (int64_t)TBE_RETRY_NONE);
+            else if (failed) def_out[base + e] = df[it];
+        }
     }
 #pragma unroll
     for (int it = 0; it < kUnItems; ++it) {
@@ -1927,14 +1958,17 @@ __global__ __launch_bounds__(kUnBlock) void k_unscatter(uint64_t n, const uint32
 // first pass stored as one byte per request, and the same tile offsets -- so pass 0 writes
 // no 4-byte permutation and this pass reads one byte per request instead of four:
 // granted[i], remaining[i] = reply at that position.  W: reply width (1 or 4 bytes).
-template <int W, bool WAIT = false>
+template <int W, bool WAIT = false, bool RETRY = false>
 __global__ __launch_bounds__(kPartBlock) void k_unrank(uint64_t n, const uint8_t *__restrict__ digit,
                                                        const uint32_t *__restrict__ tileprefix,
                                                        const uint32_t *__restrict__ blockprefix,
                                                        const uint32_t *__restrict__ digit_total,
                                                        uint32_t tiles_per_blk, const uint32_t *__restrict__ res_in,
                                                        uint8_t *__restrict__ granted,
-                                                       int32_t *__restrict__ remaining) {
+                                                       int32_t *__restrict__ remaining,
+                                                       const uint32_t *__restrict__ def_in = nullptr,
+                                                       int64_t *__restrict__ retry = nullptr,
+                                                       double rate = 0.0) {
     __shared__ RankLds<kPartBlock> L;
     __shared__ uint32_t goff[kDigits];
     __shared__ uint32_t wcnt[(kPartBlock / 64) * kDigits];
@@ -1958,6 +1992,16 @@ __global__ __launch_bounds__(kPartBlock) void k_unrank(uint64_t n, const uint8_t
                               : W == 2 ? (uint32_t)reinterpret_cast<const uint16_t *>(res_in)[q]
                                        : res_in[q])
                            : 0u;
+    }
+    if constexpr (RETRY) {   // as k_unscatter's final RETRY pass
+#pragma unroll
+        for (int it = 0; it < kPartItems; ++it) {
+            const int e = wb_elem<kPartBlock, kPartItems>(it);
+            if (e >= nvalid) continue;
+            const uint32_t q = goff[dg[it]] + lpos[it] - L.lstart[dg[it]];
+            const bool failed = wait_status<W>(r[it]) == TBE_WAIT_FAILED;
+            ST_U(retry + base + e, failed ? retry_ticks(def_in[q], rate) : (int64_t)TBE_RETRY_NONE);
+        }
     }
 #pragma unroll
     for (int it = 0; it < kPartItems; ++it) {
@@ -3251,15 +3295,24 @@ static_assert(kAChunk <= 4096, "election tags");
 #define TBE_A_WAVES 6                        // minimum waves per SIMD: 80 VGPRs, 3 workgroups per CU
                                              // (0.867 -> 0.688 ms, profiles/r02_ablate_queue_dma_approx_waves.log)
 #endif
-template <bool PACKED>
-__global__ __launch_bounds__(kFoldBlock, TBE_A_WAVES) void k_fold_a(
+// RETRY (tbe_approx_acquire_batch_retry): a request decided FAILED also leaves the 32-bit
+// deficit of its RetryAfter (A:390-395) -- max(0, _globalThrottleScore + _localThrottleScore
+// + permitCount + _queueCount - TokenLimit) in C# unchecked int32, on the key's row as it
+// stands at that request's turn -- in deficit[] at its reply position.  The global score is
+// gathered from the client view on that path only; positions of other statuses are not
+// written (the un-partition reads a deficit only beside a FAILED status).
+// The RETRY forms ask for 4 waves per SIMD (128 VGPRs, two workgroups per CU): the deficits
+// held across the owner rounds spill at 80.
+template <bool PACKED, bool RETRY = false>
+__global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
     const uint32_t *__restrict__ skeys, const int32_t *__restrict__ sperm,
     const uint32_t *__restrict__ sidx, const uint64_t *__restrict__ srec, PackFmt F,
     const uint32_t *__restrict__ bstart, int r_bits,
     uint64_t n_keys, ALocal *__restrict__ alocal, uint64_t *__restrict__ ring, AParams A,
     uint32_t *__restrict__ res, uint32_t *__restrict__ ev_cause, int64_t *__restrict__ ev_id,
     uint32_t *__restrict__ ev_count, uint32_t ev_cap, const uint32_t *__restrict__ err, uint32_t rw, FoldFmt G,
-    const uint64_t *__restrict__ rec0) {
+    const uint64_t *__restrict__ rec0, const AClient *__restrict__ aclient = nullptr,
+    uint32_t *__restrict__ deficit = nullptr) {
     __shared__ ALocal sl[kMaxRows];
     __shared__ uint32_t own[kMaxRows];
     __shared__ uint32_t rbuf[kAChunk];
@@ -3303,11 +3356,13 @@ __global__ __launch_bounds__(kFoldBlock, TBE_A_WAVES) void k_fold_a(
         for (uint32_t j = tid; j < R; j += kFoldBlock) own[j] = 0;
         uint32_t kl[kAPer];
         int32_t pm[kAPer];
+        uint32_t df[RETRY ? kAPer : 1];   // RETRY: the deficits of this thread's FAILED requests
         uint32_t pend = 0;
 #pragma unroll
         for (int r = 0; r < kAPer; ++r) {
             const uint32_t q = c + r * kFoldBlock + tid;
             kl[r] = 0; pm[r] = 0;
+            if constexpr (RETRY) df[r] = 0;
             if (q < e) {
                 if (PACKED) {   // key | permit code | escape | arrival index (k_scatter_rec NOTS),
                                 // or a fold record: row | permit code | escape | reply position
@@ -3458,6 +3513,11 @@ __global__ __launch_bounds__(kFoldBlock, TBE_A_WAVES) void k_fold_a(
                     modified = true;
                 }
                 rbuf[r * kFoldBlock + tid] = pack_wait(status, evaluated, (uint32_t)avail_of(a));
+                if constexpr (RETRY) {
+                    if (status == TBE_WAIT_FAILED) {   // a failure modifies nothing: `a` is the state it met
+                        df[r] = retry_deficit(aclient[row0 + kl[r]].global, a.local, p, a.qsum, A.token_limit);
+                    }
+                }
                 if (modified) {
                     sl[kl[r]] = a;
                     atomicOr(&dirty[kl[r] >> 5], 1u << (kl[r] & 31));
@@ -3476,6 +3536,8 @@ __global__ __launch_bounds__(kFoldBlock, TBE_A_WAVES) void k_fold_a(
                 const uint32_t at = PACKED ? reply_pos(q) : q;
                 if (rw == 2) reinterpret_cast<uint16_t *>(res)[at] = wait16(rbuf[r * kFoldBlock + tid]);
                 else res[at] = rbuf[r * kFoldBlock + tid];
+                if constexpr (RETRY)
+                    if ((rbuf[r * kFoldBlock + tid] >> 30) == TBE_WAIT_FAILED) deficit[at] = df[r];
             }
         }
     }
@@ -3823,6 +3885,9 @@ struct Workspace {
     std::vector<PassBufs> pass;
     uint32_t *blocksum = nullptr;
     uint32_t *res[2] = {nullptr, nullptr};
+    // RetryAfter deficits beside the replies (approximate kind), allocated by the first
+    // batch that asks for them; [1] only where an intermediate un-partition pass runs
+    uint32_t *def[2] = {nullptr, nullptr};
     uint32_t *bstart = nullptr;
     uint32_t *bcount = nullptr;   // requests per bucket of the batch
     uint32_t *dlist = nullptr;    // sparse batches: count + ids of the dense buckets (k_bscan)
@@ -3947,6 +4012,7 @@ struct tbe_engine {
     int64_t *d_ts = nullptr;
     uint8_t *d_granted = nullptr;
     int32_t *d_remaining = nullptr;
+    int64_t *d_retry = nullptr;   // tbe_approx_acquire_batch_retry only (stage_cap entries, on first use)
 
     // Stage timing (TBE_FLAG_STAGE_TIMING): an event pair per stage per batch, recorded
     // on the launch stream without any host synchronisation; read in tbe_stage_times.
@@ -4014,6 +4080,8 @@ void free_workspace(Workspace &w) {
     dfree(w.segbase);
     dfree(w.res[0]);
     dfree(w.res[1]);
+    dfree(w.def[0]);
+    dfree(w.def[1]);
     dfree(w.bstart);
     dfree(w.bcount);
     w.err = nullptr;   // (the word after the bucket counts)
@@ -4032,6 +4100,7 @@ void free_staging(tbe_engine *e) {
     dfree(e->d_ts);
     dfree(e->d_granted);
     dfree(e->d_remaining);
+    dfree(e->d_retry);
     e->stage_cap = 0;
 }
 
@@ -4182,7 +4251,7 @@ FoldFmt batch_fold_fmt(const tbe_engine *e, uint64_t n) {
 tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits,
                      const int64_t *ts, uint64_t n, uint8_t *granted, int32_t *remaining,
                      hipStream_t caller, int64_t id_base = 0, hipEvent_t in_ready = nullptr,
-                     hipStream_t out_stream = nullptr, uint32_t ai_base = 0) {
+                     hipStream_t out_stream = nullptr, uint32_t ai_base = 0, int64_t *retry = nullptr) {
     const bool approx = e->cfg.kind == TBE_KIND_APPROXIMATE;
     const bool wait = e->cfg.kind != TBE_KIND_TOKEN_BUCKET;   // status-packed replies
     if (n == 0) return TBE_OK;
@@ -4193,6 +4262,11 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
     Workspace &w = e->ws[pipe ? e->ws_cur : 0];
     tbe_status rc = ensure_workspace(e, w, n);
     if (rc != TBE_OK) return rc;
+    if (retry) {   // (approximate kind) the deficit side arrays, as large as the replies'
+        if (!w.def[0]) HIP_TRY(e, hipMalloc(&w.def[0], w.cap_n * sizeof(uint32_t)));
+        if (!w.def[1] && e->passes - (batch_fold_fmt(e, n).on ? 2 : 1) >= 1)
+            HIP_TRY(e, hipMalloc(&w.def[1], w.cap_n * sizeof(uint32_t)));
+    }
     uint32_t ntiles, nblk, tpb;
     tiles_for(n, ntiles, nblk, tpb);
     hipStream_t sf = caller ? caller : e->stream, sp = sf;
@@ -4409,7 +4483,19 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
         a.id_base = id_base;
         a.wait = e->wait_mode;
         a.ai_base = ai_base;
-        if (e->packed)
+        if (retry && e->packed)
+            k_fold_a<true, true><<<fold_grid, kFoldBlock, 0, sf>>>(
+                nullptr, nullptr, nullptr, sorted.rec, e->pf, w.bstart, e->r_bits, e->cfg.n_keys, e->alocal,
+                e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
+                (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(), G, rec0, e->aclient,
+                w.def[0]);
+        else if (retry)
+            k_fold_a<false, true><<<e->nbuckets, kFoldBlock, 0, sf>>>(
+                sorted.keys, sorted.permits, sorted.idx, nullptr, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
+                e->alocal, e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
+                (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(), G, rec0, e->aclient,
+                w.def[0]);
+        else if (e->packed)
             k_fold_a<true><<<fold_grid, kFoldBlock, 0, sf>>>(
                 nullptr, nullptr, nullptr, sorted.rec, e->pf, w.bstart, e->r_bits, e->cfg.n_keys, e->alocal,
                 e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
@@ -4500,7 +4586,15 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
     int cur = 0;
     // with fold records the replies are already in pass passes-2's output order
     for (int p = e->passes - (G.on ? 2 : 1); p >= 1; --p) {
-        if (e->narrow && !approx)
+        if (retry && e->medium)
+            k_unscatter<false, false, 2, true><<<untiles, kUnBlock, 0, sf>>>(
+                n, w.pass[p].perm, w.res[cur], w.res[cur ^ 1], nullptr, nullptr, nullptr, nullptr, w.def[cur],
+                w.def[cur ^ 1]);
+        else if (retry)
+            k_unscatter<false, false, 4, true><<<untiles, kUnBlock, 0, sf>>>(
+                n, w.pass[p].perm, w.res[cur], w.res[cur ^ 1], nullptr, nullptr, nullptr, nullptr, w.def[cur],
+                w.def[cur ^ 1]);
+        else if (e->narrow && !approx)
             k_unscatter<false, false, 1><<<untiles, kUnBlock, 0, sf>>>(n, w.pass[p].perm, w.res[cur],
                                                                    w.res[cur ^ 1], nullptr, nullptr);
         else if (e->medium)
@@ -4514,7 +4608,24 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
 #define TBE_UNRANK(...)                                                                             \
     __VA_ARGS__<<<ntiles, kPartBlock, 0, sf>>>(n, w.dig0, w.pass[0].tileprefix, w.pass[0].blockprefix, \
                                                w.pass[0].digit_total, tpb, w.res[cur], granted, remaining)
-    if (unrank && !wait && e->narrow)
+    // (the approximate kind has no one-byte replies: its RETRY forms are the 2- and 4-byte ones)
+    if (retry && unrank && e->medium)
+        k_unrank<2, true, true><<<ntiles, kPartBlock, 0, sf>>>(
+            n, w.dig0, w.pass[0].tileprefix, w.pass[0].blockprefix, w.pass[0].digit_total, tpb, w.res[cur],
+            granted, remaining, w.def[cur], retry, e->ap.decay_rate);
+    else if (retry && unrank)
+        k_unrank<4, true, true><<<ntiles, kPartBlock, 0, sf>>>(
+            n, w.dig0, w.pass[0].tileprefix, w.pass[0].blockprefix, w.pass[0].digit_total, tpb, w.res[cur],
+            granted, remaining, w.def[cur], retry, e->ap.decay_rate);
+    else if (retry && e->medium)
+        k_unscatter<true, true, 2, true><<<untiles, kUnBlock, 0, sf>>>(
+            n, w.pass[0].perm, w.res[cur], nullptr, granted, remaining, w.err, e->sticky, w.def[cur], nullptr,
+            retry, e->ap.decay_rate);
+    else if (retry)
+        k_unscatter<true, true, 4, true><<<untiles, kUnBlock, 0, sf>>>(
+            n, w.pass[0].perm, w.res[cur], nullptr, granted, remaining, w.err, e->sticky, w.def[cur], nullptr,
+            retry, e->ap.decay_rate);
+    else if (unrank && !wait && e->narrow)
         TBE_UNRANK(k_unrank<1>);
     else if (unrank && !wait)
         TBE_UNRANK(k_unrank<4>);
@@ -5251,9 +5362,27 @@ static tbe_status sync_queued(tbe_engine *e) {
 // synchronised.  Evictions (NewestFirst waits only) go to the engine's eviction log, read
 // lazily by tbe_evicted; its capacity n + queued_total bounds them (every eviction
 // removes an entry queued before the batch or by it).
+// The client view {est, global} of every key, where the last sync left it to be derived
+// (aclient_lazy): enqueued on the engine's stream, which ordered that sync, and `st` waits
+// for it by an event.  Nothing synchronises the host.
+static tbe_status materialise_aclient(tbe_engine *e, hipStream_t st) {
+    if (!e->aclient_lazy) return TBE_OK;
+    const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
+    k_aclient_derive<<<(unsigned)blocks, kBlock, 0, e->stream>>>(0, e->cfg.n_keys, e->gv, e->gp, e->aclient,
+                                                                 e->ap.period_s);
+    HIP_TRY(e, hipGetLastError());
+    if (st != e->stream) {
+        HIP_TRY(e, hipEventRecord(e->ev_in, e->stream));
+        HIP_TRY(e, hipStreamWaitEvent(st, e->ev_in, 0));
+    }
+    e->aclient_lazy = false;
+    return TBE_OK;
+}
+
 static tbe_status status_batch_device(tbe_engine *e, const uint64_t *d_keys, const int32_t *d_permits,
                                       const int64_t *d_ts, uint64_t n, int64_t id_base,
-                                      uint8_t *d_status, int32_t *d_remaining, void *stream) {
+                                      uint8_t *d_status, int32_t *d_remaining, void *stream,
+                                      int64_t *d_retry = nullptr) {
     e->evicted.clear();
     e->ev_pending = false;
     if (n == 0) return TBE_OK;
@@ -5276,7 +5405,12 @@ static tbe_status status_batch_device(tbe_engine *e, const uint64_t *d_keys, con
     }
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
     HIP_TRY(e, hipMemsetAsync(e->counters, 0, sizeof(uint32_t), st));
-    tbe_status rc = run_batch(e, d_keys, d_permits, d_ts, n, d_status, d_remaining, st, id_base);
+    if (d_retry) {
+        tbe_status mrc = materialise_aclient(e, st);
+        if (mrc != TBE_OK) return mrc;
+    }
+    tbe_status rc = run_batch(e, d_keys, d_permits, d_ts, n, d_status, d_remaining, st, id_base, nullptr, nullptr, 0,
+                              d_retry);
     if (rc != TBE_OK) return rc;
     e->ev_pending = may_evict;
     if (e->wait_mode == 1) {
@@ -5307,7 +5441,7 @@ tbe_status tbe_import_state(tbe_engine *e, uint64_t first, uint64_t count, const
 
 static tbe_status status_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits,
                                const int64_t *ts_us, uint64_t n, int64_t id_base, uint8_t *status,
-                               int32_t *remaining, uint64_t *n_evicted);
+                               int32_t *remaining, uint64_t *n_evicted, int64_t *retry = nullptr);
 
 tbe_status tbe_wait_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits,
                           const int64_t *ts_us, uint64_t n, int64_t id_base, uint8_t *status,
@@ -5339,6 +5473,16 @@ tbe_status tbe_approx_acquire_batch(tbe_engine *e, const uint64_t *keys, const i
     return status_batch(e, keys, permits, nullptr, n, id_base, status, available, n_evicted);
 }
 
+tbe_status tbe_approx_acquire_batch_retry(tbe_engine *e, const uint64_t *keys, const int32_t *permits,
+                                          uint64_t n, int32_t wait, int64_t id_base, uint8_t *status,
+                                          int32_t *available, int64_t *retry_after_ticks, uint64_t *n_evicted) {
+    if (!e || !n_evicted) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, "not an approximate engine");
+    if (n && !retry_after_ticks) return fail(e, TBE_EINVAL, "null buffer");
+    e->wait_mode = wait ? 1 : 0;
+    return status_batch(e, keys, permits, nullptr, n, id_base, status, available, n_evicted, retry_after_ticks);
+}
+
 tbe_status tbe_wait_batch_device(tbe_engine *e, const uint64_t *d_keys, const int32_t *d_permits,
                                  const int64_t *d_ts_us, uint64_t n, int64_t id_base, int32_t wait,
                                  uint8_t *d_status, int32_t *d_remaining, void *stream) {
@@ -5358,6 +5502,18 @@ tbe_status tbe_approx_acquire_batch_device(tbe_engine *e, const uint64_t *d_keys
     return status_batch_device(e, d_keys, d_permits, nullptr, n, id_base, d_status, d_available, stream);
 }
 
+tbe_status tbe_approx_acquire_batch_retry_device(tbe_engine *e, const uint64_t *d_keys, const int32_t *d_permits,
+                                                 uint64_t n, int32_t wait, int64_t id_base, uint8_t *d_status,
+                                                 int32_t *d_available, int64_t *d_retry_after_ticks,
+                                                 void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, "not an approximate engine");
+    if (n && !d_retry_after_ticks) return fail(e, TBE_EINVAL, "null buffer");
+    e->wait_mode = wait ? 1 : 0;
+    return status_batch_device(e, d_keys, d_permits, nullptr, n, id_base, d_status, d_available, stream,
+                               d_retry_after_ticks);
+}
+
 // Host-buffer queue / approximate batch from page-locked buffers: chunks of kHostChunk
 // requests, copy-in on cin, decide on the engine stream, copy-out on cout, so copies
 // overlap the decisions (as acquire_chunked).  The batch is validated on the host before
@@ -5365,7 +5521,7 @@ tbe_status tbe_approx_acquire_batch_device(tbe_engine *e, const uint64_t *d_keys
 // position, so the result is the unchunked call's.
 static tbe_status status_chunked(tbe_engine *e, const uint64_t *keys, const int32_t *permits, const int64_t *ts,
                                  uint64_t n, int64_t id_base, uint8_t *status, int32_t *remaining,
-                                 uint32_t *nev) {
+                                 uint32_t *nev, int64_t *retry) {
     const uint64_t nch = (n + kHostChunk - 1) / kHostChunk;
     {
         tbe_status rc = copy_in_chunks(e, keys, permits, ts, n, nch);
@@ -5380,8 +5536,11 @@ static tbe_status status_chunked(tbe_engine *e, const uint64_t *keys, const int3
         const uint64_t o = c * kHostChunk, m = std::min(kHostChunk, n - o);
         tbe_status rc = run_batch(e, e->d_keys + o, e->d_permits + o, ts ? e->d_ts + o : nullptr, m,
                                   e->d_granted + o, e->d_remaining + o, nullptr, id_base + (int64_t)o,
-                                  e->ev_chunk[c], e->cout, (uint32_t)o);
+                                  e->ev_chunk[c], e->cout, (uint32_t)o, retry ? e->d_retry + o : nullptr);
         if (rc != TBE_OK) return rc;
+        if (retry)
+            HIP_TRY(e, hipMemcpyAsync(retry + o, e->d_retry + o, m * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                      e->cout));
         HIP_TRY(e, hipMemcpyAsync(status + o, e->d_granted + o, m, hipMemcpyDeviceToHost, e->cout));
         HIP_TRY(e, hipMemcpyAsync(remaining + o, e->d_remaining + o, m * sizeof(int32_t), hipMemcpyDeviceToHost,
                                   e->cout));
@@ -5393,7 +5552,7 @@ static tbe_status status_chunked(tbe_engine *e, const uint64_t *keys, const int3
 
 static tbe_status status_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits,
                                const int64_t *ts_us, uint64_t n, int64_t id_base, uint8_t *status,
-                               int32_t *remaining, uint64_t *n_evicted) {
+                               int32_t *remaining, uint64_t *n_evicted, int64_t *retry) {
     *n_evicted = 0;
     e->evicted.clear();
     e->ev_pending = false;
@@ -5408,6 +5567,11 @@ static tbe_status status_batch(tbe_engine *e, const uint64_t *keys, const int32_
     HIP_TRY(e, hipSetDevice(e->device));
     tbe_status rc = ensure_host_staging(e, n);
     if (rc != TBE_OK) return rc;
+    if (retry) {
+        if (!e->d_retry) HIP_TRY(e, hipMalloc(&e->d_retry, e->stage_cap * sizeof(int64_t)));
+        rc = materialise_aclient(e, e->stream);
+        if (rc != TBE_OK) return rc;
+    }
     // Evictions in one batch are bounded by the entries queued before it plus n.
     const uint64_t need_ev = e->queued_total + n;
     if (need_ev > e->ev_cap) {
@@ -5421,8 +5585,8 @@ static tbe_status status_batch(tbe_engine *e, const uint64_t *keys, const int32_
     hipStream_t st = e->stream;
     uint32_t flag = 0, nev = 0;
     if (n >= 2 * kHostChunk && host_pinned(keys) && host_pinned(permits) && (!ts_us || host_pinned(ts_us)) &&
-        host_pinned(status) && host_pinned(remaining)) {
-        rc = status_chunked(e, keys, permits, ts_us, n, id_base, status, remaining, &nev);
+        host_pinned(status) && host_pinned(remaining) && (!retry || host_pinned(retry))) {
+        rc = status_chunked(e, keys, permits, ts_us, n, id_base, status, remaining, &nev, retry);
         if (rc != TBE_OK) return rc;
     } else {
         HIP_TRY(e, hipMemsetAsync(e->counters, 0, sizeof(uint32_t), st));
@@ -5431,8 +5595,10 @@ static tbe_status status_batch(tbe_engine *e, const uint64_t *keys, const int32_
         if (ts_us)
             HIP_TRY(e, hipMemcpyAsync(e->d_ts, ts_us, n * sizeof(int64_t), hipMemcpyHostToDevice, st));
         rc = run_batch(e, e->d_keys, e->d_permits, ts_us ? e->d_ts : nullptr, n, e->d_granted,
-                       e->d_remaining, st, id_base);
+                       e->d_remaining, st, id_base, nullptr, nullptr, 0, retry ? e->d_retry : nullptr);
         if (rc != TBE_OK) return rc;
+        if (retry)
+            HIP_TRY(e, hipMemcpyAsync(retry, e->d_retry, n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(e, hipMemcpyAsync(&flag, e->last_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(e, hipMemcpyAsync(&nev, e->counters, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(e, hipMemcpyAsync(status, e->d_granted, n, hipMemcpyDeviceToHost, st));

@@ -416,29 +416,49 @@ class ApproximateEngine(QueueingTokenBucketEngine):
                          queue_order, zero_wait_slots=zero_wait_slots, **kw)
         self.zero_wait_slots = zero_wait_slots
 
-    def acquire_batch(self, keys, permits, wait: bool = True, id_base: int = 0, status=None, available=None):
-        """Returns (status u8, available i32, evicted (cause index, request id))."""
+    def acquire_batch(self, keys, permits, wait: bool = True, id_base: int = 0, status=None, available=None,
+                      retry_after=False):
+        """Returns (status u8, available i32, evicted (cause index, request id)).
+
+        retry_after: True, or an int64 array to fill: the failed leases' RetryAfter in .NET
+        ticks (tbe_approx_acquire_batch_retry; TBE_RETRY_NONE where the status is not
+        FAILED), returned as a fourth element."""
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         permits = np.ascontiguousarray(permits, dtype=np.int32)
         n = keys.shape[0]
         status = np.empty(n, dtype=np.uint8) if status is None else status
         avail = np.empty(n, dtype=np.int32) if available is None else available
         n_ev = ctypes.c_uint64()
-        self._check(self._lib.tbe_approx_acquire_batch(self.handle, keys.ctypes.data, permits.ctypes.data,
-                                                       n, 1 if wait else 0, id_base, status.ctypes.data,
-                                                       avail.ctypes.data, byref(n_ev)))
+        want_retry = retry_after is not False and retry_after is not None
+        if want_retry:
+            ticks = np.empty(n, dtype=np.int64) if retry_after is True else retry_after
+            self._check(self._lib.tbe_approx_acquire_batch_retry(
+                self.handle, keys.ctypes.data, permits.ctypes.data, n, 1 if wait else 0, id_base,
+                status.ctypes.data, avail.ctypes.data, ticks.ctypes.data, byref(n_ev)))
+        else:
+            self._check(self._lib.tbe_approx_acquire_batch(self.handle, keys.ctypes.data, permits.ctypes.data,
+                                                           n, 1 if wait else 0, id_base, status.ctypes.data,
+                                                           avail.ctypes.data, byref(n_ev)))
         m = n_ev.value
         cause = np.empty(m, dtype=np.uint64)
         ids = np.empty(m, dtype=np.int64)
         nw = ctypes.c_uint64()
         if m:
             self._check(self._lib.tbe_evicted(self.handle, cause.ctypes.data, ids.ctypes.data, m, byref(nw)))
+        if want_retry:
+            return status, avail, (cause, ids), ticks
         return status, avail, (cause, ids)
 
     def acquire_batch_device(self, d_keys, d_permits, d_status, d_available, wait: bool = False,
-                             id_base: int = 0, stream: Optional[int] = None) -> None:
-        """Device tensors in and out; enqueued (tbe_approx_acquire_batch_device)."""
+                             id_base: int = 0, stream: Optional[int] = None, d_retry_after=None) -> None:
+        """Device tensors in and out; enqueued (tbe_approx_acquire_batch_device, or
+        tbe_approx_acquire_batch_retry_device with the int64 tensor `d_retry_after`)."""
         n = d_keys.numel()
+        if d_retry_after is not None:
+            self._check(self._lib.tbe_approx_acquire_batch_retry_device(
+                self.handle, d_keys.data_ptr(), d_permits.data_ptr(), n, 1 if wait else 0, id_base,
+                d_status.data_ptr(), d_available.data_ptr(), d_retry_after.data_ptr(), stream))
+            return
         self._check(self._lib.tbe_approx_acquire_batch_device(
             self.handle, d_keys.data_ptr(), d_permits.data_ptr(), n, 1 if wait else 0, id_base,
             d_status.data_ptr(), d_available.data_ptr(), stream))

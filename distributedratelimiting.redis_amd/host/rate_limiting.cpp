@@ -586,17 +586,18 @@ private:
                                           rem_.data()));
             break;
         default:  // kApproxWait / kApproxAttempt
-            Check(tbe_approx_acquire_batch(eng_, keys_.data(), permits_.data(), n, mode == kApproxWait ? 1 : 0,
-                                           id_base, status_.data(), rem_.data(), &n_ev));
+            // failed leases carry RetryAfter (A:390-395): decided with the request, on the
+            // key's state at its turn in the micro-batch (retry_after_ticks, tbe.h)
+            retry_.resize(n);
+            Check(tbe_approx_acquire_batch_retry(eng_, keys_.data(), permits_.data(), n,
+                                                 mode == kApproxWait ? 1 : 0, id_base, status_.data(), rem_.data(),
+                                                 retry_.data(), &n_ev));
             next_id_ += (int64_t)n;
             break;
         }
         if (opt_.OnBatch)
             opt_.OnBatch(BatchTrace{mode, n, keys_.data(), permits_.data(), ts_.data(), status_.data(), rem_.data()});
 
-        // Approximate failed leases carry RetryAfter (A:390-395), from the key's state after
-        // this micro-batch: deficit = max(0, consumed + p + queued permits - TokenLimit).
-        std::unordered_map<uint64_t, ApproxState> approx;
         for (uint64_t i = 0; i < n; ++i) {
             Req &r = batch[i];
             const uint8_t s = status_[i];
@@ -618,12 +619,9 @@ private:
                     wt.reg = r.ct.Register([box, key, id] { box->Post(key, id); });
                 }
             } else if (mode == kApproxWait || mode == kApproxAttempt) {
-                auto it = approx.find(r.key);
-                if (it == approx.end()) it = approx.emplace(r.key, QueryApprox(r.key)).first;
-                const ApproxState &a = it->second;
-                const int64_t consumed = (int32_t)((uint32_t)a.global + (uint32_t)a.local);
-                const int64_t deficit = std::max<int64_t>(0, consumed + r.permits + a.queued_permits - opt_.TokenLimit);
-                r.done.set_value(RateLimitLease(false, TimeSpan::FromSeconds((double)deficit * opt_.FillRatePerSecond())));
+                if (retry_[i] == TBE_RETRY_OVERFLOW)   // where TimeSpan::FromSeconds throws
+                    throw std::overflow_error("TimeSpan overflowed because the duration is too long.");
+                r.done.set_value(RateLimitLease(false, TimeSpan{retry_[i]}));
             } else {
                 r.done.set_value(RateLimitLease(false));
             }
@@ -713,6 +711,7 @@ private:
     std::vector<int64_t> ts_;
     std::vector<uint8_t> status_;
     std::vector<int32_t> rem_;
+    std::vector<int64_t> retry_;
 };
 
 static RedisQueueingTokenBucketRateLimiterOptions widen(const RedisTokenBucketRateLimiterOptions &o) {

@@ -356,6 +356,43 @@ tbe_status tbe_approx_acquire_batch_device(tbe_engine *engine, const uint64_t *d
                                            int64_t id_base, uint8_t *d_status, int32_t *d_available,
                                            void *stream);
 
+/* RetryAfter of the failed leases (A:390-395), decided on the device per request.
+ * retry_after_ticks[i], for request i in arrival order:
+ *   status[i] == TBE_WAIT_FAILED: the .NET ticks (100 ns) of
+ *       TimeSpan.FromSeconds(deficit * FillRatePerSecond),
+ *       deficit = max(0, (int32)(_globalThrottleScore + _localThrottleScore + permits[i]
+ *                                + _queueCount - TokenLimit))       (C# unchecked int32)
+ *     on the key's state at that request's turn in arrival order -- not after the batch: a
+ *     later grant, wait or eviction of the same batch does not change it.  The seconds are
+ *     one f64 multiply, the ticks a second one (* 1e7, no contraction), truncated toward
+ *     zero; a deficit of 0 gives 0 ticks.  Where seconds * 1e7 >= 2^63 the reference's
+ *     FromSeconds throws OverflowException: TBE_RETRY_OVERFLOW.  There is no NaN case:
+ *     tbe_create refuses a non-positive period, so the fill rate is finite and positive.
+ *     Every FAILED path carries it: AcquireCore with permits > 0, AcquireCore with 0 permits
+ *     while throttled, a wait that does not fit the queue, and a zero-permit wait beyond
+ *     zero_wait_slots (this engine's own departure; the same formula with permits 0).
+ *   GRANTED, QUEUED, REJECTED: TBE_RETRY_NONE (REJECTED is an exception in the reference,
+ *     not a lease).
+ * _globalThrottleScore is this client's view as of its last sync.  Everything else --
+ * validation, TBE_EINVAL with nothing applied, ordering, evictions, the chunked path for
+ * page-locked buffers -- is tbe_approx_acquire_batch's; a null retry_after_ticks with
+ * n > 0 is TBE_EINVAL. */
+#define TBE_RETRY_NONE (-1)
+#define TBE_RETRY_OVERFLOW INT64_MAX
+tbe_status tbe_approx_acquire_batch_retry(tbe_engine *engine, const uint64_t *keys, const int32_t *permits,
+                                          uint64_t n, int32_t wait, int64_t id_base, uint8_t *status,
+                                          int32_t *available, int64_t *retry_after_ticks,
+                                          uint64_t *n_evicted);
+
+/* Device-pointer tbe_approx_acquire_batch_retry: as tbe_approx_acquire_batch_device, plus
+ * d_retry_after_ticks (device memory, n int64).  Enqueue only: after a one-client sync the
+ * client view is first written on the engine's stream and the batch's stream waits for it
+ * by an event; the host is never synchronised. */
+tbe_status tbe_approx_acquire_batch_retry_device(tbe_engine *engine, const uint64_t *d_keys,
+                                                 const int32_t *d_permits, uint64_t n, int32_t wait,
+                                                 int64_t id_base, uint8_t *d_status, int32_t *d_available,
+                                                 int64_t *d_retry_after_ticks, void *stream);
+
 /* Refresh step 1 (A:430-435): d_counts[k] = _localThrottleScore of key k, then 0.
  * d_counts is device memory for n_keys int32 (the caller exchanges it between clients,
  * e.g. an RCCL all-gather over xGMI). */
