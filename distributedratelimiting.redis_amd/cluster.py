@@ -35,10 +35,11 @@ device path also runs over a "gloo" group (its collectives then stage through ho
 memory): that is how two ranks sharing one GPU exercise the whole device path in the
 tests (RCCL refuses two ranks on one device).
 
-Directories never free ids (a key keeps its bucket for the directory's lifetime, like a
-Redis key that has not expired); a batch that brings more new keys than ids remain
-raises ``TbeError(TBE_ERANGE)`` before any decision is made, and the directory must be
-recreated.
+A directory holds the keys whose buckets are alive: ``reclaim`` removes the keys whose
+bucket has expired (the Redis ``EXPIRE``, TB:232-235) and their ids are handed out again, so
+a churning key space passes through a directory of the size of its live set.  A batch that
+brings more new keys than there is room for raises ``TbeError(TBE_ERANGE)`` before any
+decision is made; that state is sticky, so an owner reclaims from a timer well before it.
 """
 from __future__ import annotations
 
@@ -195,13 +196,17 @@ def scramble_walk(x, n: int) -> np.ndarray:
 
 
 class HostDirectory:
-    """Host mirror of the device key directory (tbe_dir_*): keys new to it get counters in
-    order of first occurrence, id = scramble_walk(counter, capacity).  Used by the gloo
-    path and the tests."""
+    """Host mirror of the device key directory (tbe_dir_*): a stack of freed ids and a
+    ``fresh`` counter.  Keys new to it, in order of first occurrence, each pop the stack;
+    once it is empty they take id = scramble_walk(fresh++, capacity).  ``reclaim`` removes
+    keys and pushes their ids in ascending order.  Never reclaimed, it hands out
+    scramble_walk(0), (1), ...  Used by the gloo path and the tests."""
 
     def __init__(self, capacity: int):
         self.capacity = int(capacity)
         self.ids = {}
+        self.free = []
+        self.fresh = 0
         self.overflow = False
 
     def check(self) -> None:
@@ -217,15 +222,29 @@ class HostDirectory:
         uniq, first = np.unique(keys, return_index=True)
         new = [(f, k) for k, f in zip(uniq.tolist(), first.tolist()) if k not in self.ids]
         new.sort()
-        base = len(self.ids)
-        room = max(0, self.capacity - base)
+        room = len(self.free) + max(0, self.capacity - self.fresh)
         if len(new) > room:
             self.overflow = True
-        if new[:room]:
-            ctr = np.arange(base, base + len(new[:room]), dtype=np.uint64)
-            for (_, k), i in zip(new[:room], scramble_walk(ctr, self.capacity).tolist()):
+        new = new[:room]
+        n_pop = min(len(new), len(self.free))
+        for _, k in new[:n_pop]:
+            self.ids[k] = self.free.pop()
+        if new[n_pop:]:
+            ctr = np.arange(self.fresh, self.fresh + len(new) - n_pop, dtype=np.uint64)
+            self.fresh += len(new) - n_pop
+            for (_, k), i in zip(new[n_pop:], scramble_walk(ctr, self.capacity).tolist()):
                 self.ids[k] = i
         return self.lookup(keys)
+
+    def reclaim(self, dead_ids, keep_ids=()) -> int:
+        """Remove every held key whose id is in dead_ids and not in keep_ids; their ids go
+        onto the free stack in ascending order.  Returns the number removed."""
+        gone = {int(i) for i in dead_ids} - {int(i) for i in keep_ids}
+        victims = sorted((i, k) for k, i in self.ids.items() if i in gone)
+        for i, k in victims:
+            del self.ids[k]
+            self.free.append(i)
+        return len(victims)
 
     def lookup(self, keys) -> np.ndarray:
         get = self.ids.get
@@ -258,9 +277,10 @@ class DeviceDirectory:
             raise _capi.TbeError(st, f"tbe_dir_create({capacity}) failed")
         self._h = h
         self.capacity = int(capacity)
-        # upper bound of the ids assigned so far (each key of an assign batch adds at most
-        # one): while it stays below capacity no batch can have overflowed, so the exact
-        # count (a device synchronisation) is fetched only once the bound reaches it
+        # upper bound of the keys held (each key of an assign batch adds at most one, a
+        # reclaim only removes): while it stays below capacity no batch can have overflowed,
+        # so the exact count (a device synchronisation) is fetched only once the bound
+        # reaches it
         self._bound = 0
         self.strict = strict
         self._pending = None     # (pinned state copy, event) of the last asynchronous check
@@ -334,12 +354,51 @@ class DeviceDirectory:
         return self._run(self._lib.tbe_dir_keys_of_device, d_ids)
 
     def size(self) -> int:
+        """Keys held (assigned and not reclaimed since); raises TBE_ERANGE after an overflow."""
         import ctypes
         from . import _capi
         n = ctypes.c_uint64()
         st = self._lib.tbe_dir_size(self._h, ctypes.byref(n))
         if st != _capi.TBE_OK:
             raise _capi.TbeError(st, "directory over capacity" if st == _capi.TBE_ERANGE else "tbe_dir_size failed")
+        return n.value
+
+    def reclaim_device(self, d_dead, d_keep_ids=None):
+        """tbe_dir_reclaim_device on the current stream: d_dead is a uint8 device tensor of
+        ``capacity`` flags indexed by id (``TokenBucketEngine.expired_device``), d_keep_ids
+        an int64 device tensor of ids never to remove.  Returns a one-element int64 device
+        tensor that receives the number of keys removed (nothing is synchronised)."""
+        import torch
+        from . import _capi
+        if d_dead.numel() != self.capacity or d_dead.element_size() != 1:
+            raise ValueError("d_dead must hold one byte per id of the directory's capacity")
+        d_dead = d_dead.contiguous()
+        n_keep = 0 if d_keep_ids is None else d_keep_ids.numel()
+        if n_keep:
+            d_keep_ids = d_keep_ids.contiguous()
+        count = torch.zeros(1, dtype=torch.int64, device=d_dead.device)
+        st = self._lib.tbe_dir_reclaim_device(self._h, d_dead.data_ptr(), d_keep_ids.data_ptr() if n_keep else None,
+                                              n_keep, count.data_ptr(), device_stream(d_dead.device))
+        if st != _capi.TBE_OK:
+            raise _capi.TbeError(st, "tbe_dir_reclaim_device failed")
+        return count       # (the bound of the keys held stays valid: a reclaim only removes)
+
+    def reclaim(self, engine, ts_us: int, keep_ids=None) -> int:
+        """Drop every key whose bucket no longer exists in `engine` at ts_us (tbe_dir_reclaim:
+        the Redis EXPIRE of idle buckets, TB:232-235); keep_ids: ids of an assign whose engine
+        batch is not submitted yet.  Synchronous; returns the number of keys removed."""
+        import ctypes
+        from . import _capi
+        keep = np.ascontiguousarray([] if keep_ids is None else keep_ids, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        st = self._lib.tbe_dir_reclaim(self._h, engine.handle, int(ts_us), keep.ctypes.data if keep.size else None,
+                                       keep.size, ctypes.byref(n))
+        if st != _capi.TBE_OK:
+            raise _capi.TbeError(st, "tbe_dir_reclaim failed")
+        held = ctypes.c_uint64()
+        st = self._lib.tbe_dir_size(self._h, ctypes.byref(held))
+        # exact after a reclaim; an overflowed directory keeps check() on its exact path
+        self._bound = held.value if st == _capi.TBE_OK else self.capacity
         return n.value
 
 

@@ -248,49 +248,71 @@ __global__ __launch_bounds__(kDirBlock) void k_dir_count(const uint32_t *__restr
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
-// Exclusive scan of the block counts (in place); base = ids assigned before this batch;
-// the running total advances, clamped at capacity (overflow: sticky error).
-__global__ __launch_bounds__(kScanThreads) void k_dir_scan(uint32_t *__restrict__ bsum, uint32_t nblk,
-                                                           unsigned long long *__restrict__ state,
-                                                           uint64_t capacity) {
-    __shared__ uint32_t wsum[kScanThreads / 64];
+// Exclusive scan of per-block counts in place by one workgroup (each thread a contiguous
+// run, the carry running through it); returns the sum of the counts to every thread.
+__device__ __forceinline__ uint32_t dir_scan_blocks(uint32_t *__restrict__ v, uint32_t nblk, uint32_t *wsum) {
     const uint32_t t = threadIdx.x;
     const uint32_t per = (nblk + kScanThreads - 1) / kScanThreads;
     uint32_t sum = 0;
     for (uint32_t k = 0; k < per; ++k) {
         const uint32_t j = t * per + k;
-        if (j < nblk) sum += bsum[j];
+        if (j < nblk) sum += v[j];
     }
     uint32_t tot;
     uint32_t run = block_excl_scan<kScanThreads>(sum, wsum, &tot);
     for (uint32_t k = 0; k < per; ++k) {
         const uint32_t j = t * per + k;
         if (j < nblk) {
-            const uint32_t c = bsum[j];
-            bsum[j] = run;
+            const uint32_t c = v[j];
+            v[j] = run;
             run += c;
         }
     }
-    if (t == 0) {
-        const unsigned long long before = state[0];   // ids assigned so far
-        state[2] = before;                            // this batch's base
-        unsigned long long after = before + tot;
-        if (after > capacity) {
-            after = capacity;
+    return tot;
+}
+
+// The directory's counters (state[]): [0] keys held = [4] - [5], [1] error bits, [2] the
+// fresh counter before this batch, [3] the value of [6] the id -> key table covers, [4]
+// fresh counters used, [5] ids on the free stack, [6] ids ever handed out (only grows), [7]
+// the stack's height before this batch.  Room for new keys = [5] + capacity - [4].
+//
+// Exclusive scan of the block counts (in place); the batch's new keys take freed ids
+// first, then fresh counters, clamped at the room (overflow: sticky error).  Without a
+// reclaim [5] stays 0 and [0] = [4] advances by the new keys, clamped at capacity.
+__global__ __launch_bounds__(kScanThreads) void k_dir_scan(uint32_t *__restrict__ bsum, uint32_t nblk,
+                                                           unsigned long long *__restrict__ state,
+                                                           uint64_t capacity) {
+    __shared__ uint32_t wsum[kScanThreads / 64];
+    const uint32_t tot = dir_scan_blocks(bsum, nblk, wsum);
+    if (threadIdx.x == 0) {
+        const unsigned long long fresh = state[4], nfree = state[5];
+        const unsigned long long room = nfree + capacity - fresh;
+        unsigned long long take = tot;
+        if (take > room) {
+            take = room;
             state[1] |= 2ull;                         // capacity exceeded
         }
-        state[0] = after;
+        const unsigned long long pop = take < nfree ? take : nfree;   // freed ids go first
+        state[2] = fresh;
+        state[7] = nfree;
+        state[5] = nfree - pop;
+        state[4] = fresh + (take - pop);
+        state[0] = fresh + (take - pop) - (nfree - pop);
+        state[6] += take;
     }
 }
 
-// Assign ids to the new keys: counter = base + rank among the batch's new keys (block
-// prefix + rank in block), id = bijection of the counter; beyond capacity, none.
+// Assign ids to the new keys.  Rank r among the batch's new keys (block prefix + rank in
+// block) takes the free stack's r-th id from the top, and once the stack (nfree ids before
+// the batch) is used up the fresh counter fresh + r - nfree, id = bijection of the counter;
+// beyond capacity, none.
 __global__ __launch_bounds__(kDirBlock) void k_dir_assign(const uint32_t *__restrict__ slot_of, uint64_t n,
                                                           uint32_t *__restrict__ sid,
                                                           const uint32_t *__restrict__ sfirst,
                                                           const uint32_t *__restrict__ bsum,
                                                           const unsigned long long *__restrict__ state,
-                                                          uint64_t capacity, uint64_t imask, uint32_t ish) {
+                                                          uint64_t capacity, uint64_t imask, uint32_t ish,
+                                                          const uint32_t *__restrict__ free_ids) {
     __shared__ uint32_t wsum[kDirBlock / 64];
     constexpr int PER = kDirTile / kDirBlock;
     const uint64_t base = (uint64_t)blockIdx.x * kDirTile;
@@ -304,12 +326,18 @@ __global__ __launch_bounds__(kDirBlock) void k_dir_assign(const uint32_t *__rest
     }
     uint32_t tot;
     uint32_t r = block_excl_scan<kDirBlock>(c, wsum, &tot);   // every thread has read sid before it returns
-    const uint64_t b0 = (uint64_t)state[2] + bsum[blockIdx.x];
+    const uint64_t fresh = state[2], nfree = state[7];
+    const uint64_t r0 = bsum[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         if (!nw[k]) continue;
         const uint64_t i = base + (uint64_t)threadIdx.x * PER + k;
-        const uint64_t counter = b0 + r++;
+        const uint64_t rank = r0 + r++;
+        if (rank < nfree) {
+            sid[slot_of[i]] = free_ids[nfree - 1 - rank];
+            continue;
+        }
+        const uint64_t counter = fresh + (rank - nfree);
         if (counter < capacity) sid[slot_of[i]] = (uint32_t)scramble_walk(counter, capacity, imask, ish);
     }
 }
@@ -360,13 +388,16 @@ __global__ void k_dir_init(uint64_t *__restrict__ skey, uint32_t *__restrict__ s
 }
 
 // Reverse lookup (tbe_dir_keys_of_device): rev[id] = the key holding id, built from the
-// slots whenever ids have been assigned since the last build (state[3] = the id count
-// the table covers).  Ids are never taken back, so a rebuild only adds entries to the
-// table, which starts as all UINT64_MAX.
+// slots whenever ids have been handed out since the last build (state[3] = the value of
+// state[6], ids ever handed out, that the table covers; the keys held would not do, since
+// a reclaim and an assign can bring them back to the same number).  A build only adds
+// entries to the table, which starts as all UINT64_MAX; ids are taken back by a reclaim
+// alone, which clears its victims' entries itself (k_dr_vpush) and sets state[3] to
+// UINT64_MAX, so the next call builds again whether or not an assign came in between.
 __global__ void k_dir_rev_build(const uint64_t *__restrict__ skey, const uint32_t *__restrict__ sid,
                                 uint64_t nslots, const unsigned long long *__restrict__ state, uint64_t capacity,
                                 uint64_t *__restrict__ rev) {
-    if (state[3] == state[0]) return;
+    if (state[3] == state[6]) return;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nslots; j += stride) {
         const uint32_t id = sid[j];
@@ -378,11 +409,182 @@ __global__ void k_dir_rev_build(const uint64_t *__restrict__ skey, const uint32_
 __global__ void k_dir_keys_of(const uint64_t *__restrict__ ids, uint64_t n, const uint64_t *__restrict__ rev,
                               uint64_t capacity, unsigned long long *__restrict__ state,
                               uint64_t *__restrict__ keys) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) state[3] = state[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0) state[3] = state[6];
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const uint64_t id = ids[i];
         keys[i] = id < capacity ? rev[id] : kEmptyKey;
+    }
+}
+
+// ---------------------------------------------------------------- directory reclaim
+// Emptying a victim's slot in place would cut the probe chains that run through it, and a
+// tombstone per victim would fill the table of a churning key space.  A reclaim
+// (tbe_dir_reclaim_device) therefore rebuilds the table from its survivors:
+//   1. vict[id] = 1 for every slot's id that is flagged dead (one pass over the slots: only
+//      they know which ids are assigned), then 0 again for the keep ids;
+//   2. the victims, in ascending id order (block counts, scan, write over the ids), go
+//      onto the free stack and lose their id -> key entry;
+//   3. the surviving slots' (key, id) are compacted in slot order (block counts, scan,
+//      write over the slots) into a record list; a slot that holds a key without an id (an
+//      overflowed batch left it) is no survivor;
+//   4. the slot table is reset and every record claims a slot again by CAS, probing from
+//      its key's home slot as an assign does.
+// Every index is bounded by what it indexes: ids by capacity, slots by nslots, records by
+// the survivors (distinct ids, so at most capacity), the stack by the distinct ids not held.
+__global__ void k_dr_flag(const uint32_t *__restrict__ sid, uint64_t nslots, uint64_t capacity,
+                          const uint8_t *__restrict__ dead, uint8_t *__restrict__ vict) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nslots; s += stride) {
+        const uint32_t id = sid[s];
+        if (id != kNoId && id < capacity && dead[id]) vict[id] = 1;
+    }
+}
+
+__global__ void k_dr_keep(const uint64_t *__restrict__ keep, uint64_t n_keep, uint64_t capacity,
+                          uint8_t *__restrict__ vict) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_keep; j += stride)
+        if (keep[j] < capacity) vict[keep[j]] = 0;
+}
+
+// Victims per block of kDirTile ids (thread-contiguous, as k_dir_count).
+__global__ __launch_bounds__(kDirBlock) void k_dr_vcount(uint64_t capacity, const uint8_t *__restrict__ vict,
+                                                         uint32_t *__restrict__ bv) {
+    __shared__ uint32_t wsum[kDirBlock / 64];
+    constexpr int PER = kDirTile / kDirBlock;
+    const uint64_t base = (uint64_t)blockIdx.x * kDirTile + (uint64_t)threadIdx.x * PER;
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) c += base + k < capacity && vict[base + k];
+    uint32_t tot;
+    (void)block_excl_scan<kDirBlock>(c, wsum, &tot);
+    if (threadIdx.x == 0) bv[blockIdx.x] = tot;
+}
+
+// Exclusive scan of block counts in place; *total = their sum.  With `state` (the scan of
+// the survivors, which runs after the victims were pushed): the counters after the
+// reclaim, rc_n[0] = victims, and the caller's count.
+__global__ __launch_bounds__(kScanThreads) void k_dr_scan(uint32_t *__restrict__ v, uint32_t nblk,
+                                                          uint32_t *__restrict__ total,
+                                                          unsigned long long *__restrict__ state,
+                                                          const uint32_t *__restrict__ rc_n,
+                                                          uint64_t *__restrict__ n_reclaimed) {
+    __shared__ uint32_t wsum[kScanThreads / 64];
+    const uint32_t tot = dir_scan_blocks(v, nblk, wsum);
+    if (threadIdx.x == 0) {
+        *total = tot;
+        if (state) {
+            const unsigned long long nfree = state[5] + rc_n[0];
+            state[5] = nfree;
+            state[0] = state[4] - nfree;
+            state[3] = ~0ull;              // the id -> key table is built again
+            if (n_reclaimed) *n_reclaimed = rc_n[0];
+        }
+    }
+}
+
+// The victims onto the free stack in ascending id order (bv scanned); state[5] is still
+// the stack's height before the reclaim.
+__global__ __launch_bounds__(kDirBlock) void k_dr_vpush(uint64_t capacity, const uint8_t *__restrict__ vict,
+                                                        const uint32_t *__restrict__ bv,
+                                                        const unsigned long long *__restrict__ state,
+                                                        uint32_t *__restrict__ free_ids, uint64_t *__restrict__ rev) {
+    __shared__ uint32_t wsum[kDirBlock / 64];
+    constexpr int PER = kDirTile / kDirBlock;
+    const uint64_t base = (uint64_t)blockIdx.x * kDirTile + (uint64_t)threadIdx.x * PER;
+    bool v[PER];
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        v[k] = base + k < capacity && vict[base + k];
+        c += v[k];
+    }
+    uint32_t tot;
+    uint64_t at = (uint64_t)state[5] + bv[blockIdx.x] + block_excl_scan<kDirBlock>(c, wsum, &tot);
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+        if (v[k] && at < capacity) {
+            free_ids[at++] = (uint32_t)(base + k);
+            if (rev) rev[base + k] = kEmptyKey;
+        }
+}
+
+__device__ __forceinline__ bool dr_survives(const uint32_t *__restrict__ sid, const uint8_t *__restrict__ vict,
+                                            uint64_t s, uint64_t nslots, uint64_t capacity) {
+    if (s >= nslots) return false;
+    const uint32_t id = sid[s];
+    return id != kNoId && id < capacity && !vict[id];
+}
+
+// Surviving keys per block of kDirTile slots.
+__global__ __launch_bounds__(kDirBlock) void k_dr_scount(uint64_t nslots, uint64_t capacity,
+                                                         const uint32_t *__restrict__ sid,
+                                                         const uint8_t *__restrict__ vict,
+                                                         uint32_t *__restrict__ bs) {
+    __shared__ uint32_t wsum[kDirBlock / 64];
+    constexpr int PER = kDirTile / kDirBlock;
+    const uint64_t base = (uint64_t)blockIdx.x * kDirTile + (uint64_t)threadIdx.x * PER;
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) c += dr_survives(sid, vict, base + k, nslots, capacity);
+    uint32_t tot;
+    (void)block_excl_scan<kDirBlock>(c, wsum, &tot);
+    if (threadIdx.x == 0) bs[blockIdx.x] = tot;
+}
+
+// The survivors' (key, id) in slot order: record rank = bs[block] + rank in block.
+__global__ __launch_bounds__(kDirBlock) void k_dr_move(uint64_t nslots, uint64_t capacity,
+                                                       const uint64_t *__restrict__ skey,
+                                                       const uint32_t *__restrict__ sid,
+                                                       const uint8_t *__restrict__ vict,
+                                                       const uint32_t *__restrict__ bs,
+                                                       uint64_t *__restrict__ sv_key, uint32_t *__restrict__ sv_id) {
+    __shared__ uint32_t wsum[kDirBlock / 64];
+    constexpr int PER = kDirTile / kDirBlock;
+    const uint64_t base = (uint64_t)blockIdx.x * kDirTile + (uint64_t)threadIdx.x * PER;
+    bool sv[PER];
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        sv[k] = dr_survives(sid, vict, base + k, nslots, capacity);
+        c += sv[k];
+    }
+    uint32_t tot;
+    uint64_t r = (uint64_t)bs[blockIdx.x] + block_excl_scan<kDirBlock>(c, wsum, &tot);
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+        if (sv[k] && r < capacity) {
+            sv_key[r] = skey[base + k];
+            sv_id[r] = sid[base + k];
+            ++r;
+        }
+}
+
+// Every survivor back into the reset table: the first empty slot from its key's home
+// slot on, claimed by CAS (the keys are distinct, so a lost CAS means "probe on").
+__global__ __launch_bounds__(kDirBlock) void k_dr_place(const uint32_t *__restrict__ rc_n,
+                                                        const uint64_t *__restrict__ sv_key,
+                                                        const uint32_t *__restrict__ sv_id,
+                                                        uint64_t *__restrict__ skey, uint32_t *__restrict__ sid,
+                                                        uint64_t smask, uint64_t capacity,
+                                                        unsigned long long *__restrict__ err) {
+    const uint64_t count = min((uint64_t)rc_n[1], capacity);
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < count; r += stride) {
+        const uint64_t key = sv_key[r];
+        uint64_t h = mix64(key) & smask;
+        bool placed = false;
+        for (uint64_t probe = 0; probe <= smask; ++probe) {
+            if (skey[h] == kEmptyKey &&
+                atomicCAS(reinterpret_cast<unsigned long long *>(&skey[h]), kEmptyKey, key) == kEmptyKey) {
+                sid[h] = sv_id[r];
+                placed = true;
+                break;
+            }
+            h = (h + 1) & smask;
+        }
+        if (!placed) atomicOr(err, 1ull);   // cannot happen: survivors <= capacity <= nslots / 2
     }
 }
 
@@ -402,12 +604,50 @@ struct tbe_directory {
     uint64_t *skey = nullptr;
     uint32_t *sid = nullptr;
     uint32_t *sfirst = nullptr;
-    unsigned long long *state = nullptr;   // [0] ids assigned, [1] error bits, [2] batch base, [3] ids rev covers
+    unsigned long long *state = nullptr;   // kDirState counters, see k_dir_scan
     uint64_t *rev = nullptr;               // id -> key, capacity entries (the first tbe_dir_keys_of_device allocates it)
     uint32_t *slot_of = nullptr;           // per-request slot of the current batch
     uint32_t *bsum = nullptr;
     uint64_t tmp_cap = 0;
+    // reclaim (allocated by the first one, dir_reclaim_scratch)
+    uint32_t *free_ids = nullptr;          // the free stack, capacity ids
+    uint8_t *vict = nullptr;               // [capacity]
+    uint64_t *sv_key = nullptr;            // survivor records, capacity each
+    uint32_t *sv_id = nullptr;
+    uint32_t *rc_bv = nullptr, *rc_bs = nullptr, *rc_n = nullptr;
+    uint8_t *rc_dead = nullptr;            // tbe_dir_reclaim: the engine's flags, its keep list, its count
+    uint64_t *rc_keep = nullptr, *rc_count = nullptr;
+    uint64_t rc_keep_cap = 0;
 };
+
+namespace {
+
+constexpr int kDirState = 8;
+
+tbe_status dir_reclaim_scratch(tbe_directory *d) {
+    if (d->free_ids) return TBE_OK;
+    const uint64_t cap = d->capacity;
+    const uint64_t nbi = (cap + kDirTile - 1) / kDirTile, nbs = (d->nslots + kDirTile - 1) / kDirTile;
+    const bool ok = hipMalloc(&d->vict, cap) == hipSuccess &&
+                    hipMalloc(&d->sv_key, cap * sizeof(uint64_t)) == hipSuccess &&
+                    hipMalloc(&d->sv_id, cap * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&d->rc_bv, nbi * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&d->rc_bs, nbs * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&d->rc_n, 2 * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&d->free_ids, cap * sizeof(uint32_t)) == hipSuccess;   // last: marks the set complete
+    if (!ok) {
+        for (void *p : {(void *)d->vict, (void *)d->sv_key, (void *)d->sv_id, (void *)d->rc_bv, (void *)d->rc_bs,
+                        (void *)d->rc_n, (void *)d->free_ids})
+            if (p) (void)hipFree(p);
+        d->vict = nullptr;
+        d->sv_key = nullptr;
+        d->sv_id = d->rc_bv = d->rc_bs = d->rc_n = d->free_ids = nullptr;
+        return TBE_ENOMEM;
+    }
+    return TBE_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -489,13 +729,13 @@ tbe_status tbe_dir_create(uint64_t capacity, int32_t device, tbe_directory **out
     bool ok = hipMalloc(&d->skey, ns * sizeof(uint64_t)) == hipSuccess &&
               hipMalloc(&d->sid, ns * sizeof(uint32_t)) == hipSuccess &&
               hipMalloc(&d->sfirst, ns * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc(&d->state, 4 * sizeof(unsigned long long)) == hipSuccess;
+              hipMalloc(&d->state, kDirState * sizeof(unsigned long long)) == hipSuccess;
     if (!ok) {
         tbe_dir_destroy(d);
         return TBE_ENOMEM;
     }
     k_dir_init<<<grid_for(ns, 256), 256>>>(d->skey, d->sid, d->sfirst, ns);
-    if (hipMemset(d->state, 0, 4 * sizeof(unsigned long long)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    if (hipMemset(d->state, 0, kDirState * sizeof(unsigned long long)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
         tbe_dir_destroy(d);
         return TBE_EDEVICE;
     }
@@ -508,7 +748,9 @@ void tbe_dir_destroy(tbe_directory *d) {
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
     for (void *p : {(void *)d->skey, (void *)d->sid, (void *)d->sfirst, (void *)d->state, (void *)d->slot_of,
-                    (void *)d->bsum, (void *)d->rev})
+                    (void *)d->bsum, (void *)d->rev, (void *)d->free_ids, (void *)d->vict, (void *)d->sv_key,
+                    (void *)d->sv_id, (void *)d->rc_bv, (void *)d->rc_bs, (void *)d->rc_n, (void *)d->rc_dead,
+                    (void *)d->rc_keep, (void *)d->rc_count})
         if (p) (void)hipFree(p);
     delete d;
 }
@@ -539,7 +781,7 @@ tbe_status tbe_dir_assign_device(tbe_directory *d, const uint64_t *d_keys, uint6
     k_dir_count<<<nblk, kDirBlock, 0, st>>>(d->slot_of, n, d->sid, d->sfirst, d->bsum);
     k_dir_scan<<<1, kScanThreads, 0, st>>>(d->bsum, nblk, d->state, d->capacity);
     k_dir_assign<<<nblk, kDirBlock, 0, st>>>(d->slot_of, n, d->sid, d->sfirst, d->bsum, d->state, d->capacity,
-                                             d->imask, d->ish);
+                                             d->imask, d->ish, d->free_ids);
     k_dir_gather<<<grid_for(n, 256), 256, 0, st>>>(d->slot_of, n, d->sid, d_ids);
     return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
 }
@@ -563,9 +805,9 @@ tbe_status tbe_dir_keys_of_device(tbe_directory *d, const uint64_t *d_ids, uint6
     hipStream_t st = (hipStream_t)stream;
     if (!d->rev) {
         if (hipMalloc(&d->rev, d->capacity * sizeof(uint64_t)) != hipSuccess) return TBE_ENOMEM;
-        // every entry UINT64_MAX, and state[3] = 0: the first build fills in every id held
+        // every entry UINT64_MAX, and state[3] too: the first build fills in every id held
         if (hipMemsetAsync(d->rev, 0xFF, d->capacity * sizeof(uint64_t), st) != hipSuccess ||
-            hipMemsetAsync(d->state + 3, 0, sizeof(unsigned long long), st) != hipSuccess)
+            hipMemsetAsync(d->state + 3, 0xFF, sizeof(unsigned long long), st) != hipSuccess)
             return TBE_EDEVICE;
     }
     k_dir_rev_build<<<grid_for(d->nslots, 256), 256, 0, st>>>(d->skey, d->sid, d->nslots, d->state, d->capacity,
@@ -589,6 +831,67 @@ tbe_status tbe_dir_size(tbe_directory *d, uint64_t *n_ids) {
     if (hipMemcpy(st, d->state, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) return TBE_EDEVICE;
     *n_ids = st[0];
     return st[1] ? TBE_ERANGE : TBE_OK;
+}
+
+tbe_status tbe_dir_reclaim_device(tbe_directory *d, const uint8_t *d_dead, const uint64_t *d_keep_ids,
+                                  uint64_t n_keep, uint64_t *d_n_reclaimed, void *stream) {
+    if (!d || !d_dead || (n_keep && !d_keep_ids)) return TBE_EINVAL;
+    if (hipSetDevice(d->device) != hipSuccess) return TBE_EDEVICE;
+    const tbe_status rc = dir_reclaim_scratch(d);
+    if (rc != TBE_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t cap = d->capacity, ns = d->nslots;
+    const uint32_t nbi = (uint32_t)((cap + kDirTile - 1) / kDirTile), nbs = (uint32_t)((ns + kDirTile - 1) / kDirTile);
+    if (hipMemsetAsync(d->vict, 0, cap, st) != hipSuccess) return TBE_EDEVICE;
+    k_dr_flag<<<grid_for(ns, 256), 256, 0, st>>>(d->sid, ns, cap, d_dead, d->vict);
+    if (n_keep) k_dr_keep<<<grid_for(n_keep, 256), 256, 0, st>>>(d_keep_ids, n_keep, cap, d->vict);
+    k_dr_vcount<<<nbi, kDirBlock, 0, st>>>(cap, d->vict, d->rc_bv);
+    k_dr_scan<<<1, kScanThreads, 0, st>>>(d->rc_bv, nbi, d->rc_n, nullptr, nullptr, nullptr);
+    k_dr_vpush<<<nbi, kDirBlock, 0, st>>>(cap, d->vict, d->rc_bv, d->state, d->free_ids, d->rev);
+    k_dr_scount<<<nbs, kDirBlock, 0, st>>>(ns, cap, d->sid, d->vict, d->rc_bs);
+    k_dr_scan<<<1, kScanThreads, 0, st>>>(d->rc_bs, nbs, d->rc_n + 1, d->state, d->rc_n, d_n_reclaimed);
+    k_dr_move<<<nbs, kDirBlock, 0, st>>>(ns, cap, d->skey, d->sid, d->vict, d->rc_bs, d->sv_key, d->sv_id);
+    k_dir_init<<<grid_for(ns, 256), 256, 0, st>>>(d->skey, d->sid, d->sfirst, ns);
+    k_dr_place<<<grid_for(cap, kDirBlock), kDirBlock, 0, st>>>(d->rc_n, d->sv_key, d->sv_id, d->skey, d->sid, ns - 1,
+                                                              cap, d->state + 1);
+    return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
+}
+
+tbe_status tbe_dir_reclaim(tbe_directory *d, tbe_engine *engine, int64_t ts_us, const uint64_t *keep_ids,
+                           uint64_t n_keep, uint64_t *n_reclaimed) {
+    if (!d || !engine || !n_reclaimed || (n_keep && !keep_ids)) return TBE_EINVAL;
+    *n_reclaimed = 0;
+    // The engine must live on the directory's device: a read of one of its rows makes its
+    // device current (and changes nothing).
+    double v, t;
+    int32_t present;
+    int edev = -1;
+    if (tbe_query(engine, 0, -1, &v, &t, &present) != TBE_OK || hipGetDevice(&edev) != hipSuccess) return TBE_EINVAL;
+    // after every assign and engine batch, whatever its stream
+    if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TBE_EDEVICE;
+    if (edev != d->device) return TBE_EINVAL;
+    if ((!d->rc_dead && hipMalloc(&d->rc_dead, d->capacity) != hipSuccess) ||
+        (!d->rc_count && hipMalloc(&d->rc_count, sizeof(uint64_t)) != hipSuccess))
+        return TBE_ENOMEM;
+    if (n_keep > d->rc_keep_cap) {
+        if (d->rc_keep) (void)hipFree(d->rc_keep);
+        d->rc_keep = nullptr;
+        d->rc_keep_cap = 0;
+        if (hipMalloc(&d->rc_keep, n_keep * sizeof(uint64_t)) != hipSuccess) return TBE_ENOMEM;
+        d->rc_keep_cap = n_keep;
+    }
+    if (n_keep && hipMemcpy(d->rc_keep, keep_ids, n_keep * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        return TBE_EDEVICE;
+    // refuses the approximate kind and an engine with fewer rows than the directory has ids
+    tbe_status rc = tbe_expired_device(engine, ts_us, 0, d->capacity, d->rc_dead, 1, nullptr);
+    if (rc != TBE_OK) return rc;
+    if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TBE_EDEVICE;
+    rc = tbe_dir_reclaim_device(d, d->rc_dead, d->rc_keep, n_keep, d->rc_count, nullptr);
+    if (rc != TBE_OK) return rc;
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(n_reclaimed, d->rc_count, sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return TBE_EDEVICE;
+    return TBE_OK;
 }
 
 }  // extern "C"

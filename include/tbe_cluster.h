@@ -81,11 +81,22 @@ tbe_status tbe_route_gather_device(const uint32_t *d_pos, uint64_t n, const int6
  * first occurrence (batches in call order, arrival order inside a batch), and the id is
  * a fixed bijection of [0, capacity) applied to the counter (so hot keys, which are seen
  * first, do not crowd the first buckets).  Collision-free: the table stores whole keys.
- * Capacity: once a batch brings more new keys than `capacity` ids remain, tbe_dir_size
- * reports TBE_ERANGE from then on and the directory must be recreated.  In such a batch
- * every key that gets an id keeps a unique one in [0, capacity), but which of the new
- * keys get one is unspecified (the hash table, 2x capacity, may fill up first); the
- * others get UINT64_MAX, and an engine batch containing them is rejected as invalid. */
+ * Keys whose bucket no longer exists in the store are removed by a reclaim (below), the
+ * counterpart of Redis dropping a key at its EXPIRE (TB:232-235), by the rule of the string
+ * directory (tbe_strdir.h): the directory holds a stack of freed ids and a `fresh` counter;
+ * a reclaim pushes the ids it removes in ascending order; a batch's new keys, in order of
+ * first occurrence, each pop the stack, and once it is empty take bijection(fresh++).  Ids
+ * stay a pure function of the call sequence (assigns and reclaims), and a directory that
+ * is never reclaimed assigns the ids described above.
+ * Capacity: `capacity` bounds the keys the directory holds at one time, not the keys it has
+ * ever seen.  A caller whose key space churns (client addresses, sessions, API tokens)
+ * calls tbe_dir_reclaim from a timer, well before the limit is reached, and the ids of the
+ * buckets that have expired are used again.  Room for new keys is (freed ids) + capacity -
+ * fresh.  A batch that brings more new keys than that leaves the directory in the sticky
+ * TBE_ERANGE state (tbe_dir_size reports it from then on): every key that gets an id keeps
+ * a unique one in [0, capacity), but which of the new keys get one is unspecified (the
+ * hash table, 2x capacity, may fill up first); the others get UINT64_MAX, and an engine
+ * batch containing them is rejected as invalid.  That state is not undone by a reclaim. */
 typedef struct tbe_directory tbe_directory;
 
 tbe_status tbe_dir_create(uint64_t capacity, int32_t device, tbe_directory **out);
@@ -97,20 +108,61 @@ tbe_status tbe_dir_assign_device(tbe_directory *dir, const uint64_t *d_keys, uin
 tbe_status tbe_dir_lookup_device(tbe_directory *dir, const uint64_t *d_keys, uint64_t n, uint64_t *d_ids,
                                  void *stream);
 /* Reverse lookup: d_keys[i] = the key that holds id d_ids[i]; UINT64_MAX when no key holds
- * it or the id is >= capacity.  The id -> key table (capacity u64, allocated by the first
- * call) is built from the slots by one pass, again whenever ids have been assigned since;
- * like a lookup it must not run concurrently with an assign on another stream. */
+ * it (never assigned, or reclaimed and not assigned again) or the id is >= capacity.  The
+ * id -> key table (capacity u64, allocated by the first call) is built from the slots by
+ * one pass, again whenever ids have been assigned or reclaimed since; like a lookup it
+ * must not run concurrently with an assign or a reclaim on another stream. */
 tbe_status tbe_dir_keys_of_device(tbe_directory *dir, const uint64_t *d_ids, uint64_t n, uint64_t *d_keys,
                                   void *stream);
-/* Ids assigned so far (synchronises the directory's device). */
+/* Keys held: ids assigned and not reclaimed since (synchronises the directory's device). */
 tbe_status tbe_dir_size(tbe_directory *dir, uint64_t *n_ids);
-/* The same without synchronising: enqueues on `stream` a copy of {ids assigned, error
+/* The same without synchronising: enqueues on `stream` a copy of {keys held, error
  * bits} (two u64; error bits != 0 once a batch exceeded the capacity, the condition
  * tbe_dir_size reports as TBE_ERANGE) into out2, pinned host or device memory.  Lets a
  * caller notice an overflow a batch later without a device synchronisation per batch;
  * the batch that overflowed is caught by the engine anyway (its UINT64_MAX ids make the
  * engine batch invalid). */
 tbe_status tbe_dir_state_async(tbe_directory *dir, uint64_t *out2, void *stream);
+
+/* Remove the keys flagged dead and reuse their ids.  d_dead: `capacity` bytes of device
+ * memory indexed by id (tbe_expired_device over [0, capacity) writes them); d_keep_ids:
+ * n_keep ids (device memory) that are never removed; a keep id >= capacity is ignored and
+ * an id given twice is harmless.  For every id that is assigned, flagged and not kept: its
+ * key leaves the directory (tbe_dir_lookup_device: UINT64_MAX; tbe_dir_keys_of_device:
+ * UINT64_MAX for the id until it is assigned again, then the new key) and the id goes onto
+ * the free stack (ascending id order within one reclaim).  Every other key keeps its id.
+ * *d_n_reclaimed (device memory, may be NULL) gets the number of keys removed.  Enqueued
+ * on `stream`, nothing is synchronised.
+ *
+ * The table stays a plain linear-probe table without tombstones: the reclaim rebuilds it
+ * from the survivors, so probe chains that ran through a removed key still resolve.  After
+ * an overflow (TBE_ERANGE) a reclaim still works within bounds and frees ids, but the error
+ * state stays; slots that hold a key without an id are dropped.
+ *
+ * Contract: the reclaim rebuilds the slot table, so
+ *   - no assign, lookup or keys_of may be in flight on another stream (work enqueued on
+ *     `stream` before and after the call is ordered as usual);
+ *   - d_dead must describe the engine after every batch that used this directory's ids;
+ *     an id handed out by an assign whose engine batch has not been submitted yet has
+ *     an absent row and would be flagged: such ids go in d_keep_ids.
+ * Cost: two passes over the ids and three over the slots plus the re-insertion of the live
+ * keys: a maintenance call made every few seconds to minutes.  The first reclaim allocates
+ * its working memory, kept until tbe_dir_destroy: 17 bytes per id of capacity (1 of flags,
+ * 4 of free stack, 12 of survivor records) and 4 bytes per 1024 ids and per 1024 slots. */
+tbe_status tbe_dir_reclaim_device(tbe_directory *dir, const uint8_t *d_dead,
+                                  const uint64_t *d_keep_ids, uint64_t n_keep,
+                                  uint64_t *d_n_reclaimed, void *stream);
+
+/* The periodic call of a host: tbe_expired_device(engine, ts_us, 0, capacity, clear = 1)
+ * followed by tbe_dir_reclaim_device, ordered after everything enqueued before it on any
+ * stream; synchronous.  The engine must be of the token-bucket or queueing kind, on the
+ * directory's device, with n_keys >= capacity; anything else (the approximate kind, which
+ * tbe_expired_device refuses, included) is TBE_EINVAL and nothing changes.  The lapsed rows
+ * are written back absent, so a reused id starts from a full bucket whatever timestamp
+ * comes next.  keep_ids is a host array (may be NULL when n_keep is 0); *n_reclaimed =
+ * keys removed.  One more byte per id of capacity is held for the flags. */
+tbe_status tbe_dir_reclaim(tbe_directory *dir, tbe_engine *engine, int64_t ts_us,
+                           const uint64_t *keep_ids, uint64_t n_keep, uint64_t *n_reclaimed);
 
 #ifdef __cplusplus
 }
