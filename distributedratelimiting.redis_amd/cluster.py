@@ -195,12 +195,12 @@ def scramble_walk(x, n: int) -> np.ndarray:
     return x
 
 
-class HostDirectory:
-    """Host mirror of the device key directory (tbe_dir_*): a stack of freed ids and a
-    ``fresh`` counter.  Keys new to it, in order of first occurrence, each pop the stack;
-    once it is empty they take id = scramble_walk(fresh++, capacity).  ``reclaim`` removes
-    keys and pushes their ids in ascending order.  Never reclaimed, it hands out
-    scramble_walk(0), (1), ...  Used by the gloo path and the tests."""
+class HostIdPool:
+    """Host model of the directories' id pool (csrc/tbe_idpool.hpp, DESIGN.md §7 "The id
+    rule"): a stack of freed ids and a ``fresh`` counter.  Keys new to it, in order of first
+    occurrence, each pop the stack; once it is empty they take id = scramble_walk(fresh++,
+    capacity).  ``reclaim`` removes keys and pushes their ids in ascending order.  Never
+    reclaimed, it hands out scramble_walk(0), (1), ..."""
 
     def __init__(self, capacity: int):
         self.capacity = int(capacity)
@@ -208,6 +208,39 @@ class HostDirectory:
         self.free = []
         self.fresh = 0
         self.overflow = False
+
+    def _take(self, new) -> None:
+        """Ids for `new`: keys not in ``ids``, distinct, in order of first occurrence."""
+        room = len(self.free) + max(0, self.capacity - self.fresh)
+        if len(new) > room:
+            self.overflow = True
+        new = new[:room]
+        n_pop = min(len(new), len(self.free))
+        for k in new[:n_pop]:
+            self.ids[k] = self.free.pop()
+        if new[n_pop:]:
+            ctr = np.arange(self.fresh, self.fresh + len(new) - n_pop, dtype=np.uint64)
+            self.fresh += len(new) - n_pop
+            for k, i in zip(new[n_pop:], scramble_walk(ctr, self.capacity).tolist()):
+                self.ids[k] = i
+
+    def reclaim(self, dead_ids, keep_ids=()) -> int:
+        """Remove every held key whose id is in dead_ids and not in keep_ids; their ids go
+        onto the free stack in ascending order.  Returns the number removed."""
+        gone = {int(i) for i in dead_ids} - {int(i) for i in keep_ids}
+        victims = sorted((i, k) for k, i in self.ids.items() if i in gone)
+        for i, k in victims:
+            del self.ids[k]
+            self.free.append(i)
+        return len(victims)
+
+    def size(self) -> int:
+        return len(self.ids)
+
+
+class HostDirectory(HostIdPool):
+    """Host mirror of the device key directory (tbe_dir_*): a HostIdPool over u64 keys.
+    Used by the gloo path and the tests."""
 
     def check(self) -> None:
         """Raise TbeError(TBE_ERANGE) once a batch has brought more new keys than ids remained."""
@@ -220,41 +253,55 @@ class HostDirectory:
         if keys.size == 0:
             return np.zeros(0, dtype=np.uint64)
         uniq, first = np.unique(keys, return_index=True)
-        new = [(f, k) for k, f in zip(uniq.tolist(), first.tolist()) if k not in self.ids]
-        new.sort()
-        room = len(self.free) + max(0, self.capacity - self.fresh)
-        if len(new) > room:
-            self.overflow = True
-        new = new[:room]
-        n_pop = min(len(new), len(self.free))
-        for _, k in new[:n_pop]:
-            self.ids[k] = self.free.pop()
-        if new[n_pop:]:
-            ctr = np.arange(self.fresh, self.fresh + len(new) - n_pop, dtype=np.uint64)
-            self.fresh += len(new) - n_pop
-            for (_, k), i in zip(new[n_pop:], scramble_walk(ctr, self.capacity).tolist()):
-                self.ids[k] = i
+        self._take([k for _, k in sorted((f, k) for k, f in zip(uniq.tolist(), first.tolist()) if k not in self.ids)])
         return self.lookup(keys)
-
-    def reclaim(self, dead_ids, keep_ids=()) -> int:
-        """Remove every held key whose id is in dead_ids and not in keep_ids; their ids go
-        onto the free stack in ascending order.  Returns the number removed."""
-        gone = {int(i) for i in dead_ids} - {int(i) for i in keep_ids}
-        victims = sorted((i, k) for k, i in self.ids.items() if i in gone)
-        for i, k in victims:
-            del self.ids[k]
-            self.free.append(i)
-        return len(victims)
 
     def lookup(self, keys) -> np.ndarray:
         get = self.ids.get
         return np.array([get(k, MASK64) for k in np.asarray(keys, dtype=np.uint64).tolist()], dtype=np.uint64)
 
-    def size(self) -> int:
-        return len(self.ids)
+
+class _DeviceReclaim:
+    """reclaim_device / reclaim of a device directory: ``_RECLAIM_DEVICE`` and ``_RECLAIM``
+    name its two C entry points (tbe_dir_* or tbe_sdir_*), ``_h`` is its handle."""
+
+    def reclaim_device(self, d_dead, d_keep_ids=None):
+        """The device-form reclaim on the current stream: d_dead is a uint8 device tensor of
+        ``capacity`` flags indexed by id (``TokenBucketEngine.expired_device``), d_keep_ids
+        an int64 device tensor of ids never to remove.  Returns a one-element int64 device
+        tensor that receives the number of keys removed (nothing is synchronised)."""
+        import torch
+        from . import _capi
+        if d_dead.numel() != self.capacity or d_dead.element_size() != 1:
+            raise ValueError("d_dead must hold one byte per id of the directory's capacity")
+        d_dead = d_dead.contiguous()
+        n_keep = 0 if d_keep_ids is None else d_keep_ids.numel()
+        if n_keep:
+            d_keep_ids = d_keep_ids.contiguous()
+        count = torch.zeros(1, dtype=torch.int64, device=d_dead.device)
+        st = getattr(self._lib, self._RECLAIM_DEVICE)(self._h, d_dead.data_ptr(),
+                                                      d_keep_ids.data_ptr() if n_keep else None, n_keep,
+                                                      count.data_ptr(), device_stream(d_dead.device))
+        if st != _capi.TBE_OK:
+            raise _capi.TbeError(st, f"{self._RECLAIM_DEVICE} failed")
+        return count
+
+    def reclaim(self, engine, ts_us: int, keep_ids=None) -> int:
+        """Drop every key whose bucket no longer exists in `engine` at ts_us (the Redis EXPIRE
+        of idle buckets, TB:232-235); keep_ids: ids of an assign whose engine batch is not
+        submitted yet.  Synchronous; returns the number of keys removed."""
+        import ctypes
+        from . import _capi
+        keep = np.ascontiguousarray([] if keep_ids is None else keep_ids, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        st = getattr(self._lib, self._RECLAIM)(self._h, engine.handle, int(ts_us),
+                                               keep.ctypes.data if keep.size else None, keep.size, ctypes.byref(n))
+        if st != _capi.TBE_OK:
+            raise _capi.TbeError(st, f"{self._RECLAIM} failed")
+        return n.value
 
 
-class DeviceDirectory:
+class DeviceDirectory(_DeviceReclaim):
     """The owner's key directory in HBM (include/tbe_cluster.h tbe_dir_*).
 
     ``strict`` (default): ``check()`` raises TBE_ERANGE for the very batch that overflowed,
@@ -363,43 +410,18 @@ class DeviceDirectory:
             raise _capi.TbeError(st, "directory over capacity" if st == _capi.TBE_ERANGE else "tbe_dir_size failed")
         return n.value
 
-    def reclaim_device(self, d_dead, d_keep_ids=None):
-        """tbe_dir_reclaim_device on the current stream: d_dead is a uint8 device tensor of
-        ``capacity`` flags indexed by id (``TokenBucketEngine.expired_device``), d_keep_ids
-        an int64 device tensor of ids never to remove.  Returns a one-element int64 device
-        tensor that receives the number of keys removed (nothing is synchronised)."""
-        import torch
-        from . import _capi
-        if d_dead.numel() != self.capacity or d_dead.element_size() != 1:
-            raise ValueError("d_dead must hold one byte per id of the directory's capacity")
-        d_dead = d_dead.contiguous()
-        n_keep = 0 if d_keep_ids is None else d_keep_ids.numel()
-        if n_keep:
-            d_keep_ids = d_keep_ids.contiguous()
-        count = torch.zeros(1, dtype=torch.int64, device=d_dead.device)
-        st = self._lib.tbe_dir_reclaim_device(self._h, d_dead.data_ptr(), d_keep_ids.data_ptr() if n_keep else None,
-                                              n_keep, count.data_ptr(), device_stream(d_dead.device))
-        if st != _capi.TBE_OK:
-            raise _capi.TbeError(st, "tbe_dir_reclaim_device failed")
-        return count       # (the bound of the keys held stays valid: a reclaim only removes)
+    _RECLAIM_DEVICE, _RECLAIM = "tbe_dir_reclaim_device", "tbe_dir_reclaim"
 
     def reclaim(self, engine, ts_us: int, keep_ids=None) -> int:
-        """Drop every key whose bucket no longer exists in `engine` at ts_us (tbe_dir_reclaim:
-        the Redis EXPIRE of idle buckets, TB:232-235); keep_ids: ids of an assign whose engine
-        batch is not submitted yet.  Synchronous; returns the number of keys removed."""
         import ctypes
         from . import _capi
-        keep = np.ascontiguousarray([] if keep_ids is None else keep_ids, dtype=np.uint64)
-        n = ctypes.c_uint64()
-        st = self._lib.tbe_dir_reclaim(self._h, engine.handle, int(ts_us), keep.ctypes.data if keep.size else None,
-                                       keep.size, ctypes.byref(n))
-        if st != _capi.TBE_OK:
-            raise _capi.TbeError(st, "tbe_dir_reclaim failed")
+        n = super().reclaim(engine, ts_us, keep_ids)
         held = ctypes.c_uint64()
         st = self._lib.tbe_dir_size(self._h, ctypes.byref(held))
-        # exact after a reclaim; an overflowed directory keeps check() on its exact path
+        # exact after a reclaim (reclaim_device leaves the bound valid: it only removes); an
+        # overflowed directory keeps check() on its exact path
         self._bound = held.value if st == _capi.TBE_OK else self.capacity
-        return n.value
+        return n
 
 
 def keys_per_rank(n_keys: int, world: int, slack: float = 0.01, owner_map=None) -> int:

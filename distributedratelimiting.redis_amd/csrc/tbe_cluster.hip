@@ -17,6 +17,7 @@
 #include "../../include/tbe_cluster.h"
 #include "tbe_device.hpp"
 #include "tbe_hash.hpp"
+#include "tbe_idpool.hpp"
 
 using namespace tbe;
 
@@ -74,7 +75,6 @@ __global__ __launch_bounds__(kRtBlock) void k_route_count(const uint64_t *__rest
 
 // One workgroup: per owner, the exclusive scan of its tile counts (in place) and its
 // total; then owner bases (exclusive scan over owners).
-constexpr int kScanThreads = 1024;
 __global__ __launch_bounds__(kScanThreads) void k_route_scan(uint32_t *__restrict__ tile_counts, uint32_t ntiles,
                                                              uint32_t G, uint64_t *__restrict__ owner_counts,
                                                              uint32_t *__restrict__ owner_base) {
@@ -181,9 +181,14 @@ __global__ void k_route_gather(const uint32_t *__restrict__ pos, uint64_t n, con
 
 // ---------------------------------------------------------------- directory
 constexpr uint64_t kEmptyKey = ~0ull;
-constexpr uint32_t kNoId = 0xFFFFFFFFu;
 constexpr int kDirBlock = 256;
 constexpr int kDirTile = 1024;   // requests per flag block (4 per thread)
+// The directory's own state[] words, beside the id pool's (tbe_idpool.hpp): keys held =
+// fresh - nfree; the value of kDirEver that the id -> key table covers; ids ever handed out
+// (only grows).
+enum : int { kDirHeld = 0, kDirRevCovers = 3, kDirEver = 4 };
+// state[kStErr]: a UINT64_MAX key or a full table; more new keys than room
+constexpr unsigned long long kErrTable = 1, kErrRange = 2;
 
 // Find or claim the slot of every key (linear probing on the whole key); a slot claimed
 // in this batch records the arrival index of its first request (atomicMin).
@@ -196,39 +201,14 @@ __global__ __launch_bounds__(kDirBlock) void k_dir_claim(const uint64_t *__restr
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const uint64_t key = keys[i];
-        uint32_t found = kNoId;
-        if (key != kEmptyKey) {
-            uint64_t h = mix64(key) & smask;
-            for (uint64_t probe = 0; probe <= smask; ++probe) {
-                const uint64_t cur = skey[h];
-                if (cur == key) {
-                    found = (uint32_t)h;
-                    break;
-                }
-                if (cur == kEmptyKey) {
-                    const unsigned long long prev =
-                        atomicCAS(reinterpret_cast<unsigned long long *>(&skey[h]), kEmptyKey, key);
-                    if (prev == kEmptyKey || prev == key) {
-                        found = (uint32_t)h;
-                        break;
-                    }
-                }
-                h = (h + 1) & smask;
-            }
-        }
+        const uint32_t found = key != kEmptyKey ? probe_find_or_claim(skey, smask, key, kEmptyKey) : kNoId;
         slot_of[i] = found;
         if (found == kNoId) {
-            atomicOr(err, 1ull);            // UINT64_MAX key, or a full table
+            atomicOr(err, kErrTable);
         } else if (sid[found] == kNoId) {
             atomicMin(&sfirst[found], (uint32_t)i);
         }
     }
-}
-
-__device__ __forceinline__ bool dir_is_new(const uint32_t *slot_of, const uint32_t *sid, const uint32_t *sfirst,
-                                           uint64_t i) {
-    const uint32_t sl = slot_of[i];
-    return sl != kNoId && sid[sl] == kNoId && sfirst[sl] == (uint32_t)i;
 }
 
 // New keys per block of kDirTile requests.
@@ -241,71 +221,29 @@ __global__ __launch_bounds__(kDirBlock) void k_dir_count(const uint32_t *__restr
     uint32_t c = 0;
     for (int k = 0; k < kDirTile / kDirBlock; ++k) {
         const uint64_t i = base + (uint64_t)threadIdx.x * (kDirTile / kDirBlock) + k;
-        if (i < n && dir_is_new(slot_of, sid, sfirst, i)) ++c;
+        if (i < n && is_new(slot_of, sid, sfirst, i)) ++c;
     }
     uint32_t tot;
     (void)block_excl_scan<kDirBlock>(c, wsum, &tot);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
-// Exclusive scan of per-block counts in place by one workgroup (each thread a contiguous
-// run, the carry running through it); returns the sum of the counts to every thread.
-__device__ __forceinline__ uint32_t dir_scan_blocks(uint32_t *__restrict__ v, uint32_t nblk, uint32_t *wsum) {
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (nblk + kScanThreads - 1) / kScanThreads;
-    uint32_t sum = 0;
-    for (uint32_t k = 0; k < per; ++k) {
-        const uint32_t j = t * per + k;
-        if (j < nblk) sum += v[j];
-    }
-    uint32_t tot;
-    uint32_t run = block_excl_scan<kScanThreads>(sum, wsum, &tot);
-    for (uint32_t k = 0; k < per; ++k) {
-        const uint32_t j = t * per + k;
-        if (j < nblk) {
-            const uint32_t c = v[j];
-            v[j] = run;
-            run += c;
-        }
-    }
-    return tot;
-}
-
-// The directory's counters (state[]): [0] keys held = [4] - [5], [1] error bits, [2] the
-// fresh counter before this batch, [3] the value of [6] the id -> key table covers, [4]
-// fresh counters used, [5] ids on the free stack, [6] ids ever handed out (only grows), [7]
-// the stack's height before this batch.  Room for new keys = [5] + capacity - [4].
-//
-// Exclusive scan of the block counts (in place); the batch's new keys take freed ids
-// first, then fresh counters, clamped at the room (overflow: sticky error).  Without a
-// reclaim [5] stays 0 and [0] = [4] advances by the new keys, clamped at capacity.
+// Exclusive scan of the block counts (in place), and the pool takes the batch's new keys.
+// Without a reclaim the stack stays empty and keys held = fresh advances by the new keys,
+// clamped at capacity.
 __global__ __launch_bounds__(kScanThreads) void k_dir_scan(uint32_t *__restrict__ bsum, uint32_t nblk,
                                                            unsigned long long *__restrict__ state,
                                                            uint64_t capacity) {
     __shared__ uint32_t wsum[kScanThreads / 64];
-    const uint32_t tot = dir_scan_blocks(bsum, nblk, wsum);
+    const uint32_t tot = scan_blocks(bsum, nblk, wsum);
     if (threadIdx.x == 0) {
-        const unsigned long long fresh = state[4], nfree = state[5];
-        const unsigned long long room = nfree + capacity - fresh;
-        unsigned long long take = tot;
-        if (take > room) {
-            take = room;
-            state[1] |= 2ull;                         // capacity exceeded
-        }
-        const unsigned long long pop = take < nfree ? take : nfree;   // freed ids go first
-        state[2] = fresh;
-        state[7] = nfree;
-        state[5] = nfree - pop;
-        state[4] = fresh + (take - pop);
-        state[0] = fresh + (take - pop) - (nfree - pop);
-        state[6] += take;
+        state[kDirEver] += pool_take(state, tot, capacity, kErrRange);
+        state[kDirHeld] = state[kStFresh] - state[kStNfree];
     }
 }
 
-// Assign ids to the new keys.  Rank r among the batch's new keys (block prefix + rank in
-// block) takes the free stack's r-th id from the top, and once the stack (nfree ids before
-// the batch) is used up the fresh counter fresh + r - nfree, id = bijection of the counter;
-// beyond capacity, none.
+// Assign ids to the new keys: rank among the batch's new keys = block prefix + rank in
+// block, id by pool_id.
 __global__ __launch_bounds__(kDirBlock) void k_dir_assign(const uint32_t *__restrict__ slot_of, uint64_t n,
                                                           uint32_t *__restrict__ sid,
                                                           const uint32_t *__restrict__ sfirst,
@@ -321,34 +259,19 @@ __global__ __launch_bounds__(kDirBlock) void k_dir_assign(const uint32_t *__rest
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         const uint64_t i = base + (uint64_t)threadIdx.x * PER + k;
-        nw[k] = i < n && dir_is_new(slot_of, sid, sfirst, i);
+        nw[k] = i < n && is_new(slot_of, sid, sfirst, i);
         c += nw[k];
     }
     uint32_t tot;
     uint32_t r = block_excl_scan<kDirBlock>(c, wsum, &tot);   // every thread has read sid before it returns
-    const uint64_t fresh = state[2], nfree = state[7];
+    const uint64_t fresh = state[kStFresh0], nfree = state[kStNfree0];
     const uint64_t r0 = bsum[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         if (!nw[k]) continue;
         const uint64_t i = base + (uint64_t)threadIdx.x * PER + k;
-        const uint64_t rank = r0 + r++;
-        if (rank < nfree) {
-            sid[slot_of[i]] = free_ids[nfree - 1 - rank];
-            continue;
-        }
-        const uint64_t counter = fresh + (rank - nfree);
-        if (counter < capacity) sid[slot_of[i]] = (uint32_t)scramble_walk(counter, capacity, imask, ish);
-    }
-}
-
-__global__ void k_dir_gather(const uint32_t *__restrict__ slot_of, uint64_t n, const uint32_t *__restrict__ sid,
-                             uint64_t *__restrict__ ids) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint32_t sl = slot_of[i];
-        const uint32_t id = sl == kNoId ? kNoId : sid[sl];
-        ids[i] = id == kNoId ? ~0ull : (uint64_t)id;
+        const uint32_t id = pool_id(r0 + r++, fresh, nfree, capacity, imask, ish, free_ids);
+        if (id != kNoId) sid[slot_of[i]] = id;
     }
 }
 
@@ -377,27 +300,17 @@ __global__ __launch_bounds__(kDirBlock) void k_dir_lookup(const uint64_t *__rest
     }
 }
 
-__global__ void k_dir_init(uint64_t *__restrict__ skey, uint32_t *__restrict__ sid, uint32_t *__restrict__ sfirst,
-                           uint64_t nslots) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nslots; j += stride) {
-        skey[j] = kEmptyKey;
-        sid[j] = kNoId;
-        sfirst[j] = kNoId;
-    }
-}
-
 // Reverse lookup (tbe_dir_keys_of_device): rev[id] = the key holding id, built from the
-// slots whenever ids have been handed out since the last build (state[3] = the value of
-// state[6], ids ever handed out, that the table covers; the keys held would not do, since
+// slots whenever ids have been handed out since the last build (state[kDirRevCovers] = the
+// value of state[kDirEver], ids ever handed out, that the table covers; the keys held would not do, since
 // a reclaim and an assign can bring them back to the same number).  A build only adds
 // entries to the table, which starts as all UINT64_MAX; ids are taken back by a reclaim
-// alone, which clears its victims' entries itself (k_dr_vpush) and sets state[3] to
-// UINT64_MAX, so the next call builds again whether or not an assign came in between.
+// alone, which clears its victims' entries itself (RevForget) and sets state[kDirRevCovers]
+// to UINT64_MAX, so the next call builds again whether or not an assign came in between.
 __global__ void k_dir_rev_build(const uint64_t *__restrict__ skey, const uint32_t *__restrict__ sid,
                                 uint64_t nslots, const unsigned long long *__restrict__ state, uint64_t capacity,
                                 uint64_t *__restrict__ rev) {
-    if (state[3] == state[6]) return;
+    if (state[kDirRevCovers] == state[kDirEver]) return;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nslots; j += stride) {
         const uint32_t id = sid[j];
@@ -409,7 +322,7 @@ __global__ void k_dir_rev_build(const uint64_t *__restrict__ skey, const uint32_
 __global__ void k_dir_keys_of(const uint64_t *__restrict__ ids, uint64_t n, const uint64_t *__restrict__ rev,
                               uint64_t capacity, unsigned long long *__restrict__ state,
                               uint64_t *__restrict__ keys) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) state[3] = state[6];
+    if (blockIdx.x == 0 && threadIdx.x == 0) state[kDirRevCovers] = state[kDirEver];
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const uint64_t id = ids[i];
@@ -441,74 +354,31 @@ __global__ void k_dr_flag(const uint32_t *__restrict__ sid, uint64_t nslots, uin
     }
 }
 
-__global__ void k_dr_keep(const uint64_t *__restrict__ keep, uint64_t n_keep, uint64_t capacity,
-                          uint8_t *__restrict__ vict) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_keep; j += stride)
-        if (keep[j] < capacity) vict[keep[j]] = 0;
-}
-
-// Victims per block of kDirTile ids (thread-contiguous, as k_dir_count).
-__global__ __launch_bounds__(kDirBlock) void k_dr_vcount(uint64_t capacity, const uint8_t *__restrict__ vict,
-                                                         uint32_t *__restrict__ bv) {
-    __shared__ uint32_t wsum[kDirBlock / 64];
-    constexpr int PER = kDirTile / kDirBlock;
-    const uint64_t base = (uint64_t)blockIdx.x * kDirTile + (uint64_t)threadIdx.x * PER;
-    uint32_t c = 0;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) c += base + k < capacity && vict[base + k];
-    uint32_t tot;
-    (void)block_excl_scan<kDirBlock>(c, wsum, &tot);
-    if (threadIdx.x == 0) bv[blockIdx.x] = tot;
-}
-
-// Exclusive scan of block counts in place; *total = their sum.  With `state` (the scan of
-// the survivors, which runs after the victims were pushed): the counters after the
-// reclaim, rc_n[0] = victims, and the caller's count.
+// Exclusive scan of the survivors' block counts in place (rc_n[1] = their sum), which runs
+// after the victims (rc_n[0] of them) were pushed: the counters after the reclaim, and
+// the caller's count.
 __global__ __launch_bounds__(kScanThreads) void k_dr_scan(uint32_t *__restrict__ v, uint32_t nblk,
-                                                          uint32_t *__restrict__ total,
                                                           unsigned long long *__restrict__ state,
-                                                          const uint32_t *__restrict__ rc_n,
+                                                          uint32_t *__restrict__ rc_n,
                                                           uint64_t *__restrict__ n_reclaimed) {
     __shared__ uint32_t wsum[kScanThreads / 64];
-    const uint32_t tot = dir_scan_blocks(v, nblk, wsum);
+    const uint32_t tot = scan_blocks(v, nblk, wsum);
     if (threadIdx.x == 0) {
-        *total = tot;
-        if (state) {
-            const unsigned long long nfree = state[5] + rc_n[0];
-            state[5] = nfree;
-            state[0] = state[4] - nfree;
-            state[3] = ~0ull;              // the id -> key table is built again
-            if (n_reclaimed) *n_reclaimed = rc_n[0];
-        }
+        rc_n[1] = tot;
+        pool_reclaimed(state, rc_n[0]);
+        state[kDirHeld] = state[kStFresh] - state[kStNfree];
+        state[kDirRevCovers] = ~0ull;      // the id -> key table is built again
+        if (n_reclaimed) *n_reclaimed = rc_n[0];
     }
 }
 
-// The victims onto the free stack in ascending id order (bv scanned); state[5] is still
-// the stack's height before the reclaim.
-__global__ __launch_bounds__(kDirBlock) void k_dr_vpush(uint64_t capacity, const uint8_t *__restrict__ vict,
-                                                        const uint32_t *__restrict__ bv,
-                                                        const unsigned long long *__restrict__ state,
-                                                        uint32_t *__restrict__ free_ids, uint64_t *__restrict__ rev) {
-    __shared__ uint32_t wsum[kDirBlock / 64];
-    constexpr int PER = kDirTile / kDirBlock;
-    const uint64_t base = (uint64_t)blockIdx.x * kDirTile + (uint64_t)threadIdx.x * PER;
-    bool v[PER];
-    uint32_t c = 0;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        v[k] = base + k < capacity && vict[base + k];
-        c += v[k];
+// A victim loses its id -> key entry (once the table exists).
+struct RevForget {
+    uint64_t *rev;
+    __device__ void operator()(uint64_t id) const {
+        if (rev) rev[id] = kEmptyKey;
     }
-    uint32_t tot;
-    uint64_t at = (uint64_t)state[5] + bv[blockIdx.x] + block_excl_scan<kDirBlock>(c, wsum, &tot);
-#pragma unroll
-    for (int k = 0; k < PER; ++k)
-        if (v[k] && at < capacity) {
-            free_ids[at++] = (uint32_t)(base + k);
-            if (rev) rev[base + k] = kEmptyKey;
-        }
-}
+};
 
 __device__ __forceinline__ bool dr_survives(const uint32_t *__restrict__ sid, const uint8_t *__restrict__ vict,
                                             uint64_t s, uint64_t nslots, uint64_t capacity) {
@@ -572,25 +442,10 @@ __global__ __launch_bounds__(kDirBlock) void k_dr_place(const uint32_t *__restri
     const uint64_t count = min((uint64_t)rc_n[1], capacity);
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < count; r += stride) {
-        const uint64_t key = sv_key[r];
-        uint64_t h = mix64(key) & smask;
-        bool placed = false;
-        for (uint64_t probe = 0; probe <= smask; ++probe) {
-            if (skey[h] == kEmptyKey &&
-                atomicCAS(reinterpret_cast<unsigned long long *>(&skey[h]), kEmptyKey, key) == kEmptyKey) {
-                sid[h] = sv_id[r];
-                placed = true;
-                break;
-            }
-            h = (h + 1) & smask;
-        }
-        if (!placed) atomicOr(err, 1ull);   // cannot happen: survivors <= capacity <= nslots / 2
+        const uint32_t h = probe_insert(skey, smask, sv_key[r], kEmptyKey);
+        if (h == kNoId) atomicOr(err, kErrTable);   // cannot happen: survivors <= capacity <= nslots / 2
+        else sid[h] = sv_id[r];
     }
-}
-
-unsigned grid_for(uint64_t n, unsigned block, unsigned cap = 8192) {
-    const uint64_t g = (n + block - 1) / block;
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
 }
 
 }  // namespace
@@ -604,47 +459,33 @@ struct tbe_directory {
     uint64_t *skey = nullptr;
     uint32_t *sid = nullptr;
     uint32_t *sfirst = nullptr;
-    unsigned long long *state = nullptr;   // kDirState counters, see k_dir_scan
+    unsigned long long *state = nullptr;   // kStateWords counters (tbe_idpool.hpp, kDir*)
     uint64_t *rev = nullptr;               // id -> key, capacity entries (the first tbe_dir_keys_of_device allocates it)
     uint32_t *slot_of = nullptr;           // per-request slot of the current batch
     uint32_t *bsum = nullptr;
     uint64_t tmp_cap = 0;
     // reclaim (allocated by the first one, dir_reclaim_scratch)
-    uint32_t *free_ids = nullptr;          // the free stack, capacity ids
-    uint8_t *vict = nullptr;               // [capacity]
+    PoolScratch pool;
     uint64_t *sv_key = nullptr;            // survivor records, capacity each
     uint32_t *sv_id = nullptr;
-    uint32_t *rc_bv = nullptr, *rc_bs = nullptr, *rc_n = nullptr;
-    uint8_t *rc_dead = nullptr;            // tbe_dir_reclaim: the engine's flags, its keep list, its count
-    uint64_t *rc_keep = nullptr, *rc_count = nullptr;
-    uint64_t rc_keep_cap = 0;
+    uint32_t *rc_bs = nullptr;
 };
 
 namespace {
 
-constexpr int kDirState = 8;
-
 tbe_status dir_reclaim_scratch(tbe_directory *d) {
-    if (d->free_ids) return TBE_OK;
-    const uint64_t cap = d->capacity;
-    const uint64_t nbi = (cap + kDirTile - 1) / kDirTile, nbs = (d->nslots + kDirTile - 1) / kDirTile;
-    const bool ok = hipMalloc(&d->vict, cap) == hipSuccess &&
-                    hipMalloc(&d->sv_key, cap * sizeof(uint64_t)) == hipSuccess &&
-                    hipMalloc(&d->sv_id, cap * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&d->rc_bv, nbi * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&d->rc_bs, nbs * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&d->rc_n, 2 * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&d->free_ids, cap * sizeof(uint32_t)) == hipSuccess;   // last: marks the set complete
-    if (!ok) {
-        for (void *p : {(void *)d->vict, (void *)d->sv_key, (void *)d->sv_id, (void *)d->rc_bv, (void *)d->rc_bs,
-                        (void *)d->rc_n, (void *)d->free_ids})
-            if (p) (void)hipFree(p);
-        d->vict = nullptr;
-        d->sv_key = nullptr;
-        d->sv_id = d->rc_bv = d->rc_bs = d->rc_n = d->free_ids = nullptr;
-        return TBE_ENOMEM;
-    }
-    return TBE_OK;
+    if (d->pool.free_ids) return TBE_OK;
+    const uint64_t cap = d->capacity, nbs = (d->nslots + kDirTile - 1) / kDirTile;
+    if (hipMalloc(&d->sv_key, cap * sizeof(uint64_t)) == hipSuccess &&
+        hipMalloc(&d->sv_id, cap * sizeof(uint32_t)) == hipSuccess &&
+        hipMalloc(&d->rc_bs, nbs * sizeof(uint32_t)) == hipSuccess && pool_scratch_alloc(d->pool, cap))
+        return TBE_OK;
+    for (void *p : {(void *)d->sv_key, (void *)d->sv_id, (void *)d->rc_bs})
+        if (p) (void)hipFree(p);
+    d->sv_key = nullptr;
+    d->sv_id = d->rc_bs = nullptr;
+    pool_scratch_free(d->pool);
+    return TBE_ENOMEM;
 }
 
 }  // namespace
@@ -729,13 +570,13 @@ tbe_status tbe_dir_create(uint64_t capacity, int32_t device, tbe_directory **out
     bool ok = hipMalloc(&d->skey, ns * sizeof(uint64_t)) == hipSuccess &&
               hipMalloc(&d->sid, ns * sizeof(uint32_t)) == hipSuccess &&
               hipMalloc(&d->sfirst, ns * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc(&d->state, kDirState * sizeof(unsigned long long)) == hipSuccess;
+              hipMalloc(&d->state, kStateWords * sizeof(unsigned long long)) == hipSuccess;
     if (!ok) {
         tbe_dir_destroy(d);
         return TBE_ENOMEM;
     }
-    k_dir_init<<<grid_for(ns, 256), 256>>>(d->skey, d->sid, d->sfirst, ns);
-    if (hipMemset(d->state, 0, kDirState * sizeof(unsigned long long)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    k_table_init<<<grid_for(ns, 256), 256>>>(d->skey, d->sid, d->sfirst, ns, kEmptyKey);
+    if (hipMemset(d->state, 0, kStateWords * sizeof(unsigned long long)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
         tbe_dir_destroy(d);
         return TBE_EDEVICE;
     }
@@ -748,10 +589,9 @@ void tbe_dir_destroy(tbe_directory *d) {
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
     for (void *p : {(void *)d->skey, (void *)d->sid, (void *)d->sfirst, (void *)d->state, (void *)d->slot_of,
-                    (void *)d->bsum, (void *)d->rev, (void *)d->free_ids, (void *)d->vict, (void *)d->sv_key,
-                    (void *)d->sv_id, (void *)d->rc_bv, (void *)d->rc_bs, (void *)d->rc_n, (void *)d->rc_dead,
-                    (void *)d->rc_keep, (void *)d->rc_count})
+                    (void *)d->bsum, (void *)d->rev, (void *)d->sv_key, (void *)d->sv_id, (void *)d->rc_bs})
         if (p) (void)hipFree(p);
+    pool_scratch_free(d->pool);
     delete d;
 }
 
@@ -777,12 +617,12 @@ tbe_status tbe_dir_assign_device(tbe_directory *d, const uint64_t *d_keys, uint6
     }
     const uint32_t nblk = (uint32_t)((n + kDirTile - 1) / kDirTile);
     k_dir_claim<<<grid_for(n, kDirBlock), kDirBlock, 0, st>>>(d_keys, n, d->skey, d->sid, d->sfirst, d->nslots - 1,
-                                                             d->slot_of, d->state + 1);
+                                                             d->slot_of, d->state + kStErr);
     k_dir_count<<<nblk, kDirBlock, 0, st>>>(d->slot_of, n, d->sid, d->sfirst, d->bsum);
     k_dir_scan<<<1, kScanThreads, 0, st>>>(d->bsum, nblk, d->state, d->capacity);
     k_dir_assign<<<nblk, kDirBlock, 0, st>>>(d->slot_of, n, d->sid, d->sfirst, d->bsum, d->state, d->capacity,
-                                             d->imask, d->ish, d->free_ids);
-    k_dir_gather<<<grid_for(n, 256), 256, 0, st>>>(d->slot_of, n, d->sid, d_ids);
+                                             d->imask, d->ish, d->pool.free_ids);
+    k_gather<<<grid_for(n, 256), 256, 0, st>>>(d->slot_of, n, d->sid, d_ids);
     return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
 }
 
@@ -805,9 +645,9 @@ tbe_status tbe_dir_keys_of_device(tbe_directory *d, const uint64_t *d_ids, uint6
     hipStream_t st = (hipStream_t)stream;
     if (!d->rev) {
         if (hipMalloc(&d->rev, d->capacity * sizeof(uint64_t)) != hipSuccess) return TBE_ENOMEM;
-        // every entry UINT64_MAX, and state[3] too: the first build fills in every id held
+        // every entry UINT64_MAX, and what the table covers too: the first build fills in every id held
         if (hipMemsetAsync(d->rev, 0xFF, d->capacity * sizeof(uint64_t), st) != hipSuccess ||
-            hipMemsetAsync(d->state + 3, 0xFF, sizeof(unsigned long long), st) != hipSuccess)
+            hipMemsetAsync(d->state + kDirRevCovers, 0xFF, sizeof(unsigned long long), st) != hipSuccess)
             return TBE_EDEVICE;
     }
     k_dir_rev_build<<<grid_for(d->nslots, 256), 256, 0, st>>>(d->skey, d->sid, d->nslots, d->state, d->capacity,
@@ -829,8 +669,8 @@ tbe_status tbe_dir_size(tbe_directory *d, uint64_t *n_ids) {
     if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TBE_EDEVICE;
     unsigned long long st[2] = {0, 0};
     if (hipMemcpy(st, d->state, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) return TBE_EDEVICE;
-    *n_ids = st[0];
-    return st[1] ? TBE_ERANGE : TBE_OK;
+    *n_ids = st[kDirHeld];
+    return st[kStErr] ? TBE_ERANGE : TBE_OK;
 }
 
 tbe_status tbe_dir_reclaim_device(tbe_directory *d, const uint8_t *d_dead, const uint64_t *d_keep_ids,
@@ -841,57 +681,30 @@ tbe_status tbe_dir_reclaim_device(tbe_directory *d, const uint8_t *d_dead, const
     if (rc != TBE_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const uint64_t cap = d->capacity, ns = d->nslots;
-    const uint32_t nbi = (uint32_t)((cap + kDirTile - 1) / kDirTile), nbs = (uint32_t)((ns + kDirTile - 1) / kDirTile);
-    if (hipMemsetAsync(d->vict, 0, cap, st) != hipSuccess) return TBE_EDEVICE;
-    k_dr_flag<<<grid_for(ns, 256), 256, 0, st>>>(d->sid, ns, cap, d_dead, d->vict);
-    if (n_keep) k_dr_keep<<<grid_for(n_keep, 256), 256, 0, st>>>(d_keep_ids, n_keep, cap, d->vict);
-    k_dr_vcount<<<nbi, kDirBlock, 0, st>>>(cap, d->vict, d->rc_bv);
-    k_dr_scan<<<1, kScanThreads, 0, st>>>(d->rc_bv, nbi, d->rc_n, nullptr, nullptr, nullptr);
-    k_dr_vpush<<<nbi, kDirBlock, 0, st>>>(cap, d->vict, d->rc_bv, d->state, d->free_ids, d->rev);
-    k_dr_scount<<<nbs, kDirBlock, 0, st>>>(ns, cap, d->sid, d->vict, d->rc_bs);
-    k_dr_scan<<<1, kScanThreads, 0, st>>>(d->rc_bs, nbs, d->rc_n + 1, d->state, d->rc_n, d_n_reclaimed);
-    k_dr_move<<<nbs, kDirBlock, 0, st>>>(ns, cap, d->skey, d->sid, d->vict, d->rc_bs, d->sv_key, d->sv_id);
-    k_dir_init<<<grid_for(ns, 256), 256, 0, st>>>(d->skey, d->sid, d->sfirst, ns);
-    k_dr_place<<<grid_for(cap, kDirBlock), kDirBlock, 0, st>>>(d->rc_n, d->sv_key, d->sv_id, d->skey, d->sid, ns - 1,
-                                                              cap, d->state + 1);
+    const uint32_t nbi = (uint32_t)((cap + kPoolTile - 1) / kPoolTile), nbs = (uint32_t)((ns + kDirTile - 1) / kDirTile);
+    const PoolScratch &p = d->pool;
+    if (hipMemsetAsync(p.vict, 0, cap, st) != hipSuccess) return TBE_EDEVICE;
+    k_dr_flag<<<grid_for(ns, 256), 256, 0, st>>>(d->sid, ns, cap, d_dead, p.vict);
+    if (n_keep) k_pool_keep<<<grid_for(n_keep, 256), 256, 0, st>>>(d_keep_ids, n_keep, cap, p.vict);
+    k_pool_vcount<<<nbi, kPoolBlock, 0, st>>>(cap, p.vict, p.rc_bv);
+    k_scan_blocks<<<1, kScanThreads, 0, st>>>(p.rc_bv, nbi, p.rc_n);
+    k_pool_vpush<<<nbi, kPoolBlock, 0, st>>>(cap, p.vict, p.rc_bv, d->state, p.free_ids, RevForget{d->rev});
+    k_dr_scount<<<nbs, kDirBlock, 0, st>>>(ns, cap, d->sid, p.vict, d->rc_bs);
+    k_dr_scan<<<1, kScanThreads, 0, st>>>(d->rc_bs, nbs, d->state, p.rc_n, d_n_reclaimed);
+    k_dr_move<<<nbs, kDirBlock, 0, st>>>(ns, cap, d->skey, d->sid, p.vict, d->rc_bs, d->sv_key, d->sv_id);
+    k_table_init<<<grid_for(ns, 256), 256, 0, st>>>(d->skey, d->sid, d->sfirst, ns, kEmptyKey);
+    k_dr_place<<<grid_for(cap, kDirBlock), kDirBlock, 0, st>>>(p.rc_n, d->sv_key, d->sv_id, d->skey, d->sid, ns - 1, cap,
+                                                              d->state + kStErr);
     return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
 }
 
 tbe_status tbe_dir_reclaim(tbe_directory *d, tbe_engine *engine, int64_t ts_us, const uint64_t *keep_ids,
                            uint64_t n_keep, uint64_t *n_reclaimed) {
-    if (!d || !engine || !n_reclaimed || (n_keep && !keep_ids)) return TBE_EINVAL;
-    *n_reclaimed = 0;
-    // The engine must live on the directory's device: a read of one of its rows makes its
-    // device current (and changes nothing).
-    double v, t;
-    int32_t present;
-    int edev = -1;
-    if (tbe_query(engine, 0, -1, &v, &t, &present) != TBE_OK || hipGetDevice(&edev) != hipSuccess) return TBE_EINVAL;
-    // after every assign and engine batch, whatever its stream
-    if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TBE_EDEVICE;
-    if (edev != d->device) return TBE_EINVAL;
-    if ((!d->rc_dead && hipMalloc(&d->rc_dead, d->capacity) != hipSuccess) ||
-        (!d->rc_count && hipMalloc(&d->rc_count, sizeof(uint64_t)) != hipSuccess))
-        return TBE_ENOMEM;
-    if (n_keep > d->rc_keep_cap) {
-        if (d->rc_keep) (void)hipFree(d->rc_keep);
-        d->rc_keep = nullptr;
-        d->rc_keep_cap = 0;
-        if (hipMalloc(&d->rc_keep, n_keep * sizeof(uint64_t)) != hipSuccess) return TBE_ENOMEM;
-        d->rc_keep_cap = n_keep;
-    }
-    if (n_keep && hipMemcpy(d->rc_keep, keep_ids, n_keep * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
-        return TBE_EDEVICE;
-    // refuses the approximate kind and an engine with fewer rows than the directory has ids
-    tbe_status rc = tbe_expired_device(engine, ts_us, 0, d->capacity, d->rc_dead, 1, nullptr);
-    if (rc != TBE_OK) return rc;
-    if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TBE_EDEVICE;
-    rc = tbe_dir_reclaim_device(d, d->rc_dead, d->rc_keep, n_keep, d->rc_count, nullptr);
-    if (rc != TBE_OK) return rc;
-    if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(n_reclaimed, d->rc_count, sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return TBE_EDEVICE;
-    return TBE_OK;
+    if (!d) return TBE_EINVAL;
+    return pool_reclaim_sync(d->pool, d->device, d->capacity, engine, ts_us, keep_ids, n_keep, n_reclaimed,
+                             [d](const uint8_t *dead, const uint64_t *keep, uint64_t nk, uint64_t *count) {
+                                 return tbe_dir_reclaim_device(d, dead, keep, nk, count, nullptr);
+                             });
 }
 
 }  // extern "C"

@@ -9,7 +9,7 @@
 //   sloc[s]   u64  bit 63 | (arena offset << 17) | length of the key's text, once assigned
 //   iloc[id]  u64  the same per id (tbe_sdir_key_of)
 //   arena     key text (resourceID bytes), each key at an 8-byte aligned offset
-//   free_ids  u32  stack of ids a reclaim took back (state[6] of them), popped before fresh counters
+//   free_ids  u32  stack of ids a reclaim took back, popped before fresh counters (tbe_idpool.hpp)
 //
 // A string's tag in probe round k (0..3) is (k << 62) | (H_k(string) & hmask), H_k a
 // 64-bit hash seeded from the prefix and k.  Tags are unique in the table: a batch's
@@ -29,18 +29,17 @@
 #include "../../include/tbe_strdir.h"
 #include "tbe_device.hpp"
 #include "tbe_hash.hpp"
+#include "tbe_idpool.hpp"
 
 using namespace tbe;
 
 namespace {
 
 constexpr uint64_t kEmptyTag = ~0ull;
-constexpr uint32_t kNoId = 0xFFFFFFFFu;
 constexpr uint32_t kMaxLen = 1u << 16;
 constexpr int kRounds = 4;
 constexpr int kSdBlock = 256;
 constexpr int kSdTile = 1024;            // requests per count/assign block (4 per thread)
-constexpr int kSdScan = 1024;
 constexpr unsigned kListGrid = 1024;     // workgroups of a probe round over the collided list
 constexpr uint64_t kLocValid = 1ull << 63;
 constexpr double kWarmShare = 0.5;       // warm path while the last batch's new keys stay below this share
@@ -48,7 +47,11 @@ constexpr double kWarmShare = 0.5;       // warm path while the last batch's new
 __device__ __host__ __forceinline__ uint32_t loc_len(uint64_t loc) { return (uint32_t)(loc & (2 * kMaxLen - 1)); }
 __device__ __host__ __forceinline__ uint64_t loc_off(uint64_t loc) { return (loc >> 17) & ((1ull << 46) - 1); }
 
-// error bits (state[1])
+// The directory's own state[] words, beside the id pool's (tbe_idpool.hpp): new keys ever
+// assigned (only grows: the warm-path choice reads its deltas), arena bytes used, this
+// batch's arena base.
+enum : int { kSdEver = 0, kSdArena = 3, kSdArenaBase = 4 };
+// error bits (state[kStErr])
 constexpr unsigned long long kErrBatch = 1, kErrRange = 2, kErrRounds = 4, kErrArena = 8, kErrFull = 16;
 
 struct SdParams {
@@ -146,24 +149,7 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_claim(SdBatch B, uint64_t n, co
             continue;
         }
         const uint64_t tag = sd_tag(round, sd_hash(B.bytes, B.safe, off, len, P.seed[round]), P.hmask);
-        uint32_t found = kNoId;
-        uint64_t h = mix64(tag) & smask;
-        for (uint64_t probe = 0; probe <= smask; ++probe) {
-            const uint64_t cur = stag[h];
-            if (cur == tag) {
-                found = (uint32_t)h;
-                break;
-            }
-            if (cur == kEmptyTag) {
-                const unsigned long long prev =
-                    atomicCAS(reinterpret_cast<unsigned long long *>(&stag[h]), kEmptyTag, tag);
-                if (prev == kEmptyTag || prev == tag) {
-                    found = (uint32_t)h;
-                    break;
-                }
-            }
-            h = (h + 1) & smask;
-        }
+        const uint32_t found = probe_find_or_claim(stag, smask, tag, kEmptyTag);
         slot_of[i] = found;
         if (found == kNoId) atomicOr(err, kErrFull);
         else if (sid[found] == kNoId) atomicMin(&sfirst[found], (uint32_t)i);
@@ -227,12 +213,6 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_verify(SdBatch B, uint64_t n, c
     }
 }
 
-__device__ __forceinline__ bool sd_is_new(const uint32_t *slot_of, const uint32_t *sid, const uint32_t *sfirst,
-                                          uint64_t i) {
-    const uint32_t sl = slot_of[i];
-    return sl != kNoId && sid[sl] == kNoId && sfirst[sl] == (uint32_t)i;
-}
-
 __device__ __forceinline__ uint32_t sd_room(const uint64_t *offs, uint64_t i) {
     return (uint32_t)((offs[i + 1] - offs[i] + 7) & ~7ull);
 }
@@ -261,7 +241,7 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_count(const uint64_t *__restric
     for (int k = 0; k < kSdTile / kSdBlock; ++k) {
         uint64_t i;
         if (sd_at(list, count, base + (uint64_t)threadIdx.x * (kSdTile / kSdBlock) + k, i) &&
-            sd_is_new(slot_of, sid, sfirst, i)) {
+            is_new(slot_of, sid, sfirst, i)) {
             ++c;
             nb += sd_room(offs, i);
         }
@@ -277,30 +257,22 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_count(const uint64_t *__restric
 }
 
 // Exclusive scans of per-block counts (in place) and bytes (into u64 bbase) by one block of
-// kSdScan threads.  Returns the sum of the counts; thread kSdScan - 1 gets the sum of the
-// bytes in *bytes.
+// kScanThreads threads.  Returns the sum of the counts; thread kScanThreads - 1 gets the sum
+// of the bytes in *bytes.
 __device__ __forceinline__ uint32_t sd_scan_blocks(uint32_t *__restrict__ bsum, const uint32_t *__restrict__ bbytes,
                                                    uint64_t *__restrict__ bbase, uint32_t nblk, uint32_t *wsum,
                                                    unsigned long long *part, unsigned long long *bytes) {
     const uint32_t t = threadIdx.x;
-    const uint32_t per = (nblk + kSdScan - 1) / kSdScan;
-    uint32_t sum = 0;
     unsigned long long bs = 0;
-    for (uint32_t k = 0; k < per; ++k) {
-        const uint32_t j = t * per + k;
-        if (j < nblk) {
-            sum += bsum[j];
-            bs += bbytes[j];
-        }
-    }
+    const uint32_t sum = blocks_sum(bsum, nblk, [&](uint32_t j) { bs += bbytes[j]; });
     uint32_t tot;
-    uint32_t run = block_excl_scan<kSdScan>(sum, wsum, &tot);
+    const uint32_t run = block_excl_scan<kScanThreads>(sum, wsum, &tot);
     // bytes: u64 scan through LDS (one thread per 1024 partials; nblk is small)
     part[t] = bs;
     __syncthreads();
     if (t == 0) {
         unsigned long long acc = 0;
-        for (uint32_t k = 0; k < kSdScan; ++k) {
+        for (uint32_t k = 0; k < kScanThreads; ++k) {
             const unsigned long long v = part[k];
             part[k] = acc;
             acc += v;
@@ -308,62 +280,39 @@ __device__ __forceinline__ uint32_t sd_scan_blocks(uint32_t *__restrict__ bsum, 
     }
     __syncthreads();
     unsigned long long brun = part[t];
-    for (uint32_t k = 0; k < per; ++k) {
-        const uint32_t j = t * per + k;
-        if (j < nblk) {
-            const uint32_t c = bsum[j];
-            bsum[j] = run;
-            run += c;
-            bbase[j] = brun;
-            brun += bbytes[j];
-        }
-    }
+    blocks_write(bsum, nblk, run, [&](uint32_t j) {
+        bbase[j] = brun;
+        brun += bbytes[j];
+    });
     *bytes = brun;
     return tot;
 }
 
-// The batch's block scans and the directory's counters.  state[0] new keys ever assigned
-// (only grows: the warm-path choice reads its deltas), [1] error bits, [2] the fresh
-// counter before this batch, [3] arena bytes used, [4] this batch's arena base, [5] fresh
-// counters used, [6] ids on the free stack, [7] the stack's height before this batch.
-// Keys held = [5] - [6]; room for new keys = [6] + capacity - [5].
-__global__ __launch_bounds__(kSdScan) void k_sd_scan(uint32_t *__restrict__ bsum, const uint32_t *__restrict__ bbytes,
-                                                     uint64_t *__restrict__ bbase, uint32_t nblk,
-                                                     unsigned long long *__restrict__ state, uint64_t capacity,
-                                                     uint64_t arena_bytes) {
-    __shared__ uint32_t wsum[kSdScan / 64];
-    __shared__ unsigned long long part[kSdScan];
+// The batch's block scans; the pool takes the batch's new keys, and the arena their text
+// (beyond it: sticky error).
+__global__ __launch_bounds__(kScanThreads) void k_sd_scan(uint32_t *__restrict__ bsum, const uint32_t *__restrict__ bbytes,
+                                                          uint64_t *__restrict__ bbase, uint32_t nblk,
+                                                          unsigned long long *__restrict__ state, uint64_t capacity,
+                                                          uint64_t arena_bytes) {
+    __shared__ uint32_t wsum[kScanThreads / 64];
+    __shared__ unsigned long long part[kScanThreads];
     unsigned long long brun;
     const uint32_t tot = sd_scan_blocks(bsum, bbytes, bbase, nblk, wsum, part, &brun);
-    if (threadIdx.x == kSdScan - 1) {
-        const unsigned long long fresh = state[5], nfree = state[6];
-        const unsigned long long room = nfree + capacity - fresh;
-        unsigned long long take = tot;
-        if (take > room) {
-            take = room;
-            state[1] |= kErrRange;
-        }
-        const unsigned long long pop = take < nfree ? take : nfree;   // freed ids go first
-        state[2] = fresh;
-        state[7] = nfree;
-        state[6] = nfree - pop;
-        state[5] = fresh + (take - pop);
-        state[0] += take;
-        const unsigned long long abefore = state[3];
-        state[4] = abefore;
+    if (threadIdx.x == kScanThreads - 1) {
+        state[kSdEver] += pool_take(state, tot, capacity, kErrRange);
+        const unsigned long long abefore = state[kSdArena];
+        state[kSdArenaBase] = abefore;
         unsigned long long aafter = abefore + brun;
         if (aafter > arena_bytes) {
             aafter = arena_bytes;
-            state[1] |= kErrArena | kErrRange;
+            state[kStErr] |= kErrArena | kErrRange;
         }
-        state[3] = aafter;
+        state[kSdArena] = aafter;
     }
 }
 
-// Assign ids and store the new keys' text; beyond capacity or arena, none.  Rank r among
-// the batch's new keys takes the free stack's r-th id from the top, and once the stack
-// (nfree ids before the batch) is used up the fresh counter fresh + r - nfree (id = its
-// bijection).
+// Assign ids (pool_id of the rank among the batch's new keys) and store the new keys'
+// text; beyond capacity or arena, none.
 __global__ __launch_bounds__(kSdBlock) void k_sd_assign(SdBatch B, uint64_t n, const uint32_t *__restrict__ slot_of,
                                                         uint32_t *__restrict__ sid, const uint32_t *__restrict__ sfirst,
                                                         uint64_t *__restrict__ sloc, uint64_t *__restrict__ iloc,
@@ -384,7 +333,7 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_assign(SdBatch B, uint64_t n, c
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         nw[k] = sd_at(list, count, base + (uint64_t)threadIdx.x * PER + k, iv[k]) &&
-                sd_is_new(slot_of, sid, sfirst, iv[k]);
+                is_new(slot_of, sid, sfirst, iv[k]);
         c += nw[k];
         nb += nw[k] ? sd_room(B.offs, iv[k]) : 0u;
     }
@@ -392,41 +341,25 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_assign(SdBatch B, uint64_t n, c
     uint32_t r = block_excl_scan<kSdBlock>(c, wsum, &tc);   // every thread has read sid before it returns
     __syncthreads();
     uint32_t rb = block_excl_scan<kSdBlock>(nb, wsum, &tb);
-    const uint64_t fresh = state[2], nfree = state[7];
+    const uint64_t fresh = state[kStFresh0], nfree = state[kStNfree0];
     const uint64_t r0 = bsum[blockIdx.x];
-    const uint64_t a0 = (uint64_t)state[4] + bbase[blockIdx.x];
+    const uint64_t a0 = (uint64_t)state[kSdArenaBase] + bbase[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         if (!nw[k]) continue;
         const uint64_t i = iv[k];
-        const uint64_t rank = r0 + r++;
-        const bool reuse = rank < nfree;
-        const uint64_t counter = reuse ? 0 : fresh + (rank - nfree);
+        const uint32_t id = pool_id(r0 + r++, fresh, nfree, capacity, imask, ish, free_ids);
         const uint64_t off = B.offs[i];
         const uint32_t len = (uint32_t)(B.offs[i + 1] - off);
         const uint64_t aoff = a0 + rb;
         rb += (len + 7) & ~7u;
-        if (counter >= capacity || aoff + ((len + 7) & ~7u) > arena_bytes) continue;
+        if (id == kNoId || aoff + ((len + 7) & ~7u) > arena_bytes) continue;
         for (uint32_t w = 0; 8u * w < len; ++w)
             *reinterpret_cast<uint64_t *>(arena + aoff + 8ull * w) = sd_word(B.bytes, B.safe, off, len, w);
-        const uint32_t id = reuse ? free_ids[nfree - 1 - rank] : (uint32_t)scramble_walk(counter, capacity, imask, ish);
         const uint64_t loc = kLocValid | (aoff << 17) | len;
         sloc[slot_of[i]] = loc;
         iloc[id] = loc;
         sid[slot_of[i]] = id;
-    }
-}
-
-__global__ void k_sd_gather(const uint32_t *__restrict__ slot_of, uint64_t n, const uint32_t *__restrict__ sid,
-                            uint64_t *__restrict__ ids, const uint32_t *__restrict__ list = nullptr,
-                            const uint32_t *__restrict__ list_n = nullptr) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t count = list ? *list_n : n;
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += stride) {
-        const uint64_t i = list ? list[t] : t;
-        const uint32_t sl = slot_of[i];
-        const uint32_t id = sl == kNoId ? kNoId : sid[sl];
-        ids[i] = id == kNoId ? ~0ull : (uint64_t)id;
     }
 }
 
@@ -527,30 +460,6 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_resolve(SdBatch B, uint64_t n, 
     if (threadIdx.x == 0) bmiss[blockIdx.x] = tot;
 }
 
-// Exclusive scan of the per-block miss counts in place; *total = all misses.
-__global__ __launch_bounds__(kSdScan) void k_sd_xscan(uint32_t *__restrict__ v, uint32_t nblk,
-                                                      uint32_t *__restrict__ total) {
-    __shared__ uint32_t wsum[kSdScan / 64];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (nblk + kSdScan - 1) / kSdScan;
-    uint32_t sum = 0;
-    for (uint32_t k = 0; k < per; ++k) {
-        const uint32_t j = t * per + k;
-        if (j < nblk) sum += v[j];
-    }
-    uint32_t tot;
-    uint32_t run = block_excl_scan<kSdScan>(sum, wsum, &tot);
-    for (uint32_t k = 0; k < per; ++k) {
-        const uint32_t j = t * per + k;
-        if (j < nblk) {
-            const uint32_t c = v[j];
-            v[j] = run;
-            run += c;
-        }
-    }
-    if (t == 0) *total = tot;
-}
-
 // The misses in arrival order: list[bmiss[block] + rank in block] = i.
 __global__ __launch_bounds__(kSdBlock) void k_sd_compact(uint64_t n, const uint64_t *__restrict__ ids,
                                                          const uint32_t *__restrict__ bmiss,
@@ -571,16 +480,6 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_compact(uint64_t n, const uint6
 #pragma unroll
     for (int k = 0; k < PER; ++k)
         if (miss[k]) list[at++] = (uint32_t)(base + (uint64_t)threadIdx.x * PER + k);
-}
-
-__global__ void k_sd_init(uint64_t *__restrict__ stag, uint32_t *__restrict__ sid, uint32_t *__restrict__ sfirst,
-                          uint64_t nslots) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nslots; j += stride) {
-        stag[j] = kEmptyTag;
-        sid[j] = kNoId;
-        sfirst[j] = kNoId;
-    }
 }
 
 // ---------------------------------------------------------------- reclaim
@@ -607,52 +506,11 @@ __global__ void k_rc_flag(uint64_t capacity, const uint64_t *__restrict__ iloc, 
         vict[id] = (iloc[id] & kLocValid) && dead[id];
 }
 
-__global__ void k_rc_keep(const uint64_t *__restrict__ keep, uint64_t n_keep, uint64_t capacity,
-                          uint8_t *__restrict__ vict) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_keep; j += stride)
-        if (keep[j] < capacity) vict[keep[j]] = 0;
-}
-
-// Victims per block of kSdTile ids (thread-contiguous, as k_sd_count).
-__global__ __launch_bounds__(kSdBlock) void k_rc_vcount(uint64_t capacity, const uint8_t *__restrict__ vict,
-                                                        uint32_t *__restrict__ bv) {
-    __shared__ uint32_t wsum[kSdBlock / 64];
-    constexpr int PER = kSdTile / kSdBlock;
-    const uint64_t base = (uint64_t)blockIdx.x * kSdTile + (uint64_t)threadIdx.x * PER;
-    uint32_t c = 0;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) c += base + k < capacity && vict[base + k];
-    uint32_t tot;
-    (void)block_excl_scan<kSdBlock>(c, wsum, &tot);
-    if (threadIdx.x == 0) bv[blockIdx.x] = tot;
-}
-
-// The victims onto the free stack in ascending id order (bv scanned); their ids read as
-// never assigned from here on.
-__global__ __launch_bounds__(kSdBlock) void k_rc_vpush(uint64_t capacity, const uint8_t *__restrict__ vict,
-                                                       const uint32_t *__restrict__ bv,
-                                                       const unsigned long long *__restrict__ state,
-                                                       uint32_t *__restrict__ free_ids, uint64_t *__restrict__ iloc) {
-    __shared__ uint32_t wsum[kSdBlock / 64];
-    constexpr int PER = kSdTile / kSdBlock;
-    const uint64_t base = (uint64_t)blockIdx.x * kSdTile + (uint64_t)threadIdx.x * PER;
-    bool v[PER];
-    uint32_t c = 0;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        v[k] = base + k < capacity && vict[base + k];
-        c += v[k];
-    }
-    uint32_t tot;
-    uint64_t at = (uint64_t)state[6] + bv[blockIdx.x] + block_excl_scan<kSdBlock>(c, wsum, &tot);
-#pragma unroll
-    for (int k = 0; k < PER; ++k)
-        if (v[k]) {
-            free_ids[at++] = (uint32_t)(base + k);
-            iloc[base + k] = 0;
-        }
-}
+// A victim's id reads as never assigned from here on.
+struct IlocForget {
+    uint64_t *iloc;
+    __device__ void operator()(uint64_t id) const { iloc[id] = 0; }
+};
 
 __device__ __forceinline__ bool rc_survives(const uint32_t *__restrict__ sid, const uint8_t *__restrict__ vict,
                                             uint64_t s, uint64_t nslots) {
@@ -687,20 +545,20 @@ __global__ __launch_bounds__(kSdBlock) void k_rc_scount(uint64_t nslots, const u
 }
 
 // Scans of the survivors' block counts and bytes, and the counters after the reclaim:
-// rc_n[0] victims (k_sd_xscan), [1] survivors, [2] movers listed so far.
-__global__ __launch_bounds__(kSdScan) void k_rc_scan(uint32_t *__restrict__ bs, const uint32_t *__restrict__ bb,
+// rc_n[0] victims (k_scan_blocks), [1] survivors, [2] movers listed so far.
+__global__ __launch_bounds__(kScanThreads) void k_rc_scan(uint32_t *__restrict__ bs, const uint32_t *__restrict__ bb,
                                                      uint64_t *__restrict__ base, uint32_t nblk,
                                                      unsigned long long *__restrict__ state,
                                                      uint32_t *__restrict__ rc_n, uint64_t *__restrict__ n_reclaimed) {
-    __shared__ uint32_t wsum[kSdScan / 64];
-    __shared__ unsigned long long part[kSdScan];
+    __shared__ uint32_t wsum[kScanThreads / 64];
+    __shared__ unsigned long long part[kScanThreads];
     unsigned long long bytes;
     const uint32_t tot = sd_scan_blocks(bs, bb, base, nblk, wsum, part, &bytes);
-    if (threadIdx.x == kSdScan - 1) {
+    if (threadIdx.x == kScanThreads - 1) {
         rc_n[1] = tot;
         rc_n[2] = 0;
-        state[3] = bytes;          // the arena holds the survivors' text only
-        state[6] += rc_n[0];
+        state[kSdArena] = bytes;   // the arena holds the survivors' text only
+        pool_reclaimed(state, rc_n[0]);
         if (n_reclaimed) *n_reclaimed = rc_n[0];
     }
 }
@@ -765,22 +623,6 @@ __global__ __launch_bounds__(kSdBlock) void k_rc_move(uint64_t nslots, const uin
     }
 }
 
-// Claim the slot of a tag no one holds: the slot, or kNoId when the tag is in the table.
-__device__ __forceinline__ uint32_t rc_insert(uint64_t tag, uint64_t *__restrict__ stag, uint64_t smask) {
-    uint64_t h = mix64(tag) & smask;
-    for (uint64_t probe = 0; probe <= smask; ++probe) {
-        const uint64_t cur = stag[h];
-        if (cur == tag) return kNoId;
-        if (cur == kEmptyTag) {
-            const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&stag[h]), kEmptyTag, tag);
-            if (prev == kEmptyTag) return (uint32_t)h;
-            if (prev == tag) return kNoId;
-        }
-        h = (h + 1) & smask;
-    }
-    return kNoId;
-}
-
 // Round 0's owners back to their tags.
 __global__ __launch_bounds__(kSdBlock) void k_rc_place0(const uint32_t *__restrict__ rc_n,
                                                         const uint64_t *__restrict__ sv_tag,
@@ -794,7 +636,7 @@ __global__ __launch_bounds__(kSdBlock) void k_rc_place0(const uint32_t *__restri
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < count; r += stride) {
         const uint64_t tag = sv_tag[r];
         if (tag >> 62) continue;
-        const uint32_t h = rc_insert(tag, stag, smask);
+        const uint32_t h = probe_insert(stag, smask, tag, kEmptyTag);
         if (h == kNoId) {
             atomicOr(err, kErrRounds);
             continue;
@@ -822,10 +664,10 @@ __global__ __launch_bounds__(kSdBlock) void k_rc_place(uint32_t j, const uint32_
         if (own == kEmptyTag) continue;
         const uint64_t loc = sv_loc[r];
         const uint64_t tag = sd_tag(j, sd_hash(A.bytes, A.safe, loc_off(loc), loc_len(loc), P.seed[j]), P.hmask);
-        uint32_t h = rc_insert(tag, stag, smask);
+        uint32_t h = probe_insert(stag, smask, tag, kEmptyTag);
         if (h == kNoId) {
             if ((own >> 62) != j + 1) continue;
-            h = rc_insert(own, stag, smask);
+            h = probe_insert(stag, smask, own, kEmptyTag);
             if (h == kNoId) {
                 atomicOr(err, kErrRounds);
                 continue;
@@ -835,11 +677,6 @@ __global__ __launch_bounds__(kSdBlock) void k_rc_place(uint32_t j, const uint32_
         sid[h] = sv_id[r];
         sv_tag[r] = kEmptyTag;
     }
-}
-
-unsigned sd_grid(uint64_t n, unsigned block, unsigned cap = 8192) {
-    const uint64_t g = (n + block - 1) / block;
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
 }
 
 // Key text by id (tbe_sdir_text_lengths_device / tbe_sdir_text_device): the length from
@@ -899,18 +736,14 @@ struct tbe_string_directory {
     uint64_t *sloc = nullptr;
     uint64_t *iloc = nullptr;
     uint8_t *arena = nullptr;
-    unsigned long long *state = nullptr;   // see k_sd_scan
+    unsigned long long *state = nullptr;   // kStateWords counters (tbe_idpool.hpp, kSd*)
     // reclaim (allocated by the first one, sd_reclaim_scratch)
-    uint32_t *free_ids = nullptr;          // the free stack, capacity ids
+    PoolScratch pool;
     uint8_t *arena2 = nullptr;             // the arena the next reclaim compacts into
-    uint8_t *vict = nullptr;               // [capacity]
     uint64_t *sv_tag = nullptr, *sv_loc = nullptr;
     uint32_t *sv_id = nullptr, *movers = nullptr;   // survivor records / movers, capacity each
-    uint32_t *rc_bv = nullptr, *rc_bs = nullptr, *rc_bb = nullptr, *rc_n = nullptr;
+    uint32_t *rc_bs = nullptr, *rc_bb = nullptr;
     uint64_t *rc_base = nullptr;
-    uint8_t *rc_dead = nullptr;            // tbe_sdir_reclaim: the engine's flags, its keep list, its count
-    uint64_t *rc_keep = nullptr, *rc_count = nullptr;
-    uint64_t rc_keep_cap = 0;
     // per-batch scratch
     uint64_t tmp_cap = 0;
     uint32_t *slot_of = nullptr;
@@ -922,7 +755,7 @@ struct tbe_string_directory {
     uint32_t *bmiss = nullptr;             // warm path: misses per block (scanned)
     // warm-path choice: 0 auto (the last observed batch's new-key share), 1 full pass, 2 warm
     int mode = 0;
-    unsigned long long *h_state = nullptr; // pinned: state[0] after the last assign (async copy)
+    unsigned long long *h_state = nullptr; // pinned: state[kSdEver] after the last assign (async copy)
     hipEvent_t ev_state = nullptr;
     bool state_pending = false;
     unsigned long long last_ids = 0;       // ids at the previous observed copy
@@ -967,33 +800,31 @@ tbe_status sd_scratch(tbe_string_directory *d, uint64_t n) {
     return TBE_OK;
 }
 
+void sd_free_reclaim_scratch(tbe_string_directory *d) {
+    for (void *p : {(void *)d->arena2, (void *)d->sv_tag, (void *)d->sv_loc, (void *)d->sv_id, (void *)d->movers,
+                    (void *)d->rc_bs, (void *)d->rc_bb, (void *)d->rc_base})
+        if (p) (void)hipFree(p);
+    d->arena2 = nullptr;
+    d->sv_tag = d->sv_loc = d->rc_base = nullptr;
+    d->sv_id = d->movers = d->rc_bs = d->rc_bb = nullptr;
+    pool_scratch_free(d->pool);
+}
+
 tbe_status sd_reclaim_scratch(tbe_string_directory *d) {
-    if (d->free_ids) return TBE_OK;
-    const uint64_t cap = d->capacity;
-    const uint64_t nbi = (cap + kSdTile - 1) / kSdTile, nbs = (d->nslots + kSdTile - 1) / kSdTile;
-    const bool ok = hipMalloc(&d->arena2, d->arena_alloc) == hipSuccess &&
-                    hipMalloc(&d->vict, cap) == hipSuccess &&
-                    hipMalloc(&d->sv_tag, cap * sizeof(uint64_t)) == hipSuccess &&
-                    hipMalloc(&d->sv_loc, cap * sizeof(uint64_t)) == hipSuccess &&
-                    hipMalloc(&d->sv_id, cap * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&d->movers, cap * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&d->rc_bv, nbi * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&d->rc_bs, nbs * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&d->rc_bb, nbs * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&d->rc_base, nbs * sizeof(uint64_t)) == hipSuccess &&
-                    hipMalloc(&d->rc_n, 4 * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&d->free_ids, cap * sizeof(uint32_t)) == hipSuccess;   // last: marks the set complete
-    if (!ok || hipMemset(d->arena2, 0, d->arena_alloc) != hipSuccess) {
-        for (void *p : {(void *)d->arena2, (void *)d->vict, (void *)d->sv_tag, (void *)d->sv_loc, (void *)d->sv_id,
-                        (void *)d->movers, (void *)d->rc_bv, (void *)d->rc_bs, (void *)d->rc_bb, (void *)d->rc_base,
-                        (void *)d->rc_n, (void *)d->free_ids})
-            if (p) (void)hipFree(p);
-        d->arena2 = d->vict = nullptr;
-        d->sv_tag = d->sv_loc = d->rc_base = nullptr;
-        d->sv_id = d->movers = d->rc_bv = d->rc_bs = d->rc_bb = d->rc_n = d->free_ids = nullptr;
-        return TBE_ENOMEM;
-    }
-    return TBE_OK;
+    if (d->pool.free_ids) return TBE_OK;
+    const uint64_t cap = d->capacity, nbs = (d->nslots + kSdTile - 1) / kSdTile;
+    if (hipMalloc(&d->arena2, d->arena_alloc) == hipSuccess &&
+        hipMalloc(&d->sv_tag, cap * sizeof(uint64_t)) == hipSuccess &&
+        hipMalloc(&d->sv_loc, cap * sizeof(uint64_t)) == hipSuccess &&
+        hipMalloc(&d->sv_id, cap * sizeof(uint32_t)) == hipSuccess &&
+        hipMalloc(&d->movers, cap * sizeof(uint32_t)) == hipSuccess &&
+        hipMalloc(&d->rc_bs, nbs * sizeof(uint32_t)) == hipSuccess &&
+        hipMalloc(&d->rc_bb, nbs * sizeof(uint32_t)) == hipSuccess &&
+        hipMalloc(&d->rc_base, nbs * sizeof(uint64_t)) == hipSuccess &&
+        hipMemset(d->arena2, 0, d->arena_alloc) == hipSuccess && pool_scratch_alloc(d->pool, cap))
+        return TBE_OK;
+    sd_free_reclaim_scratch(d);
+    return TBE_ENOMEM;
 }
 
 bool batch_ok(const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *d_offs, uint64_t n) {
@@ -1037,7 +868,7 @@ tbe_status tbe_sdir_create(uint64_t capacity, uint64_t arena_bytes, const char *
               hipMalloc(&d->sloc, ns * sizeof(uint64_t)) == hipSuccess &&
               hipMalloc(&d->iloc, capacity * sizeof(uint64_t)) == hipSuccess &&
               hipMalloc(&d->arena, d->arena_alloc) == hipSuccess &&
-              hipMalloc(&d->state, 8 * sizeof(unsigned long long)) == hipSuccess &&
+              hipMalloc(&d->state, kStateWords * sizeof(unsigned long long)) == hipSuccess &&
               hipMalloc(&d->list_n, (kRounds + 1) * sizeof(uint32_t)) == hipSuccess &&
               hipHostMalloc(&d->h_state, sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess &&
               hipEventCreateWithFlags(&d->ev_state, hipEventDisableTiming) == hipSuccess;
@@ -1045,8 +876,8 @@ tbe_status tbe_sdir_create(uint64_t capacity, uint64_t arena_bytes, const char *
         tbe_sdir_destroy(d);
         return TBE_ENOMEM;
     }
-    k_sd_init<<<sd_grid(ns, 256), 256>>>(d->stag, d->sid, d->sfirst, ns);
-    if (hipMemset(d->state, 0, 8 * sizeof(unsigned long long)) != hipSuccess ||
+    k_table_init<<<grid_for(ns, 256), 256>>>(d->stag, d->sid, d->sfirst, ns, kEmptyTag);
+    if (hipMemset(d->state, 0, kStateWords * sizeof(unsigned long long)) != hipSuccess ||
         hipMemset(d->arena, 0, d->arena_alloc) != hipSuccess ||
         hipMemset(d->iloc, 0, capacity * sizeof(uint64_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
         tbe_sdir_destroy(d);
@@ -1061,14 +892,12 @@ void tbe_sdir_destroy(tbe_string_directory *d) {
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
     sd_free_scratch(d);
+    sd_free_reclaim_scratch(d);
     if (d->h_state) (void)hipHostFree(d->h_state);
     if (d->ev_state) (void)hipEventDestroy(d->ev_state);
     for (void *p : {(void *)d->stag, (void *)d->sid, (void *)d->sfirst, (void *)d->sloc, (void *)d->iloc,
                     (void *)d->arena, (void *)d->state, (void *)d->list_n, (void *)d->d_bytes, (void *)d->d_offs,
-                    (void *)d->d_ids, (void *)d->arena2, (void *)d->vict, (void *)d->sv_tag, (void *)d->sv_loc,
-                    (void *)d->sv_id, (void *)d->movers, (void *)d->rc_bv, (void *)d->rc_bs, (void *)d->rc_bb,
-                    (void *)d->rc_base, (void *)d->rc_n, (void *)d->free_ids, (void *)d->rc_dead, (void *)d->rc_keep,
-                    (void *)d->rc_count})
+                    (void *)d->d_ids})
         if (p) (void)hipFree(p);
     delete d;
 }
@@ -1091,7 +920,7 @@ tbe_status tbe_sdir_assign_device(tbe_string_directory *d, const uint8_t *d_byte
     hipStream_t st = (hipStream_t)stream;
     const SdBatch B{d_bytes, d_offs, n_bytes, n_bytes & ~7ull};
     const SdArena A{d->arena, d->arena_alloc & ~7ull};
-    unsigned long long *err = d->state + 1;
+    unsigned long long *err = d->state + kStErr;
     if (hipMemsetAsync(d->list_n, 0, (kRounds + 1) * sizeof(uint32_t), st) != hipSuccess) return TBE_EDEVICE;
     const uint64_t smask = d->nslots - 1;
     const uint32_t nblk = (uint32_t)((n + kSdTile - 1) / kSdTile);
@@ -1119,7 +948,7 @@ tbe_status tbe_sdir_assign_device(tbe_string_directory *d, const uint8_t *d_byte
     const uint32_t *miss_n = warm ? d->list_n + kRounds : nullptr;
     if (warm) {
         k_sd_resolve<<<nblk, kSdBlock, 0, st>>>(B, n, d->P, d->stag, d->sid, d->sloc, smask, A, d_ids, d->bmiss);
-        k_sd_xscan<<<1, kSdScan, 0, st>>>(d->bmiss, nblk, d->list_n + kRounds);
+        k_scan_blocks<<<1, kScanThreads, 0, st>>>(d->bmiss, nblk, d->list_n + kRounds);
         k_sd_compact<<<nblk, kSdBlock, 0, st>>>(n, d_ids, d->bmiss, d->miss);
     }
     for (int round = 0; round < kRounds; ++round) {
@@ -1127,22 +956,22 @@ tbe_status tbe_sdir_assign_device(tbe_string_directory *d, const uint8_t *d_byte
         const uint32_t *in_n = round ? d->list_n + (round - 1) : miss_n;
         uint32_t *nx = (round + 1 < kRounds) ? d->list[round & 1] : nullptr;
         uint32_t *nx_n = (round + 1 < kRounds) ? d->list_n + round : nullptr;
-        const unsigned g = in ? (round ? kListGrid : sd_grid(n, kSdBlock)) : sd_grid(n, kSdBlock);
+        const unsigned g = in ? (round ? kListGrid : grid_for(n, kSdBlock)) : grid_for(n, kSdBlock);
         k_sd_claim<<<g, kSdBlock, 0, st>>>(B, n, in, in_n, (uint32_t)round, d->P, d->stag, d->sid, d->sfirst, smask,
                                            d->slot_of, err);
         k_sd_verify<<<g, kSdBlock, 0, st>>>(B, n, in, in_n, A, d->sid, d->sfirst, d->sloc, d->slot_of, nx, nx_n, err);
     }
     k_sd_count<<<nblk, kSdBlock, 0, st>>>(d_offs, n, d->slot_of, d->sid, d->sfirst, d->bsum, d->bbytes, miss,
                                           miss_n);
-    k_sd_scan<<<1, kSdScan, 0, st>>>(d->bsum, d->bbytes, d->bbase, nblk, d->state, d->capacity, d->arena_bytes);
+    k_sd_scan<<<1, kScanThreads, 0, st>>>(d->bsum, d->bbytes, d->bbase, nblk, d->state, d->capacity, d->arena_bytes);
     k_sd_assign<<<nblk, kSdBlock, 0, st>>>(B, n, d->slot_of, d->sid, d->sfirst, d->sloc, d->iloc, d->arena, d->bsum,
                                            d->bbase, d->state, d->capacity, d->arena_bytes, d->imask, d->ish,
-                                           d->free_ids, miss, miss_n);
-    k_sd_gather<<<sd_grid(n, 256), 256, 0, st>>>(d->slot_of, n, d->sid, d_ids, miss, miss_n);
+                                           d->pool.free_ids, miss, miss_n);
+    k_gather<<<grid_for(n, 256), 256, 0, st>>>(d->slot_of, n, d->sid, d_ids, miss, miss_n);
     d->since_n += n;
     if (!d->state_pending) {
         // the id count after this batch, for a later call's choice
-        if (hipMemcpyAsync(d->h_state, d->state, sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        if (hipMemcpyAsync(d->h_state, d->state + kSdEver, sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipEventRecord(d->ev_state, st) != hipSuccess)
             return TBE_EDEVICE;
         d->state_pending = true;
@@ -1166,7 +995,7 @@ tbe_status tbe_sdir_lookup_device(tbe_string_directory *d, const uint8_t *d_byte
     if (hipSetDevice(d->device) != hipSuccess) return TBE_EDEVICE;
     const SdBatch B{d_bytes, d_offs, n_bytes, n_bytes & ~7ull};
     const SdArena A{d->arena, d->arena_alloc & ~7ull};
-    k_sd_lookup<<<sd_grid(n, kSdBlock), kSdBlock, 0, (hipStream_t)stream>>>(B, n, d->P, d->stag, d->sid, d->sloc,
+    k_sd_lookup<<<grid_for(n, kSdBlock), kSdBlock, 0, (hipStream_t)stream>>>(B, n, d->P, d->stag, d->sid, d->sloc,
                                                                             d->nslots - 1, A, d_ids);
     return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
 }
@@ -1202,11 +1031,11 @@ tbe_status tbe_sdir_assign(tbe_string_directory *d, const uint8_t *bytes, uint64
 tbe_status tbe_sdir_size(tbe_string_directory *d, uint64_t *n_ids) {
     if (!d || !n_ids) return TBE_EINVAL;
     if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TBE_EDEVICE;
-    unsigned long long st[8] = {0};
+    unsigned long long st[kStateWords] = {0};
     if (hipMemcpy(st, d->state, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) return TBE_EDEVICE;
-    *n_ids = st[5] - st[6];   // counters handed out less the ids waiting on the free stack
-    if (st[1] & (kErrRange | kErrRounds | kErrArena | kErrFull)) return TBE_ERANGE;
-    return (st[1] & kErrBatch) ? TBE_EINVAL : TBE_OK;
+    *n_ids = st[kStFresh] - st[kStNfree];   // counters handed out less the ids waiting on the free stack
+    if (st[kStErr] & (kErrRange | kErrRounds | kErrArena | kErrFull)) return TBE_ERANGE;
+    return (st[kStErr] & kErrBatch) ? TBE_EINVAL : TBE_OK;
 }
 
 tbe_status tbe_sdir_reclaim_device(tbe_string_directory *d, const uint8_t *d_dead, const uint64_t *d_keep_ids,
@@ -1217,56 +1046,36 @@ tbe_status tbe_sdir_reclaim_device(tbe_string_directory *d, const uint8_t *d_dea
     if (rc != TBE_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const uint64_t cap = d->capacity, ns = d->nslots, smask = ns - 1;
-    const uint32_t nbi = (uint32_t)((cap + kSdTile - 1) / kSdTile), nbs = (uint32_t)((ns + kSdTile - 1) / kSdTile);
-    unsigned long long *err = d->state + 1;
-    k_rc_flag<<<sd_grid(cap, 256), 256, 0, st>>>(cap, d->iloc, d_dead, d->vict);
-    if (n_keep) k_rc_keep<<<sd_grid(n_keep, 256), 256, 0, st>>>(d_keep_ids, n_keep, cap, d->vict);
-    k_rc_vcount<<<nbi, kSdBlock, 0, st>>>(cap, d->vict, d->rc_bv);
-    k_sd_xscan<<<1, kSdScan, 0, st>>>(d->rc_bv, nbi, d->rc_n);
-    k_rc_vpush<<<nbi, kSdBlock, 0, st>>>(cap, d->vict, d->rc_bv, d->state, d->free_ids, d->iloc);
-    k_rc_scount<<<nbs, kSdBlock, 0, st>>>(ns, d->sid, d->sloc, d->vict, d->rc_bs, d->rc_bb);
-    k_rc_scan<<<1, kSdScan, 0, st>>>(d->rc_bs, d->rc_bb, d->rc_base, nbs, d->state, d->rc_n, d_n_reclaimed);
-    k_rc_move<<<nbs, kSdBlock, 0, st>>>(ns, d->stag, d->sid, d->sloc, d->vict, d->rc_bs, d->rc_base, d->arena,
-                                        d->arena2, d->sv_tag, d->sv_id, d->sv_loc, d->iloc, d->movers, d->rc_n);
-    k_sd_init<<<sd_grid(ns, 256), 256, 0, st>>>(d->stag, d->sid, d->sfirst, ns);
+    const uint32_t nbi = (uint32_t)((cap + kPoolTile - 1) / kPoolTile), nbs = (uint32_t)((ns + kSdTile - 1) / kSdTile);
+    unsigned long long *err = d->state + kStErr;
+    const PoolScratch &p = d->pool;
+    k_rc_flag<<<grid_for(cap, 256), 256, 0, st>>>(cap, d->iloc, d_dead, p.vict);
+    if (n_keep) k_pool_keep<<<grid_for(n_keep, 256), 256, 0, st>>>(d_keep_ids, n_keep, cap, p.vict);
+    k_pool_vcount<<<nbi, kPoolBlock, 0, st>>>(cap, p.vict, p.rc_bv);
+    k_scan_blocks<<<1, kScanThreads, 0, st>>>(p.rc_bv, nbi, p.rc_n);
+    k_pool_vpush<<<nbi, kPoolBlock, 0, st>>>(cap, p.vict, p.rc_bv, d->state, p.free_ids, IlocForget{d->iloc});
+    k_rc_scount<<<nbs, kSdBlock, 0, st>>>(ns, d->sid, d->sloc, p.vict, d->rc_bs, d->rc_bb);
+    k_rc_scan<<<1, kScanThreads, 0, st>>>(d->rc_bs, d->rc_bb, d->rc_base, nbs, d->state, p.rc_n, d_n_reclaimed);
+    k_rc_move<<<nbs, kSdBlock, 0, st>>>(ns, d->stag, d->sid, d->sloc, p.vict, d->rc_bs, d->rc_base, d->arena,
+                                        d->arena2, d->sv_tag, d->sv_id, d->sv_loc, d->iloc, d->movers, p.rc_n);
+    k_table_init<<<grid_for(ns, 256), 256, 0, st>>>(d->stag, d->sid, d->sfirst, ns, kEmptyTag);
     std::swap(d->arena, d->arena2);   // every later call reads the compacted arena
     const SdArena A{d->arena, d->arena_alloc & ~7ull};
-    k_rc_place0<<<sd_grid(cap, kSdBlock), kSdBlock, 0, st>>>(d->rc_n, d->sv_tag, d->sv_id, d->sv_loc, d->stag, d->sid,
+    k_rc_place0<<<grid_for(cap, kSdBlock), kSdBlock, 0, st>>>(p.rc_n, d->sv_tag, d->sv_id, d->sv_loc, d->stag, d->sid,
                                                             d->sloc, smask, err);
     for (uint32_t j = 0; j + 1 < (uint32_t)kRounds; ++j)
-        k_rc_place<<<kListGrid, kSdBlock, 0, st>>>(j, d->rc_n, d->movers, d->sv_tag, d->sv_id, d->sv_loc, A, d->P,
+        k_rc_place<<<kListGrid, kSdBlock, 0, st>>>(j, p.rc_n, d->movers, d->sv_tag, d->sv_id, d->sv_loc, A, d->P,
                                                    d->stag, d->sid, d->sloc, smask, err);
     return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
 }
 
 tbe_status tbe_sdir_reclaim(tbe_string_directory *d, tbe_engine *engine, int64_t ts_us, const uint64_t *keep_ids,
                             uint64_t n_keep, uint64_t *n_reclaimed) {
-    if (!d || !engine || !n_reclaimed || (n_keep && !keep_ids)) return TBE_EINVAL;
-    *n_reclaimed = 0;
-    // after every assign and engine batch, whatever its stream
-    if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TBE_EDEVICE;
-    if ((!d->rc_dead && hipMalloc(&d->rc_dead, d->capacity) != hipSuccess) ||
-        (!d->rc_count && hipMalloc(&d->rc_count, sizeof(uint64_t)) != hipSuccess))
-        return TBE_ENOMEM;
-    if (n_keep > d->rc_keep_cap) {
-        if (d->rc_keep) (void)hipFree(d->rc_keep);
-        d->rc_keep = nullptr;
-        d->rc_keep_cap = 0;
-        if (hipMalloc(&d->rc_keep, n_keep * sizeof(uint64_t)) != hipSuccess) return TBE_ENOMEM;
-        d->rc_keep_cap = n_keep;
-    }
-    if (n_keep && hipMemcpy(d->rc_keep, keep_ids, n_keep * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
-        return TBE_EDEVICE;
-    // the engine must hold a row for every id of the directory (TBE_EINVAL otherwise)
-    tbe_status rc = tbe_expired_device(engine, ts_us, 0, d->capacity, d->rc_dead, 1, nullptr);
-    if (rc != TBE_OK) return rc;
-    if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TBE_EDEVICE;
-    rc = tbe_sdir_reclaim_device(d, d->rc_dead, d->rc_keep, n_keep, d->rc_count, nullptr);
-    if (rc != TBE_OK) return rc;
-    if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(n_reclaimed, d->rc_count, sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return TBE_EDEVICE;
-    return TBE_OK;
+    if (!d) return TBE_EINVAL;
+    return pool_reclaim_sync(d->pool, d->device, d->capacity, engine, ts_us, keep_ids, n_keep, n_reclaimed,
+                             [d](const uint8_t *dead, const uint64_t *keep, uint64_t nk, uint64_t *count) {
+                                 return tbe_sdir_reclaim_device(d, dead, keep, nk, count, nullptr);
+                             });
 }
 
 tbe_status tbe_sdir_text_lengths_device(tbe_string_directory *d, const uint64_t *d_ids, uint64_t n, uint64_t *d_lens,
@@ -1277,7 +1086,7 @@ tbe_status tbe_sdir_text_lengths_device(tbe_string_directory *d, const uint64_t 
     hipStream_t st = (hipStream_t)stream;
     if (d_n_missing && hipMemsetAsync(d_n_missing, 0, sizeof(uint64_t), st) != hipSuccess) return TBE_EDEVICE;
     if (n == 0) return TBE_OK;
-    k_sd_text_len<<<sd_grid(n, 256), 256, 0, st>>>(d_ids, n, d->iloc, d->capacity, d_lens,
+    k_sd_text_len<<<grid_for(n, 256), 256, 0, st>>>(d_ids, n, d->iloc, d->capacity, d_lens,
                                                    reinterpret_cast<unsigned long long *>(d_n_missing));
     return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
 }
@@ -1288,7 +1097,7 @@ tbe_status tbe_sdir_text_device(tbe_string_directory *d, const uint64_t *d_ids, 
     if (n == 0) return TBE_OK;
     if (!d_ids || !d_offs || !d_bytes) return TBE_EINVAL;
     if (hipSetDevice(d->device) != hipSuccess) return TBE_EDEVICE;
-    k_sd_text<<<sd_grid(n, 256), 256, 0, (hipStream_t)stream>>>(d_ids, n, d->iloc, d->capacity, d->arena, d_offs,
+    k_sd_text<<<grid_for(n, 256), 256, 0, (hipStream_t)stream>>>(d_ids, n, d->iloc, d->capacity, d->arena, d_offs,
                                                                 d_bytes);
     return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
 }

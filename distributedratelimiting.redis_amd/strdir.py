@@ -15,7 +15,7 @@ from typing import Iterable, List, Sequence, Tuple
 
 import numpy as np
 
-from .cluster import MASK64, scramble_walk
+from .cluster import MASK64, HostIdPool, _DeviceReclaim
 
 
 def _as_bytes(s) -> bytes:
@@ -35,63 +35,24 @@ def pack_strings(strings: Iterable) -> Tuple[np.ndarray, np.ndarray]:
     return buf, offs
 
 
-class HostStringDirectory:
-    """Host mirror of tbe_sdir_*: a stack of freed ids and a ``fresh`` counter.  Strings new
-    to it, in order of first occurrence, each pop the stack; once it is empty they take
-    id = scramble_walk(fresh++, capacity).  ``reclaim`` removes keys and pushes their ids
-    in ascending order.  Never reclaimed, it hands out scramble_walk(0), (1), ..."""
-
-    def __init__(self, capacity: int):
-        self.capacity = int(capacity)
-        self.ids = {}
-        self.free: List[int] = []
-        self.fresh = 0
-        self.overflow = False
+class HostStringDirectory(HostIdPool):
+    """Host mirror of tbe_sdir_*: a HostIdPool over key text."""
 
     def assign(self, strings: Sequence) -> np.ndarray:
         keys = [_as_bytes(s) for s in strings]
-        new = []
-        seen = set()
-        for k in keys:
-            if k not in self.ids and k not in seen:
-                seen.add(k)
-                new.append(k)
-        room = len(self.free) + max(0, self.capacity - self.fresh)
-        if len(new) > room:
-            self.overflow = True
-        new = new[:room]
-        n_pop = min(len(new), len(self.free))
-        for k in new[:n_pop]:
-            self.ids[k] = self.free.pop()
-        if new[n_pop:]:
-            ctr = np.arange(self.fresh, self.fresh + len(new) - n_pop, dtype=np.uint64)
-            self.fresh += len(new) - n_pop
-            for k, i in zip(new[n_pop:], scramble_walk(ctr, self.capacity).tolist()):
-                self.ids[k] = i
+        self._take([k for k in dict.fromkeys(keys) if k not in self.ids])
         return self.lookup(keys)
 
     def lookup(self, strings: Sequence) -> np.ndarray:
         get = self.ids.get
         return np.array([get(_as_bytes(s), MASK64) for s in strings], dtype=np.uint64)
 
-    def reclaim(self, dead_ids: Iterable, keep_ids: Iterable = ()) -> int:
-        """Remove every held key whose id is in dead_ids and not in keep_ids; their ids go
-        onto the free stack in ascending order.  Returns the number removed."""
-        gone = {int(i) for i in dead_ids} - {int(i) for i in keep_ids}
-        victims = sorted((i, k) for k, i in self.ids.items() if i in gone)
-        for i, k in victims:
-            del self.ids[k]
-            self.free.append(i)
-        return len(victims)
 
-    def size(self) -> int:
-        return len(self.ids)
-
-
-class StringDirectory:
+class StringDirectory(_DeviceReclaim):
     """The device string directory of one limiter (prefix = its InstanceName)."""
 
     MODES = {"auto": 0, "full": 1, "warm": 2}
+    _RECLAIM_DEVICE, _RECLAIM = "tbe_sdir_reclaim_device", "tbe_sdir_reclaim"
 
     def __init__(self, capacity: int, arena_bytes: int, prefix: str = "", device: int = -1,
                  hash_bits: int = None, mode: str = "auto"):
@@ -173,41 +134,6 @@ class StringDirectory:
         if st != _capi.TBE_OK:
             raise _capi.TbeError(st, "string directory over capacity" if st == _capi.TBE_ERANGE
                                  else "string directory error")
-        return n.value
-
-    def reclaim_device(self, d_dead, d_keep_ids=None):
-        """tbe_sdir_reclaim_device on the current stream: d_dead is a uint8 device tensor of
-        ``capacity`` flags indexed by id (``TokenBucketEngine.expired_device``), d_keep_ids
-        an int64 device tensor of ids never to remove.  Returns a one-element int64 device
-        tensor that receives the number of keys removed (nothing is synchronised)."""
-        import torch
-        from . import _capi
-        from .cluster import device_stream
-        if d_dead.numel() != self.capacity or d_dead.element_size() != 1:
-            raise ValueError("d_dead must hold one byte per id of the directory's capacity")
-        d_dead = d_dead.contiguous()
-        n_keep = 0 if d_keep_ids is None else d_keep_ids.numel()
-        if n_keep:
-            d_keep_ids = d_keep_ids.contiguous()
-        count = torch.zeros(1, dtype=torch.int64, device=d_dead.device)
-        st = self._lib.tbe_sdir_reclaim_device(self._h, d_dead.data_ptr(), d_keep_ids.data_ptr() if n_keep else None,
-                                               n_keep, count.data_ptr(), device_stream(d_dead.device))
-        if st != _capi.TBE_OK:
-            raise _capi.TbeError(st, "tbe_sdir_reclaim_device failed")
-        return count
-
-    def reclaim(self, engine, ts_us: int, keep_ids=None) -> int:
-        """Drop every key whose bucket no longer exists in `engine` at ts_us (tbe_sdir_reclaim:
-        the Redis EXPIRE of idle buckets, TB:232-235); keep_ids: ids of an assign whose engine
-        batch is not submitted yet.  Synchronous; returns the number of keys removed."""
-        import ctypes
-        from . import _capi
-        keep = np.ascontiguousarray([] if keep_ids is None else keep_ids, dtype=np.uint64)
-        n = ctypes.c_uint64()
-        st = self._lib.tbe_sdir_reclaim(self._h, engine.handle, int(ts_us), keep.ctypes.data if keep.size else None,
-                                        keep.size, ctypes.byref(n))
-        if st != _capi.TBE_OK:
-            raise _capi.TbeError(st, "tbe_sdir_reclaim failed")
         return n.value
 
     def text_of(self, d_ids, return_missing: bool = False):

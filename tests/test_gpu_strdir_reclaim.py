@@ -209,6 +209,69 @@ def test_removed_keys_and_reuse(engine_lib, gpu):
         check(d, h, first + second + third, [])
 
 
+@pytest.mark.parametrize("mode", ["full", "warm"])
+def test_stack_then_counter_across_tiles_and_overflow(engine_lib, gpu, mode):
+    """The string twin of the u64 directory's test of the same name: one batch takes 700 ids
+    from the stack and 1,300 from the counter, its new strings spread over three
+    1,024-request blocks; a batch past the room overflows, and a reclaim afterwards works
+    but leaves the error in place.  The arena (64 bytes per id) is never the limit."""
+    import torch
+    from distributedratelimiting.redis_amd import _capi
+    from distributedratelimiting.redis_amd.strdir import HostStringDirectory, StringDirectory, to_device
+    cap = 4_096
+    rng = np.random.default_rng(5)
+
+    def text(nums):
+        return [b"user-%d" % k for k in np.asarray(nums).tolist()]
+
+    def assign(d, h, s):
+        want = h.assign(s)
+        got = _u64(d.assign(*to_device(s, gpu)))
+        assert np.array_equal(got, want)
+        return want
+
+    def flags(ids):
+        f = np.zeros(cap, dtype=np.uint8)
+        f[np.asarray(ids, dtype=np.int64)] = 1
+        return torch.from_numpy(f).to(gpu)
+
+    def erange(d):
+        with pytest.raises(_capi.TbeError) as ei:
+            d.size()
+        return ei.value.status == _capi.TBE_ERANGE
+
+    with _side_stream(gpu):
+        d = StringDirectory(cap, 64 * cap, prefix="t:", device=0, mode=mode)
+        h = HostStringDirectory(cap)
+        ids = assign(d, h, text(np.arange(1_500)))
+        vid = rng.permutation(ids.astype(np.int64))[:700]
+        assert int(d.reclaim_device(flags(vid)).item()) == h.reclaim(vid.tolist()) == 700
+        assert len(h.free) == 700 and h.fresh == 1_500
+        # 2,000 new strings, 600 of them twice, and 400 requests of surviving strings, shuffled
+        new = np.arange(10_000, 12_000)
+        surv = np.array([k for k in range(1_500) if b"user-%d" % k in h.ids])
+        batch = rng.permutation(np.concatenate([new, new[:600], surv[:400]]))
+        assert batch.shape[0] == 3_000
+        firsts = np.sort(np.unique(batch, return_index=True)[1][np.isin(np.unique(batch), new)])
+        assert firsts[0] < 1_024 and (firsts >= 2_048).any() and ((firsts >= 1_024) & (firsts < 2_048)).any()
+        assign(d, h, text(batch))
+        assert h.free == [] and h.fresh == 1_500 + 1_300 and d.size() == h.size() == 2_800
+        # room is 4,096 - 2,800 = 1,296: one string more overflows
+        over = text(np.arange(20_000, 21_297))
+        want = assign(d, h, over)
+        assert h.overflow and (want[:1_296] != NONE).all() and want[1_296] == NONE
+        assert erange(d)
+        # a reclaim stays in bounds, frees ids, drops the string that has no id; the error stays
+        vid = h.lookup(over[:50]).astype(np.int64)
+        assert int(d.reclaim_device(flags(vid)).item()) == h.reclaim(vid.tolist()) == 50
+        assert erange(d)
+        probe = over + text(batch[:200])
+        assert np.array_equal(_u64(d.lookup(*to_device(probe, gpu))), h.lookup(probe))
+        assign(d, h, over[-3:][::-1])                      # the string without an id among them
+        assert erange(d)
+        d.close()
+
+
 def test_noop_reclaims(engine_lib, gpu):
     import torch
     from distributedratelimiting.redis_amd import TokenBucketEngine

@@ -77,3 +77,30 @@ def test_reclaim_of_nothing_changes_nothing():
     ids = h.assign([b"p", b"q"])
     assert h.reclaim([]) == 0
     assert np.array_equal(h.assign([b"q", b"p", b"r"]), np.concatenate([ids[::-1], _walk(2, 3, 16)]))
+
+
+def test_stack_then_counter_and_overflow_same_rule_as_u64_directory():
+    """Reclaim, a batch that empties the stack and goes on with the counter, an overflow and
+    another reclaim: strings and u64 keys get the same ids at every step (one HostIdPool)."""
+    from distributedratelimiting.redis_amd.cluster import HostDirectory
+    cap = 4_096
+    rng = np.random.default_rng(5)
+    hs, hu = HostStringDirectory(cap), HostDirectory(cap)
+
+    def both(nums):
+        ids = hu.assign(np.asarray(nums, dtype=np.uint64))
+        assert np.array_equal(hs.assign([b"user-%d" % k for k in nums]), ids)
+        return ids
+
+    ids = both(list(range(1_500)))
+    vid = rng.permutation(ids.astype(np.int64))[:700].tolist()
+    assert hs.reclaim(vid) == hu.reclaim(vid) == 700 and hs.free == hu.free
+    surv = [k for k in range(1_500) if k in hu.ids]
+    batch = rng.permutation(list(range(10_000, 12_000)) + list(range(10_000, 10_600)) + surv[:400]).tolist()
+    both(batch)
+    assert hs.free == [] and hs.fresh == hu.fresh == 2_800 and hs.size() == hu.size() == 2_800
+    over = both(list(range(20_000, 21_297)))
+    assert hs.overflow and hu.overflow and over[1_295] != MASK64 and over[1_296] == MASK64
+    vid = over[:50].astype(np.int64).tolist()
+    assert hs.reclaim(vid) == hu.reclaim(vid) == 50 and hs.free == hu.free
+    both([21_296, 21_295, 21_294])
