@@ -40,7 +40,10 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_approx_export_state", "tbe_approx_import_state", "tbe_wait_batch_tick_device",
             "tbe_approx_sync_stream", "tbe_batch_format", "tbe_expired_device",
             "tbe_export_live_device", "tbe_export_live", "tbe_import_rows_device", "tbe_import_rows",
-            "tbe_approx_acquire_batch_retry", "tbe_approx_acquire_batch_retry_device")
+            "tbe_approx_acquire_batch_retry", "tbe_approx_acquire_batch_retry_device",
+            "tbe_approx_idle_device", "tbe_approx_reset_device", "tbe_approx_idle", "tbe_approx_reset",
+            "tbe_approx_export_live_device", "tbe_approx_export_live", "tbe_approx_import_rows_device",
+            "tbe_approx_import_rows")
 TBE_WAIT_FAILED, TBE_WAIT_GRANTED, TBE_WAIT_QUEUED, TBE_WAIT_REJECTED = 0, 1, 2, 3
 TBE_RETRY_NONE, TBE_RETRY_OVERFLOW = -1, 2**63 - 1   # retry_after_ticks of the approximate kind
 
@@ -181,6 +184,24 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_approx_export_state.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]
     lib.tbe_approx_import_state.restype = c_int32
     lib.tbe_approx_import_state.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]
+    lib.tbe_approx_idle_device.restype = c_int32
+    lib.tbe_approx_idle_device.argtypes = [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p]
+    lib.tbe_approx_reset_device.restype = c_int32
+    lib.tbe_approx_reset_device.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]
+    lib.tbe_approx_idle.restype = c_int32
+    lib.tbe_approx_idle.argtypes = [c_void_p, c_int64, c_uint64, c_uint64, c_void_p]
+    lib.tbe_approx_reset.restype = c_int32
+    lib.tbe_approx_reset.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p]
+    lib.tbe_approx_export_live_device.restype = c_int32
+    lib.tbe_approx_export_live_device.argtypes = [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]
+    lib.tbe_approx_export_live.restype = c_int32
+    lib.tbe_approx_export_live.argtypes = [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_uint64, POINTER(c_uint64)]
+    lib.tbe_approx_import_rows_device.restype = c_int32
+    lib.tbe_approx_import_rows_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]
+    lib.tbe_approx_import_rows.restype = c_int32
+    lib.tbe_approx_import_rows.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
     lib.tbe_gen_zipf_keys_device.restype = c_int32
     lib.tbe_gen_zipf_keys_device.argtypes = [c_uint64, c_uint64, c_double, c_uint64, c_uint64, c_void_p,
                                              c_void_p]

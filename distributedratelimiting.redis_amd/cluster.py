@@ -300,6 +300,37 @@ class _DeviceReclaim:
             raise _capi.TbeError(st, f"{self._RECLAIM} failed")
         return n.value
 
+    def reclaim_idle(self, engine, ts_us: int, keep_ids=None, d_idle=None):
+        """Give back the ids of the keys an ``ApproximateEngine`` no longer needs at ts_us
+        (DESIGN.md §2c): scan (``idle_device``), clear the flags of keep_ids (an int64 device
+        tensor or a sequence: ids of an assign whose engine batch is not submitted yet),
+        remove the flagged keys (``reclaim_device``) and reset the flagged ids to a new
+        engine's state (``reset_device``) -- all on the current stream, nothing synchronised.
+        d_idle: flags already scanned and agreed between the clients of a replicated tier
+        (``approx_idle_epoch``); the scan is then skipped.  The engine must cover the
+        directory's ids.  Ids no key holds are idle too and are reset with the rest (a sync
+        replays every id and leaves an unheld one a row with a period estimate), so an id
+        assigned after this call and before the next sync starts as a new limiter.  Returns (count, d_idle): a one-element int64 device tensor that
+        receives the number of keys removed, and the flags used."""
+        import torch
+        if engine.n_keys < self.capacity:
+            raise ValueError("the engine has fewer keys than the directory has ids")
+        dev = torch.device("cuda", torch.cuda.current_device()) if d_idle is None else d_idle.device
+        st = device_stream(dev)
+        if d_idle is None:
+            d_idle = torch.empty(self.capacity, dtype=torch.uint8, device=dev)
+            engine.idle_device(ts_us, d_idle, stream=st)
+        elif d_idle.numel() != self.capacity or d_idle.element_size() != 1:
+            raise ValueError("d_idle must hold one byte per id of the directory's capacity")
+        if keep_ids is not None:
+            keep = keep_ids if torch.is_tensor(keep_ids) else torch.as_tensor(
+                np.asarray(keep_ids, dtype=np.int64), device=dev)
+            if keep.numel():
+                d_idle.index_fill_(0, keep.to(device=dev, dtype=torch.int64), 0)
+        count = self.reclaim_device(d_idle)
+        engine.reset_device(d_idle, stream=st)
+        return count, d_idle
+
 
 class DeviceDirectory(_DeviceReclaim):
     """The owner's key directory in HBM (include/tbe_cluster.h tbe_dir_*).
@@ -760,6 +791,24 @@ def approx_epoch(engine, counts, ts_us: int, stagger_us: int, mode: str = "clien
         _all_reduce_sum(counts, group=group)
         return engine.sync(counts, 1, 0, ts_us, stagger_us, **_after_collective(counts))
     raise ValueError(f"unknown mode {mode!r}")
+
+
+def approx_idle_epoch(engine, ts_us: int, d_idle, group=None):
+    """Which keys every client of a replicated tier agrees are idle at ts_us.  Each rank scans
+    its own engine into the uint8 tensor ``d_idle`` (``idle_device``); the "not idle" flags
+    are summed over the ranks as int32, and a key stays flagged only where the sum is 0: a
+    key one client still queues on or has consumed from is kept by all.  Every rank then
+    reclaims and resets the same ids (``reclaim_idle(..., d_idle=d_idle)``), so replicas and
+    directories stay identical.  Returns d_idle."""
+    import torch
+    import torch.distributed as dist
+
+    engine.idle_device(ts_us, d_idle, **_after_collective(d_idle))
+    if dist.is_initialized() and dist.get_world_size(group) > 1:
+        busy = (d_idle == 0).to(torch.int32)
+        _all_reduce_sum(busy, group=group)
+        d_idle.copy_((busy == 0).to(torch.uint8))
+    return d_idle
 
 
 def _after_collective(t) -> dict:

@@ -3862,6 +3862,159 @@ __global__ void k_rows_write(Slot *__restrict__ table, const uint64_t *__restric
     }
 }
 
+// ---- approximate kind: idle scan, reset and portable snapshots of the {v, p, t} tier
+// (tbe_approx_idle_device / tbe_approx_reset_device / tbe_approx_export_live_device /
+// tbe_approx_import_rows_device)
+__device__ __forceinline__ ALocal alocal_load_nt(const ALocal *p) {
+    static_assert(sizeof(ALocal) == 16, "ALocal is one dwordx4 access");
+    const u32x4 w = ld_nt(reinterpret_cast<const u32x4 *>(p));
+    ALocal a;
+    a.cap = (int32_t)w.x;
+    a.local = (int32_t)w.y;
+    a.qsum = (uint16_t)(w.z & 0xFFFFu);
+    a.zc = (uint16_t)(w.z >> 16);
+    a.hc = w.w;
+    return a;
+}
+
+// idle[k - first] = 1 when key k could be handed to another name without losing anything:
+// nothing queued (zero-permit registrations included), ConsumedTokens == 0 (A:36, A:503-506:
+// the client view's global score plus the local score, C# unchecked int32), and a tier row
+// that gives a client syncing at ts_us nothing: absent, lapsed by k_approx_sync's test, or
+// decayed to 0 by its own operations (A:255-258).  aclient == nullptr: the view is derived
+// (aclient_lazy), its global score is (int32)(int64)gv[k] and AClient is not read.  One key
+// per lane: 16 B of ALocal, 8 B each of v and t (coalesced), 4 of the 16 B of AClient.
+__global__ __launch_bounds__(kBlock) void k_approx_idle(const ALocal *__restrict__ alocal,
+                                                        const AClient *__restrict__ aclient,
+                                                        const double *__restrict__ gv, const int64_t *__restrict__ gt,
+                                                        uint64_t first, uint64_t count, int64_t ts_us,
+                                                        double decay_rate, uint8_t *__restrict__ idle) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t k = first + i;
+    const ReqTime rq = req_time(ts_us, kApproxTtlMs);
+    const ALocal a = alocal_load_nt(alocal + k);
+    const double v = ld_nt(gv + k);
+    const int64_t t = ld_nt(gt + k);
+    const int32_t global = aclient ? ld_nt(&aclient[k].global) : (int32_t)(int64_t)v;
+    const bool present = (t != kAbsent) && !(t < rq.exp_lt);
+    bool worthless = true;
+    if (present) {
+        const double dt = lua_max(0.0, rq.new_t - new_t_of(t));   // A:255
+        const double decay = dt * decay_rate;
+        worthless = lua_max(0.0, v - decay) == 0.0;               // A:258 without the count
+    }
+    const bool consumed = (int32_t)((uint32_t)global + (uint32_t)a.local) != 0;
+    idle[i] = ((a.hc >> 16) == 0 && !consumed && worthless) ? 1 : 0;
+}
+
+// Every flagged key of the range gets k_init_approx's state; unflagged rows are not written.
+__global__ __launch_bounds__(kBlock) void k_approx_reset(ALocal *__restrict__ alocal, AClient *__restrict__ aclient,
+                                                         double *__restrict__ gv, double *__restrict__ gp,
+                                                         int64_t *__restrict__ gt, uint64_t first, uint64_t count,
+                                                         const uint8_t *__restrict__ flags, int32_t token_limit) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    if (!ld_nt(flags + i)) return;
+    const uint64_t k = first + i;
+    alocal[k] = ALocal{token_limit, 0, 0, 0, 0u};
+    aclient[k] = AClient{1.0, 0, 0};
+    gv[k] = 0.0;
+    gp[k] = 0.0;
+    gt[k] = kAbsent;
+}
+
+// Export of the SoA tier in k_live_count / k_live_scan / k_live_write's form (the scan
+// kernel is shared): a row is exported when it is live by row_live and its skip byte, if
+// there is a mask, is 0.
+__device__ __forceinline__ bool arow_out(const int64_t *__restrict__ gt, const uint8_t *__restrict__ skip,
+                                         uint64_t first, uint64_t i, int64_t exp_lt, int64_t &t) {
+    t = ld_nt(gt + first + i);
+    return row_live(t, exp_lt) && !(skip && ld_nt(skip + i));
+}
+
+__global__ __launch_bounds__(kBlock) void k_alive_count(const int64_t *__restrict__ gt,
+                                                        const uint8_t *__restrict__ skip, uint64_t first,
+                                                        uint64_t count, int64_t exp_lt,
+                                                        unsigned long long *__restrict__ tile_n) {
+    __shared__ uint32_t wsum[kWaves];
+    const uint64_t base = (uint64_t)blockIdx.x * kLiveTile;
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < kLiveItems; ++k) {
+        const uint64_t i = base + (uint64_t)k * kBlock + threadIdx.x;
+        int64_t t;
+        if (i < count && arow_out(gt, skip, first, i, exp_lt, t)) ++c;
+    }
+    uint32_t tot;
+    (void)block_excl_scan<kBlock>(c, wsum, &tot);
+    if (threadIdx.x == 0) tile_n[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(kBlock) void k_alive_write(const double *__restrict__ gv, const double *__restrict__ gp,
+                                                        const int64_t *__restrict__ gt,
+                                                        const uint8_t *__restrict__ skip, uint64_t first,
+                                                        uint64_t count, int64_t exp_lt,
+                                                        const unsigned long long *__restrict__ tile_at,
+                                                        uint64_t capacity, uint64_t *__restrict__ ids,
+                                                        double *__restrict__ v, double *__restrict__ p,
+                                                        int64_t *__restrict__ t_us) {
+    __shared__ uint32_t cnt[kLiveItems * kWaves];
+    const uint64_t at = tile_at[blockIdx.x];
+    if (at >= capacity) return;   // (the whole workgroup: nothing of this tile fits)
+    const uint64_t base = (uint64_t)blockIdx.x * kLiveTile;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int64_t t[kLiveItems];
+    bool live[kLiveItems];
+    uint32_t rank[kLiveItems];
+#pragma unroll
+    for (int k = 0; k < kLiveItems; ++k) {
+        const uint64_t i = base + (uint64_t)k * kBlock + threadIdx.x;
+        live[k] = i < count && arow_out(gt, skip, first, i, exp_lt, t[k]);
+        const uint64_t bal = __ballot(live[k]);
+        rank[k] = (uint32_t)__popcll(bal & lanemask_lt());
+        if (lane == 0) cnt[k * kWaves + w] = (uint32_t)__popcll(bal);
+    }
+    __syncthreads();
+    uint32_t run = 0;
+#pragma unroll
+    for (int k = 0; k < kLiveItems; ++k) {
+#pragma unroll
+        for (int w2 = 0; w2 < kWaves; ++w2) {
+            if (w2 == w && live[k]) {
+                const uint64_t pos = at + run + rank[k];
+                if (pos < capacity) {
+                    const uint64_t key = first + base + (uint64_t)k * kBlock + threadIdx.x;
+                    ids[pos] = key;
+                    v[pos] = ld_nt(gv + key);   // only the exported rows' v and p are read
+                    p[pos] = ld_nt(gp + key);
+                    t_us[pos] = t[k];
+                }
+            }
+            run += cnt[k * kWaves + w2];
+        }
+    }
+}
+
+// Import by id after k_rows_check: nothing is written when any row was invalid.
+__global__ void k_arows_write(double *__restrict__ gv, double *__restrict__ gp, int64_t *__restrict__ gt,
+                              const uint64_t *__restrict__ ids, const double *__restrict__ v,
+                              const double *__restrict__ p, const int64_t *__restrict__ t_us, uint64_t n,
+                              const uint32_t *__restrict__ bad, uint32_t *__restrict__ sticky) {
+    if (*bad) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) *sticky = 1u;
+        return;
+    }
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int64_t t = t_us[i];
+        const uint64_t k = ids[i];
+        gv[k] = t == kAbsent ? 0.0 : v[i];
+        gp[k] = t == kAbsent ? 0.0 : p[i];
+        gt[k] = t;
+    }
+}
+
 // ----------------------------------------------------------------------------- host side
 enum Stage { ST_HIST = 0, ST_COLSCAN, ST_SCATTER, ST_BOUNDS, ST_FOLD, ST_UNSCATTER, ST_HOT, ST_COUNT };
 
@@ -5948,6 +6101,219 @@ tbe_status tbe_approx_import_state(tbe_engine *e, uint64_t first, uint64_t count
     HIP_TRY(e, hipMemcpy(e->gv + first, tv.data(), count * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(e, hipMemcpy(e->gp + first, tp.data(), count * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(e, hipMemcpy(e->gt + first, t_us, count * sizeof(int64_t), hipMemcpyHostToDevice));
+    return TBE_OK;
+}
+
+// ---- approximate kind: idle scan, reset, portable snapshots.  Stream ordering is
+// tbe_expired_device's throughout: the kernels run on the engine's stream (where every sync
+// runs), a caller's stream is joined before and after.
+static tbe_status approx_range_args(tbe_engine *e, uint64_t first, uint64_t count) {
+    if (e->cfg.kind != TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, "not an approximate engine");
+    if (first > e->cfg.n_keys || count > e->cfg.n_keys - first)
+        return fail(e, TBE_EINVAL, "range out of bounds");
+    return TBE_OK;
+}
+static tbe_status join_in(tbe_engine *e, hipStream_t caller) {
+    if (caller && caller != e->stream) {
+        HIP_TRY(e, hipEventRecord(e->ev_in, caller));
+        HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_in, 0));
+    }
+    return TBE_OK;
+}
+static tbe_status join_out(tbe_engine *e, hipStream_t caller) {
+    if (caller && caller != e->stream) {
+        HIP_TRY(e, hipEventRecord(e->ev_out, e->stream));
+        HIP_TRY(e, hipStreamWaitEvent(caller, e->ev_out, 0));
+    }
+    return TBE_OK;
+}
+
+tbe_status tbe_approx_idle_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, uint8_t *d_idle,
+                                  void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (tbe_status rc = approx_range_args(e, first, count); rc != TBE_OK) return rc;
+    if (ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+    if (count == 0) return TBE_OK;
+    if (!d_idle) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    hipStream_t caller = (hipStream_t)stream;
+    if (tbe_status rc = join_in(e, caller); rc != TBE_OK) return rc;
+    const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
+    k_approx_idle<<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient_lazy ? nullptr : e->aclient, e->gv, e->gt,
+                                                    first, count, ts_us, e->ap.decay_rate, d_idle);
+    HIP_TRY(e, hipGetLastError());
+    return join_out(e, caller);
+}
+
+tbe_status tbe_approx_reset_device(tbe_engine *e, uint64_t first, uint64_t count, const uint8_t *d_flags,
+                                   void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (tbe_status rc = approx_range_args(e, first, count); rc != TBE_OK) return rc;
+    if (count == 0) return TBE_OK;
+    if (!d_flags) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    hipStream_t caller = (hipStream_t)stream;
+    if (tbe_status rc = join_in(e, caller); rc != TBE_OK) return rc;
+    // a derived view of a reset row would read est = inf (P / 0) where a new limiter has 1:
+    // write every view the last one-client sync left to be derived, then reset
+    if (tbe_status rc = materialise_aclient(e, e->stream); rc != TBE_OK) return rc;
+    const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
+    k_approx_reset<<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient, e->gv, e->gp, e->gt, first, count, d_flags,
+                                                     e->ap.token_limit);
+    HIP_TRY(e, hipGetLastError());
+    e->queued_exact = false;   // a flagged key's queue, if it had one, is gone: queued_total is a bound
+    return join_out(e, caller);
+}
+
+tbe_status tbe_approx_idle(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, uint8_t *idle) {
+    if (!e) return TBE_EINVAL;
+    if (tbe_status rc = approx_range_args(e, first, count); rc != TBE_OK) return rc;
+    if (ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+    if (count == 0) return TBE_OK;
+    if (!idle) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch, whatever its stream
+    void *buf = nullptr;
+    HIP_TRY(e, hipMalloc(&buf, count));
+    tbe_status rc = tbe_approx_idle_device(e, ts_us, first, count, static_cast<uint8_t *>(buf), nullptr);
+    hipError_t hrc = hipSuccess;
+    if (rc == TBE_OK) hrc = hipMemcpyAsync(idle, buf, count, hipMemcpyDeviceToHost, e->stream);
+    if (rc == TBE_OK && hrc == hipSuccess) hrc = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
+    return TBE_OK;
+}
+
+tbe_status tbe_approx_reset(tbe_engine *e, uint64_t first, uint64_t count, const uint8_t *flags) {
+    if (!e) return TBE_EINVAL;
+    if (tbe_status rc = approx_range_args(e, first, count); rc != TBE_OK) return rc;
+    if (count == 0) return TBE_OK;
+    if (!flags) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());
+    void *buf = nullptr;
+    HIP_TRY(e, hipMalloc(&buf, count));
+    hipError_t hrc = hipMemcpy(buf, flags, count, hipMemcpyHostToDevice);
+    tbe_status rc = TBE_OK;
+    if (hrc == hipSuccess) rc = tbe_approx_reset_device(e, first, count, static_cast<const uint8_t *>(buf), nullptr);
+    if (hrc == hipSuccess && rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
+    return TBE_OK;
+}
+
+tbe_status tbe_approx_export_live_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count,
+                                         const uint8_t *d_skip, uint64_t *d_ids, double *d_v, double *d_p,
+                                         int64_t *d_t_us, uint64_t capacity, uint64_t *d_n_live, void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (tbe_status rc = approx_range_args(e, first, count); rc != TBE_OK) return rc;
+    if (!d_n_live || (capacity && (!d_ids || !d_v || !d_p || !d_t_us))) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (!e->live_tiles)
+        HIP_TRY(e, hipMalloc(&e->live_tiles,
+                             ((e->cfg.n_keys + kLiveTile - 1) / kLiveTile) * sizeof(unsigned long long)));
+    hipStream_t st = e->stream, caller = (hipStream_t)stream;
+    if (tbe_status rc = join_in(e, caller); rc != TBE_OK) return rc;
+    if (count == 0) {
+        HIP_TRY(e, hipMemsetAsync(d_n_live, 0, sizeof(uint64_t), st));
+    } else {
+        const int64_t exp_lt = ts_us < 0 ? kAbsent : (ts_us / 1000 - kApproxTtlMs) * 1000;   // < 0: no row lapses
+        const uint64_t ntiles = (count + kLiveTile - 1) / kLiveTile;
+        k_alive_count<<<(unsigned)ntiles, kBlock, 0, st>>>(e->gt, d_skip, first, count, exp_lt, e->live_tiles);
+        k_live_scan<<<1, kLiveScan, 0, st>>>(e->live_tiles, ntiles, reinterpret_cast<unsigned long long *>(d_n_live));
+        if (capacity)
+            k_alive_write<<<(unsigned)ntiles, kBlock, 0, st>>>(e->gv, e->gp, e->gt, d_skip, first, count, exp_lt,
+                                                               e->live_tiles, capacity, d_ids, d_v, d_p, d_t_us);
+        HIP_TRY(e, hipGetLastError());
+    }
+    return join_out(e, caller);
+}
+
+tbe_status tbe_approx_export_live(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, const uint8_t *skip,
+                                  uint64_t *ids, double *v, double *p, int64_t *t_us, uint64_t capacity,
+                                  uint64_t *n_live) {
+    if (!e || !n_live) return TBE_EINVAL;
+    if (tbe_status rc = approx_range_args(e, first, count); rc != TBE_OK) return rc;
+    if (capacity && (!ids || !v || !p || !t_us)) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch and sync, whatever its stream
+    const uint64_t cap = std::min(capacity, count);   // no more rows than the range holds
+    void *buf = nullptr;
+    HIP_TRY(e, hipMalloc(&buf, 8 + cap * 32 + (skip ? count : 0)));
+    uint64_t *d_n = static_cast<uint64_t *>(buf), *d_ids = d_n + 1;
+    double *d_v = reinterpret_cast<double *>(d_ids + cap), *d_p = d_v + cap;
+    int64_t *d_t = reinterpret_cast<int64_t *>(d_p + cap);
+    uint8_t *d_skip = skip ? reinterpret_cast<uint8_t *>(d_t + cap) : nullptr;
+    hipError_t hrc = skip && count ? hipMemcpy(d_skip, skip, count, hipMemcpyHostToDevice) : hipSuccess;
+    tbe_status rc = TBE_OK;
+    if (hrc == hipSuccess)
+        rc = tbe_approx_export_live_device(e, ts_us, first, count, d_skip, cap ? d_ids : nullptr, cap ? d_v : nullptr,
+                                           cap ? d_p : nullptr, cap ? d_t : nullptr, cap, d_n, nullptr);
+    if (rc == TBE_OK && hrc == hipSuccess) {
+        hrc = hipMemcpyAsync(n_live, d_n, sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream);
+        if (hrc == hipSuccess) hrc = hipStreamSynchronize(e->stream);
+        const uint64_t m = hrc == hipSuccess ? std::min<uint64_t>(*n_live, cap) : 0;
+        if (m && hrc == hipSuccess) hrc = hipMemcpy(ids, d_ids, m * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        if (m && hrc == hipSuccess) hrc = hipMemcpy(v, d_v, m * sizeof(double), hipMemcpyDeviceToHost);
+        if (m && hrc == hipSuccess) hrc = hipMemcpy(p, d_p, m * sizeof(double), hipMemcpyDeviceToHost);
+        if (m && hrc == hipSuccess) hrc = hipMemcpy(t_us, d_t, m * sizeof(int64_t), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
+    return TBE_OK;
+}
+
+tbe_status tbe_approx_import_rows_device(tbe_engine *e, const uint64_t *d_ids, const double *d_v, const double *d_p,
+                                         const int64_t *d_t_us, uint64_t n, void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, "not an approximate engine");
+    if (n == 0) return TBE_OK;
+    if (!d_ids || !d_v || !d_p || !d_t_us) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (!e->rows_bad) HIP_TRY(e, hipMalloc(&e->rows_bad, sizeof(uint32_t)));
+    hipStream_t st = e->stream, caller = (hipStream_t)stream;
+    if (tbe_status rc = join_in(e, caller); rc != TBE_OK) return rc;
+    // the client views still follow from the tier rows this import overwrites: write them
+    if (tbe_status rc = materialise_aclient(e, st); rc != TBE_OK) return rc;
+    HIP_TRY(e, hipMemsetAsync(e->rows_bad, 0, sizeof(uint32_t), st));
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192);
+    // the validating pass ends before the first row is written (one stream)
+    k_rows_check<<<blocks, kBlock, 0, st>>>(d_ids, d_t_us, n, e->cfg.n_keys, e->rows_bad);
+    k_arows_write<<<blocks, kBlock, 0, st>>>(e->gv, e->gp, e->gt, d_ids, d_v, d_p, d_t_us, n, e->rows_bad, e->sticky);
+    HIP_TRY(e, hipGetLastError());
+    return join_out(e, caller);
+}
+
+tbe_status tbe_approx_import_rows(tbe_engine *e, const uint64_t *ids, const double *v, const double *p,
+                                  const int64_t *t_us, uint64_t n) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, "not an approximate engine");
+    if (n == 0) return TBE_OK;
+    if (!ids || !v || !p || !t_us) return fail(e, TBE_EINVAL, "null buffer");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (ids[i] >= e->cfg.n_keys) return fail(e, TBE_EINVAL, "id out of range");
+        if (t_us[i] != kAbsent && t_us[i] < 0) return fail(e, TBE_EINVAL, "t_us < 0");
+    }
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch and sync, whatever its stream
+    void *buf = nullptr;
+    HIP_TRY(e, hipMalloc(&buf, n * 32));
+    uint64_t *d_ids = static_cast<uint64_t *>(buf);
+    double *d_v = reinterpret_cast<double *>(d_ids + n), *d_p = d_v + n;
+    int64_t *d_t = reinterpret_cast<int64_t *>(d_p + n);
+    hipError_t hrc = hipMemcpy(d_ids, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (hrc == hipSuccess) hrc = hipMemcpy(d_v, v, n * sizeof(double), hipMemcpyHostToDevice);
+    if (hrc == hipSuccess) hrc = hipMemcpy(d_p, p, n * sizeof(double), hipMemcpyHostToDevice);
+    if (hrc == hipSuccess) hrc = hipMemcpy(d_t, t_us, n * sizeof(int64_t), hipMemcpyHostToDevice);
+    tbe_status rc = TBE_OK;
+    if (hrc == hipSuccess) rc = tbe_approx_import_rows_device(e, d_ids, d_v, d_p, d_t, n, nullptr);
+    if (hrc == hipSuccess && rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
     return TBE_OK;
 }
 

@@ -520,6 +520,82 @@ class ApproximateEngine(QueueingTokenBucketEngine):
         self._check(self._lib.tbe_approx_import_state(self.handle, first, v.shape[0], v.ctypes.data,
                                                       p.ctypes.data, t_us.ctypes.data))
 
+    # ------------------------------------------------------------------ idle keys, snapshots
+    def idle_device(self, ts_us: int, d_idle, first: int = 0, stream: Optional[int] = None) -> None:
+        """d_idle (uint8 device tensor): d_idle[k - first] = 1 for every key of [first, first +
+        len) that is idle at ts_us -- nothing queued, ConsumedTokens == 0 and a tier row worth
+        no tokens (tbe_approx_idle_device; ``snapshot.approx_idle_rows`` states the rule).
+        Enqueued, not synchronised; stream as in ``acquire_batch_device``."""
+        self._check(self._lib.tbe_approx_idle_device(self.handle, ts_us, first, d_idle.numel(), d_idle.data_ptr(),
+                                                     stream))
+
+    def reset_device(self, d_flags, first: int = 0, stream: Optional[int] = None) -> None:
+        """Every key k of [first, first + len) with d_flags[k - first] != 0 (uint8 device
+        tensor) gets the state of a new engine (tbe_approx_reset_device).  Enqueued."""
+        self._check(self._lib.tbe_approx_reset_device(self.handle, first, d_flags.numel(), d_flags.data_ptr(),
+                                                      stream))
+
+    def export_live_device(self, ts_us: int, d_ids, d_v, d_t_us, d_n_live, first: int = 0,
+                           count: Optional[int] = None, capacity: Optional[int] = None,
+                           stream: Optional[int] = None, d_p=None, d_skip=None, tier: bool = False) -> None:
+        """One tbe_approx_export_live_device call: the {v, p, t} tier rows that are present and
+        not lapsed at ts_us, minus those with a non-zero byte in d_skip (uint8, one per key of
+        the range), into int64 ids, float64 v and p, int64 t_us and a one-element int64 count.
+        Selected by d_p (or, for a counting call without buffers, tier=True); without either
+        this is the token-bucket entry point, which refuses an approximate engine (tbe.h)."""
+        if d_p is None and d_skip is None and not tier:
+            return super().export_live_device(ts_us, d_ids, d_v, d_t_us, d_n_live, first, count, capacity, stream)
+        if count is None:
+            count = self.n_keys - first
+        if capacity is None:
+            capacity = 0 if d_ids is None else d_ids.numel()
+        if capacity and min(d_ids.numel(), d_v.numel(), d_p.numel(), d_t_us.numel()) < capacity:
+            raise ValueError("capacity exceeds the output tensors")
+        if d_skip is not None and (d_skip.numel() != count or d_skip.element_size() != 1):
+            raise ValueError("d_skip must hold one byte per key of the range")
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        self._check(self._lib.tbe_approx_export_live_device(self.handle, ts_us, first, count, ptr(d_skip), ptr(d_ids),
+                                                            ptr(d_v), ptr(d_p), ptr(d_t_us), capacity,
+                                                            d_n_live.data_ptr(), stream))
+
+    def export_live(self, ts_us: int, first: int = 0, count: Optional[int] = None, stream: Optional[int] = None,
+                    d_skip=None):
+        """The exported tier rows of [first, first + count) as (ids int64, v, p float64, t_us
+        int64) device tensors, ascending ids: a counting call, one read-back of the count,
+        then the filling call (as ``TokenBucketEngine.export_live``)."""
+        import torch
+        if count is None:
+            count = self.n_keys - first
+        dev = torch.device("cuda", self.config.device if self.config.device >= 0 else torch.cuda.current_device())
+        d_n = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.export_live_device(ts_us, None, None, None, d_n, first, count, 0, stream, d_skip=d_skip, tier=True)
+        torch.cuda.synchronize(dev)
+        n = int(d_n.item())
+        d_ids = torch.empty(n, dtype=torch.int64, device=dev)
+        d_v = torch.empty(n, dtype=torch.float64, device=dev)
+        d_p = torch.empty(n, dtype=torch.float64, device=dev)
+        d_t = torch.empty(n, dtype=torch.int64, device=dev)
+        if n:
+            self.export_live_device(ts_us, d_ids, d_v, d_t, d_n, first, count, n, stream, d_p=d_p, d_skip=d_skip)
+            if not stream:
+                torch.cuda.synchronize(dev)
+        return d_ids, d_v, d_p, d_t
+
+    def import_rows(self, d_ids, d_v, d_t_us, stream: Optional[int] = None, d_p=None) -> None:
+        """tier[d_ids[i]] = {d_v[i], d_p[i], d_t_us[i]} from device tensors
+        (tbe_approx_import_rows_device); enqueued, an invalid row voids the call and raises at
+        ``synchronize()``.  Without d_p this is the token-bucket entry point, which refuses an
+        approximate engine (tbe.h)."""
+        if d_p is None:
+            return super().import_rows(d_ids, d_v, d_t_us, stream)
+        n = d_ids.numel()
+        if d_v.numel() != n or d_p.numel() != n or d_t_us.numel() != n:
+            raise ValueError("d_ids, d_v, d_p and d_t_us must have the same length")
+        d_ids, d_v, d_p, d_t_us = d_ids.contiguous(), d_v.contiguous(), d_p.contiguous(), d_t_us.contiguous()
+        self._check(self._lib.tbe_approx_import_rows_device(self.handle, d_ids.data_ptr(), d_v.data_ptr(),
+                                                            d_p.data_ptr(), d_t_us.data_ptr(), n, stream))
+        self._rows_in_flight = (d_ids, d_v, d_p, d_t_us)   # read by the enqueued kernels
+
     def local_state(self, key: int):
         """(local, global, est, available, queued) of one key."""
         lo, gl, av = c_int32(), c_int32(), c_int32()

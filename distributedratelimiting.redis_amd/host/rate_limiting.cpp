@@ -194,12 +194,15 @@ public:
     // the enqueue happen under a shared lock that the reclaim takes exclusively, and keys
     // with requests still in the submitter's queue are kept, so no request of an old
     // string can land on a reassigned key.
-    std::future<RateLimitLease> SubmitResource(const std::string &resource, int32_t permits, int mode) {
+    // Approximate kind: the keys reclaimed are the idle ones (tbe_approx_idle: nothing
+    // queued, ConsumedTokens == 0, a tier row worth no tokens), reset to a new limiter's state.
+    std::future<RateLimitLease> SubmitResource(const std::string &resource, int32_t permits, int mode,
+                                               const CancellationToken &ct = {}) {
         for (int attempt = 0;; ++attempt) {
             {
                 std::shared_lock<std::shared_mutex> g(reclaim_mu_);
                 uint64_t k;
-                if (TryKeyOf(resource, k)) return Submit(k, permits, mode);
+                if (TryKeyOf(resource, k)) return Submit(k, permits, mode, ct);
             }
             if (attempt)
                 throw RateLimiterEngineException(TBE_ERANGE, "PartitionLimit reached: no key left for '" +
@@ -228,7 +231,26 @@ public:
         }
         names_[key] = bucket;
         dir_.emplace(bucket, key);
+        if (kind_ == TBE_KIND_APPROXIMATE) fresh_keys_.push_back(key);
         return true;
+    }
+
+    // Approximate kind, submitter thread, before a batch: every key a name took since the
+    // last batch is reset, so the name starts as a newly constructed limiter over an absent
+    // Redis key whatever refreshes passed over the key while no name held it (a refresh
+    // syncs every key and leaves an unheld one a row with a period estimate).
+    void ResetFreshKeys() {
+        std::vector<uint64_t> keys;
+        {
+            std::lock_guard<std::mutex> g(dir_mu_);
+            keys.swap(fresh_keys_);
+        }
+        if (keys.empty()) return;
+        const auto mm = std::minmax_element(keys.begin(), keys.end());
+        const uint64_t first = *mm.first, count = *mm.second - first + 1;
+        std::vector<uint8_t> flags(count, 0);
+        for (uint64_t k : keys) flags[k - first] = 1;
+        Check(tbe_approx_reset(eng_, first, count, flags.data()));
     }
 
     // Submitter thread (so every request enqueued before it has been decided).
@@ -243,6 +265,7 @@ public:
         std::lock_guard<std::mutex> g(dir_mu_);
         const uint64_t n = names_.size();
         if (n == 0) return 0;
+        if (kind_ == TBE_KIND_APPROXIMATE) return ReclaimIdle(n, busy);
         // TB:234: EXPIRE ceil(min(max(capacity / fill_rate, 1), 31536000)) seconds; the
         // engine's expiry test is tbe_query's (millisecond resolution).
         double q = (double)opt_.TokenLimit / opt_.FillRatePerSecond();
@@ -279,6 +302,38 @@ public:
             }
             // this thread is the engine's only submitter: the other rows go back unchanged
             if (cleared) Check(tbe_import_state(eng_, k0, m, v.data(), t.data()));
+        }
+        reclaimed_ += freed;
+        return freed;
+    }
+
+    // The approximate branch of Reclaim (reclaim_mu_ and dir_mu_ held, submitter thread): the
+    // engine says which keys are idle now; the free ones and those with requests still in
+    // the submitter's queue keep their flag clear; the rest lose their name and are reset.
+    // A queued wait keeps its key by the idle rule itself.
+    uint64_t ReclaimIdle(uint64_t n, const std::unordered_set<uint64_t> &busy) {
+        const int64_t now = clock_();
+        std::vector<uint8_t> is_free(n, 0);
+        for (uint64_t k : free_ids_) is_free[k] = 1;
+        uint64_t freed = 0;
+        constexpr uint64_t kChunk = 1u << 20;
+        std::vector<uint8_t> flags(std::min(n, kChunk));
+        for (uint64_t k0 = 0; k0 < n; k0 += kChunk) {
+            const uint64_t m = std::min(kChunk, n - k0);
+            Check(tbe_approx_idle(eng_, now, k0, m, flags.data()));
+            bool any = false;
+            for (uint64_t j = 0; j < m; ++j) {
+                const uint64_t k = k0 + j;
+                if (is_free[k] || busy.count(k)) flags[j] = 0;
+                if (!flags[j]) continue;
+                dir_.erase(names_[k]);
+                names_[k].clear();
+                last_reply_.erase(k);
+                free_ids_.push_back(k);
+                any = true;
+                ++freed;
+            }
+            if (any) Check(tbe_approx_reset(eng_, k0, m, flags.data()));
         }
         reclaimed_ += freed;
         return freed;
@@ -546,6 +601,7 @@ private:
             }
             lk.unlock();
             try {
+                if (kind_ == TBE_KIND_APPROXIMATE && partitioned_) ResetFreshKeys();
                 RunBatch(mode, batch);
             } catch (...) {  // engine error: every caller of the batch sees it (TB:63 propagation)
                 for (auto &r : batch) {
@@ -681,6 +737,7 @@ private:
     std::unordered_map<std::string, uint64_t> dir_;
     std::vector<std::string> names_;       // key -> bucket string
     std::vector<uint64_t> free_ids_;       // reclaimed keys, reused first
+    std::vector<uint64_t> fresh_keys_;     // approximate kind: keys assigned since the last batch
     std::shared_mutex reclaim_mu_;
     std::atomic<uint64_t> reclaimed_{0};
     std::unordered_map<uint64_t, int32_t> last_reply_;
@@ -829,6 +886,43 @@ std::future<RateLimitLease> RedisApproximateTokenBucketRateLimiter::AcquireAsync
     return core_->Submit(0, p, kApproxWait, ct);
 }
 void RedisApproximateTokenBucketRateLimiter::DisposeCore() { core_->Dispose(); }
+
+// ------------------------------------------------------------------ partitioned approximate
+PartitionedRedisApproximateTokenBucketRateLimiter::PartitionedRedisApproximateTokenBucketRateLimiter(
+    const RedisApproximateTokenBucketRateLimiterOptions &o)
+    : core_(std::make_unique<LimiterCore>(TBE_KIND_APPROXIMATE, o, true,
+                                          "PartitionedRedisApproximateTokenBucketRateLimiter")) {}
+PartitionedRedisApproximateTokenBucketRateLimiter::~PartitionedRedisApproximateTokenBucketRateLimiter() = default;
+int PartitionedRedisApproximateTokenBucketRateLimiter::GetAvailablePermits(const std::string &id) {
+    core_->ThrowIfDisposed();
+    // on the submitter thread, where reclaims run: the name cannot lose its key in between
+    return core_->Run([this, &id] {
+        uint64_t k;
+        return core_->KnownKey(id, k) ? core_->QueryApprox(k).available : core_->options().TokenLimit;
+    });
+}
+bool PartitionedRedisApproximateTokenBucketRateLimiter::TryReplenish() {
+    if (core_->options().AutoReplenishment) return false;
+    core_->ThrowIfDisposed();
+    core_->Run([this] { core_->RefreshNow(); });
+    return true;
+}
+uint64_t PartitionedRedisApproximateTokenBucketRateLimiter::ReclaimIdle() {
+    core_->ThrowIfDisposed();
+    return core_->Run([this] { return core_->Reclaim(); });
+}
+RateLimitLease PartitionedRedisApproximateTokenBucketRateLimiter::AttemptAcquireCore(const std::string &id, int p) {
+    check_limit(p, core_->options().TokenLimit);
+    core_->ThrowIfDisposed();
+    return core_->SubmitResource(id, p, kApproxAttempt).get();
+}
+std::future<RateLimitLease> PartitionedRedisApproximateTokenBucketRateLimiter::AcquireAsyncCore(
+    const std::string &id, int p, const CancellationToken &ct) {
+    check_limit(p, core_->options().TokenLimit);
+    core_->ThrowIfDisposed();  // A:124
+    return core_->SubmitResource(id, p, kApproxWait, ct);
+}
+void PartitionedRedisApproximateTokenBucketRateLimiter::DisposeCore() { core_->Dispose(); }
 
 // ------------------------------------------------------------------ registration
 ServiceCollection &ServiceCollection::AddRedisTokenBucketRateLimiter(

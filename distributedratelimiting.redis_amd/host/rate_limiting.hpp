@@ -14,6 +14,7 @@
 //   PartitionedRedisTokenBucketRateLimiter TokenBucket/PartitionedRedisTokenBucketRateLimiter.cs:7-212
 //   RedisQueueingTokenBucketRateLimiter    TokenBucketWithQueue/RedisTokenBucketRateLimiter.cs:9-400
 //   RedisApproximateTokenBucketRateLimiter ApproximateTokenBucket/RedisApproximateTokenBucketRateLimiter.cs:9-599
+//   PartitionedRedisApproximateTokenBucketRateLimiter   the reference README's second TODO (no file upstream)
 //   *Options                               */Redis*Options.cs (TBO:9-85, QO, AO)
 //   ServiceCollection::AddRedis*           ServiceCollectionExtensions.cs:10-26
 // Method names follow the GA System.Threading.RateLimiting API (AttemptAcquire /
@@ -299,6 +300,33 @@ protected:
     RateLimitLease AttemptAcquireCore(int permitCount) override;                     // A:84-113
     std::future<RateLimitLease> AcquireAsyncCore(int permitCount, const CancellationToken &ct) override;          // A:116-183
     void DisposeCore() override;                                                      // A:274-300
+private:
+    std::unique_ptr<detail::LimiterCore> core_;
+};
+
+// The partitioned approximate limiter the reference's README lists as still to do: one
+// approximate limiter per resourceID (BucketId = InstanceName + resourceID, as PTB:42), all
+// of them in one engine.  Each name has its own local tier, queue and global-tier row; one
+// TryReplenish (or timer tick) is one RefreshAsync (A:412-508) of every name.  Failed leases
+// carry RetryAfter (A:390-395).  When all PartitionLimit keys are taken the idle names --
+// nothing queued, ConsumedTokens == 0 (A:36, A:503-506) and a global row worth no tokens
+// now -- give their keys back (ReclaimIdle, which also runs by itself), and a name that
+// takes a reused key starts as a newly constructed limiter does (tbe_approx_reset, tbe.h).
+class PartitionedRedisApproximateTokenBucketRateLimiter final : public PartitionedRateLimiter<std::string> {
+public:
+    explicit PartitionedRedisApproximateTokenBucketRateLimiter(
+        const RedisApproximateTokenBucketRateLimiterOptions &options);
+    ~PartitionedRedisApproximateTokenBucketRateLimiter() override;
+    // A:81 for a name that holds a key; TokenLimit for one that does not (what its limiter
+    // would report once constructed), without assigning a key.
+    int GetAvailablePermits(const std::string &resourceID) override;
+    bool TryReplenish();  // one RefreshAsync of every name now; false when AutoReplenishment is on
+    uint64_t ReclaimIdle();  // frees the keys of idle names; returns the number freed
+protected:
+    RateLimitLease AttemptAcquireCore(const std::string &resourceID, int permitCount) override;   // A:84-113
+    std::future<RateLimitLease> AcquireAsyncCore(const std::string &resourceID, int permitCount,
+                                                 const CancellationToken &ct) override;           // A:116-183
+    void DisposeCore() override;
 private:
     std::unique_ptr<detail::LimiterCore> core_;
 };

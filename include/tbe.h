@@ -444,6 +444,68 @@ tbe_status tbe_approx_export_state(tbe_engine *engine, uint64_t first, uint64_t 
 tbe_status tbe_approx_import_state(tbe_engine *engine, uint64_t first, uint64_t count, const double *v,
                                    const double *p, const int64_t *t_us);
 
+/* Which keys of [first, first + count) an approximate engine could hand to another name
+ * (DESIGN.md §2c).  The tier rows never lapse while the engine runs -- every sync rewrites
+ * every key's row -- so the rule is not tbe_expired_device's.  d_idle (device memory, count
+ * bytes) gets d_idle[k - first] = 1 when all of these hold, else 0:
+ *   1. nothing is queued on the key, zero-permit registrations included;
+ *   2. ConsumedTokens == 0, the reference's own idle test (A:36, A:503-506):
+ *      (int32)((uint32)_globalThrottleScore + (uint32)_localThrottleScore) == 0, the global
+ *      score being the client view tbe_approx_query reports;
+ *   3. the tier row hands a client that syncs at ts_us nothing: it is absent, or lapsed by
+ *      the sync's own test (t_us < 1000 * (ts_us / 1000 - 86 400 000)), or
+ *      max(0, v - max(0, new_t(ts_us) - new_t(t_us)) * decay_rate) == 0 with the sync
+ *      script's operations in its order (A:255-258), no contraction.
+ * Ordered after every batch and sync already enqueued on the engine; `stream` as in
+ * tbe_expired_device.  ts_us < 0, a range past n_keys or another kind of engine: TBE_EINVAL,
+ * nothing written.  On a replicated tier every client scans and the flags are combined (a
+ * key is idle only where every client says so) before anything is reset, which is why scan
+ * and reset are two calls. */
+tbe_status tbe_approx_idle_device(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                                  uint8_t *d_idle, void *stream);
+/* Every key k of the range with d_flags[k - first] != 0 gets the state of a new engine:
+ * local tier {cap TokenLimit, local 0, empty queue}, client view {est 1, global 0}, tier
+ * row absent (v = p = 0).  A reused id is then what the reference has for a new resourceID:
+ * a freshly constructed limiter over an absent Redis key, the estimator's warm-up included.
+ * Unflagged rows are not written.  After a one-client sync the client views of all keys are
+ * first written (as tbe_approx_import_state does).  Ordering, `stream` and argument checks
+ * as above.
+ * Known departure: a name that is reclaimed and returns within a day finds, in the
+ * reference, its old row -- worth 0 tokens by rule 3 -- with its old period estimate p;
+ * here it finds the script's absent default (A:247-252), as the reference does after its
+ * own EXPIRE or a Redis flush.  Only the estimator's warm-up differs. */
+tbe_status tbe_approx_reset_device(tbe_engine *engine, uint64_t first, uint64_t count,
+                                   const uint8_t *d_flags, void *stream);
+/* The same with host buffers; synchronous. */
+tbe_status tbe_approx_idle(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count, uint8_t *idle);
+tbe_status tbe_approx_reset(tbe_engine *engine, uint64_t first, uint64_t count, const uint8_t *flags);
+
+/* Portable snapshots of the approximate kind's {v, p, t} tier, in the form
+ * of tbe_export_live_device / tbe_import_rows_device.  Export: a row of [first, first +
+ * count) is written when it is present, not lapsed at ts_us (one-day TTL, A:268; ts_us < 0
+ * skips the lapse test) and d_skip is NULL or d_skip[k - first] == 0 (device memory, count
+ * bytes: every synced id holds a row, so the caller masks with the idle flags or with "not
+ * held by the directory").  Rows are compacted in ascending id order; *d_n_live (device
+ * u64) gets their total; nothing at or past `capacity` is touched and capacity == 0 only
+ * counts.  Local tiers and client views are in-process state (A:36-40) and not part of it. */
+tbe_status tbe_approx_export_live_device(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                                         const uint8_t *d_skip, uint64_t *d_ids, double *d_v, double *d_p,
+                                         int64_t *d_t_us, uint64_t capacity, uint64_t *d_n_live, void *stream);
+/* The same with host buffers (skip included); synchronous. */
+tbe_status tbe_approx_export_live(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                                  const uint8_t *skip, uint64_t *ids, double *v, double *p, int64_t *t_us,
+                                  uint64_t capacity, uint64_t *n_live);
+/* Import by id: tier[d_ids[i]] = {d_v[i], d_p[i], d_t_us[i]}; t_us = INT64_MIN writes {0, 0,
+ * absent}.  Unique ids.  An id >= n_keys, or a t_us < 0 other than INT64_MIN, voids the
+ * whole call (every row is validated before any is written) and is reported by
+ * tbe_synchronize.  After a one-client sync the client views are first written, as in
+ * tbe_approx_import_state.  Every rank of a replicated tier imports every row. */
+tbe_status tbe_approx_import_rows_device(tbe_engine *engine, const uint64_t *d_ids, const double *d_v,
+                                         const double *d_p, const int64_t *d_t_us, uint64_t n, void *stream);
+/* The same from host buffers; synchronous, invalid rows: TBE_EINVAL, nothing written. */
+tbe_status tbe_approx_import_rows(tbe_engine *engine, const uint64_t *ids, const double *v, const double *p,
+                                  const int64_t *t_us, uint64_t n);
+
 /* How the engine lays a batch out (for reports and tests): *passes = 8-bit partition
  * passes over the bucket id, *r_bits = log2 of the keys per bucket (one workgroup
  * each), *packed: bit 0 set when the passes move packed 8-byte request records (token
