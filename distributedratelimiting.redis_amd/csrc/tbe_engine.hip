@@ -20,8 +20,10 @@
 //      (speculative rounds, LDS atomicMax election), so per-key order is the reference's
 //      serial order.  Dirty lines are written back once.  Sparse batches: k_fold_sparse
 //      (one wave per bucket); hot keys: their own runs (k_hot_*).
-//   4. k_unscatter: {granted, remaining} back in arrival order through pass 0's
-//      permutation (the fold already put each reply at its pass-0 output position).
+//   4. k_unpart_runs: {granted, remaining} back in arrival order, per partition tile: the
+//      tile's 256 digit runs of replies staged in LDS, indexed by pass 0's 2-byte tile-local
+//      permutation (the fold already put each reply at its pass-0 output position).  Other
+//      kinds and intermediate passes: k_unscatter, a gather through a 4-byte permutation.
 // DESIGN.md §5 describes every kernel.
 //
 // Memory-bound integer/byte work plus a little FP64; no MFMA.
@@ -84,7 +86,10 @@ constexpr int kPartBlock = TBE_PART_BLOCK;             // partition workgroup
 constexpr int kPartItems = TBE_PART_ITEMS;             // elements per thread per tile
 constexpr int kTile = kPartBlock * kPartItems;         // 4096 requests per partition tile
 // k_unscatter's own tiles (any size is correct; 8192 keeps each workgroup's gathers in
-// the digit runs of two partition tiles)
+// the digit runs of two partition tiles).  k_unscatter runs the intermediate un-partition
+// passes of every kind and the final one of the queueing and approximate kinds, of engines
+// without packed records and under TBE_UNPART_RUNS=0; the token-bucket kind's final pass
+// over packed records is k_unpart_runs (partition tiles), or k_unrank when re-ranking.
 #ifndef TBE_UN_BLOCK
 #define TBE_UN_BLOCK 1024
 #endif
@@ -221,7 +226,10 @@ __device__ __forceinline__ void hot_sortkeys(const KeyT (&kv)[N], const uint64_t
 // its run's partition key (hot_sortkey), as in k_scatter_rec<true, true>.
 //
 // 512 threads x 8 keys per tile, and the next tile's keys are loaded while this one is
-// counted (the loads, not the LDS counting, bound this kernel).
+// counted.  Under TBE_HIST_LOAD16 a lane takes four pairs of consecutive keys of a full tile
+// of 8-byte keys (a histogram does not care which lane counts which key), and everything
+// that names a request -- validation, dig_out, the last pass's tile_lo -- goes by the pair's
+// element index (elem()).
 constexpr int kHBlock = 512;
 constexpr int kHItems = kTile / kHBlock;              // 8
 #ifndef TBE_HIST_AHEAD
@@ -233,6 +241,14 @@ constexpr int kHItems = kTile / kHBlock;              // 8
 #ifndef TBE_HIST_HOT_WAVES
 #define TBE_HIST_HOT_WAVES 6
 #endif
+#ifndef TBE_HIST_LOAD16
+// 16-byte key loads in full tiles (1) or 8-byte loads (0).  Off: in config B the histogram took
+// 126.8 us with them against 130.1 us (parent) and 131.1 us (off), inside the 12-16 us spread of
+// each (profiles/r11_unpart_ab.txt), so its 8-byte non-temporal loads are not what bounds it;
+// kept for A/B (tools/ablate.py, set unpart)
+#define TBE_HIST_LOAD16 0
+#endif
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 template <typename KeyT, bool HOT = false>
 __global__ __launch_bounds__(kHBlock, HOT ? TBE_HIST_HOT_WAVES : TBE_HIST_WAVES) void k_hist(const KeyT *__restrict__ keys, uint64_t n,
                                                   int shift, uint32_t tiles_per_blk,
@@ -260,7 +276,29 @@ __global__ __launch_bounds__(kHBlock, HOT ? TBE_HIST_HOT_WAVES : TBE_HIST_WAVES)
 #if TBE_HIST_AHEAD >= 2
     KeyT kn2[kHItems];
 #endif
+    // 8-byte keys of a full tile, 16-byte aligned: a lane loads two consecutive keys at once
+    // (8-byte non-temporal loads run at about 2/3 of the 16-byte rate).  The batch's partial
+    // tile and an unaligned key array take the element-wise loads.
+    constexpr bool kLoad16 = TBE_HIST_LOAD16 && sizeof(KeyT) == 8;
+    const bool al16 = kLoad16 && (reinterpret_cast<uintptr_t>(keys) & 15u) == 0;
+    auto wide = [&](uint32_t t) { return al16 && t < t1 && ((uint64_t)t + 1) * kTile <= n; };
+    // tile element of this thread's item `it`: striped, or in pairs (slot it / 2, key it % 2)
+    auto elem = [&](bool w16, int it) {
+        return w16 ? (uint32_t)((((it >> 1) * kHBlock + tid) << 1) | (it & 1)) : (uint32_t)(it * kHBlock + tid);
+    };
     auto load_into = [&](KeyT (&dst)[kHItems], uint32_t t) {
+        if constexpr (kLoad16) {
+            if (wide(t)) {
+                const u64x2 *k2 = reinterpret_cast<const u64x2 *>(keys + (uint64_t)t * kTile);
+#pragma unroll
+                for (int s = 0; s < kHItems / 2; ++s) {
+                    const u64x2 v = LD_P(k2 + s * kHBlock + tid);
+                    dst[2 * s] = (KeyT)v.x;
+                    dst[2 * s + 1] = (KeyT)v.y;
+                }
+                return;
+            }
+        }
 #pragma unroll
         for (int it = 0; it < kHItems; ++it) {
             const uint64_t i = (uint64_t)t * kTile + it * kHBlock + tid;
@@ -286,6 +324,7 @@ __global__ __launch_bounds__(kHBlock, HOT ? TBE_HIST_HOT_WAVES : TBE_HIST_WAVES)
         for (int u = 0; u < 4; ++u) h8[u * kHBlock + tid] = 0;
         __syncthreads();
         const uint64_t base = (uint64_t)t * kTile;
+        const bool w16 = wide(t);                    // how this tile's keys were loaded
         const uint64_t last = min<uint64_t>(base + kTile, n) - 1;
         uint32_t skv[kHItems];
         if (HOT && any_hot) {
@@ -296,7 +335,7 @@ __global__ __launch_bounds__(kHBlock, HOT ? TBE_HIST_HOT_WAVES : TBE_HIST_WAVES)
         }
 #pragma unroll
         for (int it = 0; it < kHItems; ++it) {
-            const uint64_t i = base + it * kHBlock + tid;
+            const uint64_t i = base + elem(w16, it);
             const bool valid = i < n;
             const uint32_t sk = skv[it];
             const uint32_t d = (sk >> shift) & (kDigits - 1);
@@ -353,7 +392,7 @@ __global__ __launch_bounds__(kHBlock, HOT ? TBE_HIST_HOT_WAVES : TBE_HIST_WAVES)
                 __syncthreads();
 #pragma unroll
                 for (int it = 0; it < kHItems; ++it) {
-                    const uint64_t i = base + it * kHBlock + tid;
+                    const uint64_t i = base + elem(w16, it);
                     const uint32_t bk = skv[it] >> r_bits;
                     if (i < n) atomicAdd(&h8[((bk & ((1u << lowbits) - 1u)) - lo0) * kDigits + ((bk >> lowbits) & (kDigits - 1))], 1u);
                 }
@@ -368,7 +407,7 @@ __global__ __launch_bounds__(kHBlock, HOT ? TBE_HIST_HOT_WAVES : TBE_HIST_WAVES)
             } else {
 #pragma unroll
                 for (int it = 0; it < kHItems; ++it) {
-                    const uint64_t i = base + it * kHBlock + tid;
+                    const uint64_t i = base + elem(w16, it);
                     const uint32_t bk = skv[it] >> r_bits;
                     if (i < n && bk < nbt) atomicAdd(&bcount[bk], 1u);
                 }
@@ -1008,7 +1047,10 @@ __device__ __forceinline__ void fold_input_fam(uint64_t rec, uint32_t q, const F
 // The last pass's 45 KB of LDS let three workgroups share a CU; its FAM instances keep the
 // registers for that many waves per SIMD (at most 80 VGPRs at 512 threads)
 constexpr int kLastWaves = 3 * (kPartBlock / 64) / 4;
-template <bool FIRST, bool HOT = false, bool IDX = false, bool NOTS = false, bool LAST = false, int FAM = -1>
+// P16 (FIRST, TBE_UNPART_RUNS): the permutation entry is the request's tile-local sorted index
+// lpos (< kTile, 2 bytes) instead of its global position: k_unpart_runs stages the tile's digit
+// runs in LDS and indexes them with it.
+template <bool FIRST, bool HOT = false, bool IDX = false, bool NOTS = false, bool LAST = false, int FAM = -1, bool P16 = false>
 __global__ __launch_bounds__(kPartBlock, FIRST ? TBE_SCATTER0_WAVES : (FAM >= 0 ? kLastWaves : 1)) void k_scatter_rec(
     const uint64_t *__restrict__ kin, const int32_t *__restrict__ pin, const int64_t *__restrict__ tin,
     const uint64_t *__restrict__ rin, uint64_t n, int shift, PackFmt F,
@@ -1020,6 +1062,7 @@ __global__ __launch_bounds__(kPartBlock, FIRST ? TBE_SCATTER0_WAVES : (FAM >= 0 
     const uint8_t *__restrict__ din = nullptr, int64_t *__restrict__ ts0 = nullptr, Pass1Codec C = Pass1Codec{}) {
     static_assert(!(FIRST && LAST), "fold records come from a pass after the first");
     static_assert(FAM < 0 || LAST, "the record family is fixed only for the last pass");
+    static_assert(!P16 || FIRST, "tile-local permutation entries are pass 0's");
     // narrow pass-0 records (F.n0): FIRST writes u32 records (+ escaped times to ts0), LAST
     // reads them with the pass-1 digit from the digit stream `din`; the LDS stage then holds
     // record | digit(s) << 32, since the record no longer carries the key.  The queueing
@@ -1130,6 +1173,8 @@ __global__ __launch_bounds__(kPartBlock, FIRST ? TBE_SCATTER0_WAVES : (FAM >= 0 
                 stage[lpos[it]] = n0 ? (rec[it] & 0x0000FFFFFFFFFFFFull) : rec[it];
                 if (LAST)
                     stage_e[lpos[it]] = (uint16_t)e;
+                else if (P16)
+                    ST_PERM(reinterpret_cast<uint16_t *>(perm) + base + e, (uint16_t)lpos[it]);
                 else if (perm)   // (null: k_unrank recomputes the positions)
                     ST_PERM(perm + base + e, goff[d] + lpos[it] - L.lstart[d]);
                 if (FIRST && n0 && ((rec[it] >> 48) & 1u))   // escaped: its time beside its position
@@ -1864,6 +1909,11 @@ __device__ __forceinline__ uint32_t wait_status(uint32_t v) {
     return W == 1 ? v >> 6 : W == 2 ? v >> 14 : v >> 30;
 }
 
+// Un-partition by gather through a pass's 4-byte permutation: out[i] = in[perm[i]].  Every
+// lane of the gather sits in a 128-byte line of its own (consecutive requests carry independent
+// digits), which is what bounds it: about 64 vector-L1 accesses per wave instruction
+// (profiles/r11_unpart_floor.txt).  Launched for the intermediate passes (FINAL = false) and
+// for the final pass wherever k_unpart_runs / k_unrank do not apply (see kUnTile).
 // RETRY (approximate kind, tbe_approx_acquire_batch_retry): the 32-bit deficit of each
 // FAILED request travels with its reply -- def_out[i] = def_in[perm[i]] for the lanes whose
 // gathered status is FAILED -- and the final pass stores retry[i] in arrival order: the
@@ -1897,6 +1947,16 @@ __global__ __launch_bounds__(kUnBlock) void k_unscatter(uint64_t n, const uint32
 #pragma unroll
     for (int it = 0; it < kUnItems; ++it) {
         const int e = it * kUnBlock + tid;
+#ifdef TBE_UN_NO_GATHER
+        // timing only (WRONG replies; never in tests): the final pass reads the reply at its
+        // own position, so the permutation is still loaded but the gather is coalesced --
+        // the difference to the real kernel is what the divergent gathers cost
+        // (profiles/r11_unpart_floor.txt)
+        if (FINAL) {
+            asm volatile("" ::"v"(pv[it]));   // (the load stays live)
+            pv[it] = (uint32_t)(base + e);
+        }
+#endif
         r[it] = (e < nvalid) ? (W == 1 ? (uint32_t)reinterpret_cast<const uint8_t *>(res_in)[pv[it]]
                                 : W == 2 ? (uint32_t)reinterpret_cast<const uint16_t *>(res_in)[pv[it]]
                                          : res_in[pv[it]])
@@ -2026,6 +2086,165 @@ __global__ __launch_bounds__(kPartBlock) void k_unrank(uint64_t n, const uint8_t
         } else {
             ST_U(granted + i, (uint8_t)(r[it] >> 31));
             ST_U(remaining + i, (int32_t)(r[it] & 0x7FFFFFFFu));
+        }
+    }
+}
+
+// Final un-partition of the token-bucket kind through LDS-staged digit runs (TBE_UNPART_RUNS).
+// Pass 0 is a stable partition, so the replies of one partition tile are 256 contiguous runs,
+// one per digit, that start at the tile's offsets goff[d]; pass 0 (k_scatter_rec<.., P16>) left
+// each request's index into the tile in sorted order (its stage[] index, < kTile) as 2 bytes.
+// One workgroup per partition tile, numbered as in pass 0:
+//   1. goff[d] (tile_offsets) and the tile's count per digit: the next tile's running count
+//      minus this one's inside a histogram block, the block's total (from blockprefix /
+//      digit_total) minus it at a block's last tile; lstart = exclusive scan of the counts --
+//      the numbers rank_tile_wb left in pass 0's L.lstart;
+//   2. the digit of every load task: each non-empty digit writes d at its first task into a
+//      zeroed byte array, and a running maximum (blocked per thread, wave, workgroup) fills
+//      the rest (an empty digit shares its start with the next non-empty one and writes
+//      nothing).  Four-byte replies: a task is one staged reply.  One-byte replies: a task is
+//      one aligned dword of a run (at most kTile / 4 + 1.5 * 256 of them), because what bounds
+//      this kernel is the number of vector-memory instructions, and a one-byte load costs as
+//      much as a dword load (profiles/r11_unpart_floor.txt);
+//   3. the runs into LDS in staged order: consecutive tasks of a run are consecutive bytes,
+//      so a wave instruction covers a few runs where k_unscatter's gather has every lane in a
+//      line of its own;
+//   4. granted[i], remaining[i] = the staged reply at request i's 2-byte index, decoded as in
+//      k_unscatter<true, false, W>.  The tile's indices come in with one 16-byte load per lane
+//      and are turned to striped order through LDS.
+// Also k_unscatter's sticky-error duty.  Workgroup barriers only.  W: reply width (1 or 4 bytes).
+#ifndef TBE_UNPART_RUNS
+#define TBE_UNPART_RUNS 1                    // 0: 4-byte permutation and k_unscatter, as before (A/B)
+#endif
+constexpr int kRunTasks1 = 3 * kPartBlock;   // one-byte replies: dword tasks per tile, rounded up to the block
+static_assert(kTile / 4 + 3 * kDigits / 2 <= kRunTasks1, "every run: its dwords, plus at most 1.5 for its ragged ends");
+template <int W>
+__global__ __launch_bounds__(kPartBlock, 8) void k_unpart_runs(
+    uint64_t n, const uint16_t *__restrict__ idx, const uint32_t *__restrict__ tileprefix,
+    const uint32_t *__restrict__ blockprefix, const uint32_t *__restrict__ digit_total,
+    uint32_t tiles_per_blk, uint32_t ntiles, uint32_t nblk, const uint32_t *__restrict__ res_in,
+    uint8_t *__restrict__ granted, int32_t *__restrict__ remaining, const uint32_t *__restrict__ err,
+    uint32_t *__restrict__ sticky) {
+    static_assert(W == 1 || W == 4, "one-byte or four-byte replies");
+    static_assert(kTile == 8 * kPartBlock && kPartBlock >= kDigits && kPartItems == 8, "8 indices (16 bytes) per thread");
+    using R = std::conditional_t<W == 1, uint8_t, uint32_t>;
+    constexpr int kTasks = W == 1 ? kRunTasks1 : kTile;
+    constexpr int kPer = kTasks / kPartBlock;   // tasks per thread: 3 or 8
+    __shared__ uint32_t goff[kDigits];          // global position of the run's first reply
+    __shared__ uint32_t lst[kDigits];           // its staged index (lstart)
+    __shared__ uint32_t rcnt[kDigits];          // its length
+    __shared__ uint32_t tst[kDigits];           // its first task
+    __shared__ uint32_t wsum[kPartBlock / 64];
+    __shared__ uint32_t wmax[kPartBlock / 64];
+    __shared__ __attribute__((aligned(16))) uint8_t tdig[kTile];   // digit of task k (kTasks used)
+    __shared__ __attribute__((aligned(16))) uint16_t lidx[kTile];
+    __shared__ R reply[kTile];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (sticky && blockIdx.x == 0 && tid == 0 && *err) *sticky = 1u;
+    const uint32_t tile = xcd_swizzle(blockIdx.x, gridDim.x);
+    const uint64_t base = (uint64_t)tile * kTile;
+    const int nvalid = (int)min<uint64_t>(kTile, n - base);
+    // the tile's indices, 8 per lane (the permutation buffer holds whole tiles: entries past
+    // nvalid are read and never used); in flight during the offset loads and the scan, and
+    // waited for where they go to LDS, before the runs are loaded
+    const u32x4 iv = LD_U(reinterpret_cast<const u32x4 *>(idx + base) + tid);
+    // 1. offsets and counts
+    uint32_t cnt = 0;
+    if (tid < kDigits) {
+        const uint32_t blk = tile / tiles_per_blk;
+        const uint32_t tp = tileprefix[(uint64_t)tile * kDigits + tid];
+        if (tile + 1 < ntiles && (tile + 1) % tiles_per_blk != 0) {
+            cnt = tileprefix[(uint64_t)(tile + 1) * kDigits + tid] - tp;
+        } else {   // the block's last tile: the block's total minus the running count
+            const uint32_t bp = blockprefix[(uint64_t)blk * kDigits + tid];
+            const uint32_t nx = blk + 1 < nblk ? blockprefix[(uint64_t)(blk + 1) * kDigits + tid] : digit_total[tid];
+            cnt = nx - bp - tp;
+        }
+    }
+    tile_offsets<kPartBlock>(tile, tiles_per_blk, tileprefix, blockprefix, digit_total, goff, wsum);
+    const uint32_t g = tid < kDigits ? goff[tid] : 0u;   // (this thread's own store)
+    // tasks of this digit's run: its replies, or the aligned dwords they lie in
+    const uint32_t ntask = W == 1 ? (cnt ? ((g & 3u) + cnt + 3u) >> 2 : 0u) : cnt;
+    // one scan for both: counts sum to at most kTile (low half), tasks to at most kTasks
+    uint32_t all;
+    const uint32_t sc = block_excl_scan<kPartBlock>(cnt | (ntask << 16), wsum, &all);
+    const uint32_t lstart = sc & 0xFFFFu, tstart = sc >> 16;
+    const uint32_t ntasks = all >> 16;
+    // 2. digit of every task
+    reinterpret_cast<uint2 *>(tdig)[tid] = make_uint2(0u, 0u);
+    reinterpret_cast<u32x4 *>(lidx)[tid] = iv;
+    __syncthreads();
+    if (tid < kDigits) {
+        lst[tid] = lstart;
+        rcnt[tid] = cnt;
+        tst[tid] = tstart;
+        if (cnt) tdig[tstart] = (uint8_t)tid;
+    }
+    __syncthreads();
+    {
+        const uint2 v = reinterpret_cast<const uint2 *>(tdig)[tid];
+        uint32_t b[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) b[k] = ((k < 4 ? v.x : v.y) >> (8 * (k & 3))) & 0xFFu;
+#pragma unroll
+        for (int k = 1; k < 8; ++k) b[k] = max(b[k], b[k - 1]);
+        uint32_t inc = b[7];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(inc, o, 64);
+            if (lane >= o) inc = max(inc, y);
+        }
+        uint32_t carry = __shfl_up(inc, 1, 64);
+        if (lane == 0) carry = 0;
+        if (lane == 63) wmax[w] = inc;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < kPartBlock / 64; ++j) carry = max(carry, j < w ? wmax[j] : 0u);
+        uint2 o2 = make_uint2(0u, 0u);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t d = max(b[k], carry);
+            if (k < 4) o2.x |= d << (8 * k);
+            else o2.y |= d << (8 * (k - 4));
+        }
+        reinterpret_cast<uint2 *>(tdig)[tid] = o2;
+    }
+    __syncthreads();
+    // 3. the runs, in staged order
+#pragma unroll
+    for (int it = 0; it < kPer; ++it) {
+        const uint32_t k = (uint32_t)(it * kPartBlock + tid);
+        if (k >= ntasks) continue;
+        const uint32_t d = tdig[k];
+        const uint32_t gd = goff[d], t = k - tst[d];
+        if constexpr (W == 1) {
+            // the t-th aligned dword of the run; its bytes inside the run go to the stage
+            const uint32_t a = (gd & ~3u) + 4u * t;
+            const uint32_t v = res_in[a >> 2];
+            const uint32_t c = rcnt[d], s = lst[d];
+#pragma unroll
+            for (uint32_t bb = 0; bb < 4; ++bb) {
+                const uint32_t p = a + bb - gd;   // (wraps below the run's start)
+                if (p < c) reply[s + p] = (uint8_t)(v >> (8 * bb));
+            }
+        } else {
+            reply[k] = res_in[gd + t];            // (tasks are staged replies: k = lst[d] + t)
+        }
+    }
+    __syncthreads();
+    // 4. arrival order
+#pragma unroll
+    for (int it = 0; it < kPartItems; ++it) {
+        const int e = it * kPartBlock + tid;
+        if (e >= nvalid) continue;
+        const uint64_t i = base + e;
+        const uint32_t r = reply[lidx[e] & (kTile - 1)];
+        if (W == 1) {
+            ST_U(granted + i, (uint8_t)(r >> 7));
+            ST_U(remaining + i, (int32_t)(r & 0x7Fu));
+        } else {
+            ST_U(granted + i, (uint8_t)(r >> 31));
+            ST_U(remaining + i, (int32_t)(r & 0x7FFFFFFFu));
         }
     }
 }
@@ -4452,6 +4671,9 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
     const uint64_t *rec0 = G.on ? (G.n0 ? reinterpret_cast<const uint64_t *>(w.ts0) : w.pass[e->passes - 2].rec)
                                 : nullptr;
     const bool unrank = e->unrank;
+    // the final un-partition through staged digit runs (k_unpart_runs), pass 0 writing 2-byte
+    // tile-local indices: the token-bucket kind with packed records and a stored permutation
+    const bool runs = TBE_UNPART_RUNS && e->packed && !approx && !wait && !unrank && !retry;
     const unsigned fold_grid = G.on ? (unsigned)((1ull << G.region_bits) * G.n_hi) : e->nbuckets;
     // token bucket: a sparse batch's dense buckets are listed for k_fold_wide, the rest go to
     // one wave each (k_fold_sparse)
@@ -4546,6 +4768,16 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
                 nullptr, nullptr, nullptr, w.pass[p - 1].rec, n, shift, e->pf, out.tileprefix,
                 out.blockprefix, out.digit_total, tpb, out.rec, out.perm, w.err, nullptr, 0, 0,
                 w.pass[p - 1].idx, out.idx);
+        else if (e->packed && p == 0 && hot && runs)
+            k_scatter_rec<true, true, false, false, false, -1, true><<<ntiles, kPartBlock, 0, sp>>>(
+                keys, permits, ts, nullptr, n, shift, pf, out.tileprefix, out.blockprefix,
+                out.digit_total, tpb, out.rec, out.perm, w.err, hot, e->nbuckets, e->r_bits,
+                nullptr, nullptr, FoldFmt{}, dnext, nullptr, w.ts0);
+        else if (e->packed && p == 0 && runs)
+            k_scatter_rec<true, false, false, false, false, -1, true><<<ntiles, kPartBlock, 0, sp>>>(
+                keys, permits, ts, nullptr, n, shift, pf, out.tileprefix, out.blockprefix,
+                out.digit_total, tpb, out.rec, out.perm, w.err, nullptr, 0, 0, nullptr,
+                nullptr, FoldFmt{}, dnext, nullptr, w.ts0);
         else if (e->packed && p == 0 && hot)
             k_scatter_rec<true, true><<<ntiles, kPartBlock, 0, sp>>>(
                 keys, permits, ts, nullptr, n, shift, pf, out.tileprefix, out.blockprefix,
@@ -4778,6 +5010,14 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
         k_unscatter<true, true, 4, true><<<untiles, kUnBlock, 0, sf>>>(
             n, w.pass[0].perm, w.res[cur], nullptr, granted, remaining, w.err, e->sticky, w.def[cur], nullptr,
             retry, e->ap.decay_rate);
+    else if (runs && e->narrow)
+        k_unpart_runs<1><<<ntiles, kPartBlock, 0, sf>>>(
+            n, reinterpret_cast<const uint16_t *>(w.pass[0].perm), w.pass[0].tileprefix, w.pass[0].blockprefix,
+            w.pass[0].digit_total, tpb, ntiles, nblk, w.res[cur], granted, remaining, w.err, e->sticky);
+    else if (runs)
+        k_unpart_runs<4><<<ntiles, kPartBlock, 0, sf>>>(
+            n, reinterpret_cast<const uint16_t *>(w.pass[0].perm), w.pass[0].tileprefix, w.pass[0].blockprefix,
+            w.pass[0].digit_total, tpb, ntiles, nblk, w.res[cur], granted, remaining, w.err, e->sticky);
     else if (unrank && !wait && e->narrow)
         TBE_UNRANK(k_unrank<1>);
     else if (unrank && !wait)

@@ -281,6 +281,20 @@ VARIANT_SETS = {
         "foldfam0_u": (["TBE_FOLD_FAM=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
         "absent0_u": (["TBE_ABSENT_BASE=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
     },
+    "unpart": {   # the final un-partition through staged digit runs against k_unscatter; k_hist with 16-byte key loads (off by default) (run with --plain)
+        "base_u": ([], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "runs0_u": (["TBE_UNPART_RUNS=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "load16_u": (["TBE_HIST_LOAD16=1"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+    },
+    "unpart_z": {
+        "base_z": ([], ["--workload", "zipf", "--steps", "20", "--warmup", "5"]),
+        "runs0_z": (["TBE_UNPART_RUNS=0"], ["--workload", "zipf", "--steps", "20", "--warmup", "5"]),
+        "load16_z": (["TBE_HIST_LOAD16=1"], ["--workload", "zipf", "--steps", "20", "--warmup", "5"]),
+    },
+    "unpart_floor": {   # timing only (wrong replies): k_unscatter's final pass without its divergent gathers
+        "runs0_u": (["TBE_UNPART_RUNS=0"], ["--workload", "uniform", "--no-host-buffer", "--no-strdir", "--no-sparse"]),
+        "nogather_u": (["TBE_UNPART_RUNS=0", "TBE_UN_NO_GATHER"], ["--workload", "uniform", "--no-host-buffer", "--no-strdir", "--no-sparse"]),
+    },
     "uniform": {
         "base_u": ([], ["--workload", "uniform"]),
         "hist2_u": (["TBE_HIST_AHEAD=2"], ["--workload", "uniform"]),
