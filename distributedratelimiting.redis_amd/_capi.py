@@ -43,7 +43,8 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_approx_acquire_batch_retry", "tbe_approx_acquire_batch_retry_device",
             "tbe_approx_idle_device", "tbe_approx_reset_device", "tbe_approx_idle", "tbe_approx_reset",
             "tbe_approx_export_live_device", "tbe_approx_export_live", "tbe_approx_import_rows_device",
-            "tbe_approx_import_rows")
+            "tbe_approx_import_rows", "tbe_create_classes", "tbe_classes", "tbe_set_class_device",
+            "tbe_set_class", "tbe_get_class_device", "tbe_get_class")
 TBE_WAIT_FAILED, TBE_WAIT_GRANTED, TBE_WAIT_QUEUED, TBE_WAIT_REJECTED = 0, 1, 2, 3
 TBE_RETRY_NONE, TBE_RETRY_OVERFLOW = -1, 2**63 - 1   # retry_after_ticks of the approximate kind
 
@@ -63,6 +64,15 @@ class TbeConfig(Structure):
         ("max_batch", c_uint64),
         ("zero_wait_slots", c_int32),
         ("reserved", c_int32),
+    ]
+
+
+class TbeClass(Structure):
+    """One limit class: tbe_class of include/tbe.h."""
+    _fields_ = [
+        ("token_limit", c_int32),
+        ("tokens_per_period", c_int32),
+        ("replenishment_period_ticks", c_int64),
     ]
 
 
@@ -90,6 +100,18 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_fill_rate.argtypes = [c_int32, c_int64]
     lib.tbe_create.restype = c_int32
     lib.tbe_create.argtypes = [POINTER(TbeConfig), POINTER(c_void_p)]
+    lib.tbe_create_classes.restype = c_int32
+    lib.tbe_create_classes.argtypes = [POINTER(TbeConfig), POINTER(TbeClass), c_uint32, POINTER(c_void_p)]
+    lib.tbe_classes.restype = c_int32
+    lib.tbe_classes.argtypes = [c_void_p, POINTER(TbeClass), c_uint32, POINTER(c_uint32)]
+    lib.tbe_set_class_device.restype = c_int32
+    lib.tbe_set_class_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]
+    lib.tbe_set_class.restype = c_int32
+    lib.tbe_set_class.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64]
+    lib.tbe_get_class_device.restype = c_int32
+    lib.tbe_get_class_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]
+    lib.tbe_get_class.restype = c_int32
+    lib.tbe_get_class.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
     lib.tbe_destroy.restype = None
     lib.tbe_destroy.argtypes = [c_void_p]
     lib.tbe_last_error.restype = c_char_p

@@ -1367,9 +1367,35 @@ static_assert(kWideChunk <= 4096 && kWideTail <= kWideBlock, "election tags and 
 #define WIDE_FT_GET(j, srow) req_time_rel((srow).t_us == kAbsent ? absent_t(TB) : (srow).t_us, TB, 0).new_t
 #define WIDE_FT_SET(j, v) ((void)0)
 
+// Limit classes: one byte per key, padded to whole buckets (a bucket's class
+// slice is loaded whole), and the engine's class table {cap, rate, ttl_ms} in device memory.
+// Kernels that know about classes are the CLS = true instantiations; every other one takes
+// an empty view and never reads it.
+struct ClsView {
+    const uint8_t *cls;
+    const TbParams *par;   // kMaxClasses entries (those past the engine's classes are zero)
+};
+constexpr uint32_t kMaxClasses = 256;
+// Classes whose parameters k_fold_wide copies into LDS (384 bytes; with the 2 KB of class
+// bytes 54,176 bytes per workgroup, three of which still fit a CU's 160 KiB); a row of a
+// higher class takes its parameters from the table in global memory.
+constexpr uint32_t kClsLds = 16;
+// The lapse bound of one key in the maintenance kernels, which take the view as a parameter
+// pack (none: a plain engine, and the kernel's signature is what it was before classes):
+// `x` is the engine-wide bound, or with a view the millisecond snapshot ts_us / 1000 that
+// the key's own ttl_ms is taken from.
+__device__ __forceinline__ int64_t key_exp_lt(int64_t x, uint64_t) { return x; }
+__device__ __forceinline__ int64_t key_exp_lt(int64_t x, uint64_t key, const ClsView &C) {
+    return (x - C.par[C.cls[key]].ttl_ms) * 1000;
+}
+
 // Buckets of >= wide_min requests (every nonempty bucket of a dense batch), shaped as above
 // (three workgroups per CU, chunks of 1536 requests).  k_fold_sparse takes the other buckets.
-template <bool PACKED, int FAM = -1>
+// CLS (wide records only): the bucket's class bytes sit in LDS beside its rows, and every
+// evaluation takes {cap, rate, ttl_ms} of its row's class from the class table: an LDS copy
+// of its first kClsLds entries, global loads for the others (256 classes are 6 KB, which
+// three workgroups per CU have no LDS for).
+template <bool PACKED, int FAM = -1, bool CLS = false>
 __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
     const uint32_t *__restrict__ skeys, const int32_t *__restrict__ sperm,
     const int64_t *__restrict__ sts, const uint64_t *__restrict__ srec,
@@ -1377,8 +1403,28 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
     int r_bits, uint64_t n_keys, Slot *__restrict__ table, TbParams P,
     uint32_t *__restrict__ res, const uint32_t *__restrict__ err, HotSet *__restrict__ hot_next,
     uint32_t narrow, uint32_t wide_min, FoldFmt G, const uint64_t *__restrict__ rec0,
-    const uint32_t *__restrict__ dlist = nullptr) {
+    const uint32_t *__restrict__ dlist = nullptr, ClsView C = ClsView{nullptr, nullptr}) {
+    static_assert(!CLS || !PACKED, "classes: wide records only");
     __shared__ Slot row[kMaxRows];
+    uint8_t *lcls = nullptr;   // CLS: the bucket's class bytes
+    if constexpr (CLS) {
+        __shared__ uint32_t lcls_w[kMaxRows / 4];
+        lcls = reinterpret_cast<uint8_t *>(lcls_w);
+    }
+    TbParams *lpar = nullptr;  // CLS: the first kClsLds classes' parameters
+    if constexpr (CLS) {
+        __shared__ TbParams lpar_s[kClsLds];
+        lpar = lpar_s;
+    }
+    // the parameters of one evaluation: the engine's, or the row's class's
+    auto par_of = [&](uint32_t j) -> TbParams {
+        if constexpr (CLS) {
+            const uint32_t c = lcls[j];
+            return c < kClsLds ? lpar[c] : C.par[c];
+        } else {
+            return P;
+        }
+    };
     // aux: requests per row in buckets that may hold a hot key (hcnt), otherwise the
     // compact list of requests still pending after round 1 (t_*)
     // A pending entry is 16 bytes (row | local id << 16, permits, timestamp); its request
@@ -1463,6 +1509,16 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
 #endif
     load_chunk(s);   // in flight together with the dense slice
     if (dense) slice_dma();
+    if constexpr (CLS) {
+        // R class bytes, four per lane, coalesced (cls is padded to whole buckets); visible
+        // after the first chunk's barrier, like the slice
+        static_assert(kMaxRows <= 4 * kWideBlock, "one class word per thread");
+        if ((uint32_t)tid * 4u < R)
+            reinterpret_cast<uint32_t *>(lcls)[tid] = reinterpret_cast<const uint32_t *>(C.cls + row0)[tid];
+        static_assert(sizeof(TbParams) == 24 && kClsLds * 3 <= kWideBlock, "class parameters as 8-byte words");
+        if ((uint32_t)tid < kClsLds * 3u)
+            reinterpret_cast<uint64_t *>(lpar)[tid] = reinterpret_cast<const uint64_t *>(C.par)[tid];
+    }
     for (uint32_t j = tid; j < (R + 31) / 32; j += kWideBlock) dirty[j] = 0;
 #ifdef TBE_FOLD_COPY_ONLY
     // A/B floor (not a decision path): the fold's memory traffic without its rounds --
@@ -1537,8 +1593,9 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
                     nrow[r] = row[kl[r]];
                     bool m;
                     // request times recomputed per evaluation (registers: three slots)
-                    const ReqTime rqr = PACKED ? req_time_rel(tsv[r], TB, P.ttl_ms) : req_time(tsv[r], P.ttl_ms);
-                    rep[r] = tb_step_ft(nrow[r], WIDE_FT_GET(kl[r], nrow[r]), pm[r], rqr, P, m);
+                    const TbParams Pk = par_of(kl[r]);
+                    const ReqTime rqr = PACKED ? req_time_rel(tsv[r], TB, P.ttl_ms) : req_time(tsv[r], Pk.ttl_ms);
+                    rep[r] = tb_step_ft(nrow[r], WIDE_FT_GET(kl[r], nrow[r]), pm[r], rqr, Pk, m);
                     if (m) atomicMax(&own[kl[r]], (round << 12) | (4095u - (uint32_t)(r * kWideBlock + tid)));
                 }
             }
@@ -1594,13 +1651,15 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
             int32_t tpm = 0;
             int64_t tts = 0;
             ReqTime trq{0.0, 0, 0};
+            TbParams tP = P;
             auto take = [&](uint32_t at) {
                 tkl = t_kl_lid[at] & 0xFFFFu;
                 tlid = t_kl_lid[at] >> 16;
                 tpm = t_pm[at];
                 tts = t_ts[at];
                 tpos = t_pos[at];
-                trq = PACKED ? req_time_rel(tts, TB, P.ttl_ms) : req_time(tts, P.ttl_ms);
+                if constexpr (CLS) tP = par_of(tkl);
+                trq = PACKED ? req_time_rel(tts, TB, P.ttl_ms) : req_time(tts, tP.ttl_ms);
             };
             if (tp) take(tid);
             // Each round settles at least the first pending request of every row; when the
@@ -1614,7 +1673,7 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
                 if (tp) {
                     nr = row[tkl];
                     bool m;
-                    trep = tb_step_ft(nr, WIDE_FT_GET(tkl, nr), tpm, trq, P, m);
+                    trep = tb_step_ft(nr, WIDE_FT_GET(tkl, nr), tpm, trq, tP, m);
                     if (m) atomicMax(&own[tkl], tag);
                 }
                 __syncthreads();
@@ -1673,7 +1732,7 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
                         if (tp) {
                             nr = row[tkl];
                             bool m;
-                            trep = tb_step_ft(nr, WIDE_FT_GET(tkl, nr), tpm, trq, P, m);
+                            trep = tb_step_ft(nr, WIDE_FT_GET(tkl, nr), tpm, trq, tP, m);
                             if (m) atomicMax(&own[tkl], tag);
                         }
                         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1717,8 +1776,9 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
                     if (pend & bit) {
                         nr = row[kl[r]];
                         bool m;
-                        const ReqTime rqr = PACKED ? req_time_rel(tsv[r], TB, P.ttl_ms) : req_time(tsv[r], P.ttl_ms);
-                        rep[r] = tb_step_ft(nr, WIDE_FT_GET(kl[r], nr), pm[r], rqr, P, m);
+                        const TbParams Pk = par_of(kl[r]);
+                        const ReqTime rqr = PACKED ? req_time_rel(tsv[r], TB, P.ttl_ms) : req_time(tsv[r], Pk.ttl_ms);
+                        rep[r] = tb_step_ft(nr, WIDE_FT_GET(kl[r], nr), pm[r], rqr, Pk, m);
                         if (m) atomicMax(&own[kl[r]], tag);
                     }
                     __syncthreads();
@@ -1784,14 +1844,17 @@ __device__ __forceinline__ double field_t(int64_t t_us, const TimeBase &B) {
 // chunk is re-read by the next after a workgroup-scope fence.
 constexpr int kSpBlock = 256;
 constexpr int kSpWaves = kSpBlock / 64;
-template <bool PACKED>
+// CLS (wide records only): the key's leader lane gathers cls[key] with the row and takes its
+// class's parameters from the class table.
+template <bool PACKED, bool CLS = false>
 __global__ __launch_bounds__(kSpBlock) void k_fold_sparse(
     const uint32_t *__restrict__ skeys, const int32_t *__restrict__ sperm,
     const int64_t *__restrict__ sts, const uint64_t *__restrict__ srec,
     const int64_t *__restrict__ ts_orig, PackFmt F, const uint32_t *__restrict__ bstart,
     int r_bits, uint64_t n_keys, Slot *__restrict__ table, TbParams P,
     uint32_t *__restrict__ res, const uint32_t *__restrict__ err, uint32_t narrow, uint32_t wide_min,
-    FoldFmt G, const uint64_t *__restrict__ rec0, uint32_t n_walk) {
+    FoldFmt G, const uint64_t *__restrict__ rec0, uint32_t n_walk, ClsView C = ClsView{nullptr, nullptr}) {
+    static_assert(!CLS || !PACKED, "classes: wide records only");
     if (*err) return;
     const int lane = threadIdx.x & 63;
     const uint32_t wave = blockIdx.x * kSpWaves + (threadIdx.x >> 6);
@@ -1848,7 +1911,11 @@ __global__ __launch_bounds__(kSpBlock) void k_fold_sparse(
                 }
                 const bool leader = v && (peers & lt) == 0;   // the key's earliest request here
                 Slot st = Slot{0.0, 0};
-                if (leader) st = rows[kl];
+                TbParams Pk = P;
+                if (leader) {
+                    st = rows[kl];
+                    if constexpr (CLS) Pk = C.par[C.cls[((uint64_t)b << r_bits) + kl]];
+                }
                 uint64_t todo = leader ? peers : 0ull;
                 bool mod = false;
                 while (__any(todo != 0ull)) {
@@ -1857,9 +1924,9 @@ __global__ __launch_bounds__(kSpBlock) void k_fold_sparse(
                     const int64_t ts_m = __shfl(tsv, m, 64);
                     const uint32_t pos_m = __shfl(pos, m, 64);
                     if (todo) {
-                        const ReqTime rq = PACKED ? req_time_rel(ts_m, TB, P.ttl_ms) : req_time(ts_m, P.ttl_ms);
+                        const ReqTime rq = PACKED ? req_time_rel(ts_m, TB, P.ttl_ms) : req_time(ts_m, Pk.ttl_ms);
                         bool md;
-                        const uint32_t rep = tb_step_ft(st, field_t(st.t_us, TB), pm_m, rq, P, md);
+                        const uint32_t rep = tb_step_ft(st, field_t(st.t_us, TB), pm_m, rq, Pk, md);
                         mod |= md;
                         put_reply(res, pos_m, rep, narrow);
                         todo &= todo - 1;
@@ -3953,15 +4020,20 @@ __global__ __launch_bounds__(kBlock) void k_count_queued(uint64_t n_keys, const 
 // bound is exp_lt (req_time: t_us < exp_lt has lapsed, TB:232-235) and, for the queueing
 // kind, nothing is queued on it.  One 16-byte row per lane, byte flags out.  clear: a
 // lapsed row is rewritten absent, so that a later, earlier timestamp finds a full bucket.
-template <typename HW>
+// With a ClsView: exp_lt carries ts_us / 1000 and each key's bound comes from its class
+// (key_exp_lt); the class bytes stay as they are (the caller sets a reused id's class).
+template <typename HW, typename... CV>
 __global__ __launch_bounds__(kBlock) void k_expired(Slot *__restrict__ table, const HW *__restrict__ qhdr,
                                                     uint64_t first, uint64_t count, int64_t exp_lt, double cap,
-                                                    int32_t clear, uint8_t *__restrict__ dead) {
+                                                    int32_t clear, uint8_t *__restrict__ dead, CV... C) {
+    static_assert(sizeof...(CV) <= 1, "at most one class view");
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= count) return;
     const Slot s = table[first + i];
     const bool absent = s.t_us == kAbsent;
-    const bool gone = absent || s.t_us < exp_lt;
+    bool gone;
+    if constexpr (sizeof...(CV) == 0) gone = absent || s.t_us < exp_lt;
+    else gone = absent || s.t_us < key_exp_lt(exp_lt, first + i, C...);
     if (clear && gone && !absent) table[first + i] = Slot{cap, kAbsent};
     const bool queued = qhdr && ((qh_widen(qhdr[first + i]) >> 16) & 0xFFFFu) != 0;
     dead[i] = gone && !queued;
@@ -3982,15 +4054,17 @@ constexpr int kLiveScan = 1024;                  // tile counts one k_live_scan 
 
 __device__ __forceinline__ bool row_live(int64_t t_us, int64_t exp_lt) { return t_us != kAbsent && !(t_us < exp_lt); }
 
+template <typename... CV>   // (a ClsView: per-key bounds, as in k_expired)
 __global__ __launch_bounds__(kBlock) void k_live_count(const Slot *__restrict__ table, uint64_t first, uint64_t count,
-                                                       int64_t exp_lt, unsigned long long *__restrict__ tile_n) {
+                                                       int64_t exp_lt, unsigned long long *__restrict__ tile_n,
+                                                       CV... C) {
     __shared__ uint32_t wsum[kWaves];
     const uint64_t base = (uint64_t)blockIdx.x * kLiveTile;
     uint32_t c = 0;
 #pragma unroll
     for (int k = 0; k < kLiveItems; ++k) {
         const uint64_t i = base + (uint64_t)k * kBlock + threadIdx.x;
-        if (i < count && row_live(ld_nt(&table[first + i].t_us), exp_lt)) ++c;
+        if (i < count && row_live(ld_nt(&table[first + i].t_us), key_exp_lt(exp_lt, first + i, C...))) ++c;
     }
     uint32_t tot;
     (void)block_excl_scan<kBlock>(c, wsum, &tot);
@@ -4013,10 +4087,11 @@ __global__ __launch_bounds__(kLiveScan) void k_live_scan(unsigned long long *__r
     if (threadIdx.x == 0) *n_live = carry;
 }
 
+template <typename... CV>
 __global__ __launch_bounds__(kBlock) void k_live_write(const Slot *__restrict__ table, uint64_t first, uint64_t count,
                                                        int64_t exp_lt, const unsigned long long *__restrict__ tile_at,
                                                        uint64_t capacity, uint64_t *__restrict__ ids,
-                                                       double *__restrict__ v, int64_t *__restrict__ t_us) {
+                                                       double *__restrict__ v, int64_t *__restrict__ t_us, CV... C) {
     __shared__ uint32_t cnt[kLiveItems * kWaves];
     const uint64_t at = tile_at[blockIdx.x];
     if (at >= capacity) return;   // (the whole workgroup: nothing of this tile fits)
@@ -4031,7 +4106,7 @@ __global__ __launch_bounds__(kBlock) void k_live_write(const Slot *__restrict__ 
         live[k] = false;
         if (i < count) {
             s[k] = slot_load_nt(&table[first + i]);
-            live[k] = row_live(s[k].t_us, exp_lt);
+            live[k] = row_live(s[k].t_us, key_exp_lt(exp_lt, first + i, C...));
         }
         const uint64_t bal = __ballot(live[k]);
         rank[k] = (uint32_t)__popcll(bal & lanemask_lt());
@@ -4079,6 +4154,47 @@ __global__ void k_rows_write(Slot *__restrict__ table, const uint64_t *__restric
         const int64_t t = t_us[i];
         table[ids[i]] = t == kAbsent ? Slot{cap, kAbsent} : Slot{v[i], t};
     }
+}
+
+// ---- limit classes (tbe_set_class_device / tbe_get_class_device), shaped like the import by
+// id: k_set_class_check sets *bad for an id >= n_keys or a class >= n_classes, and
+// k_set_class_write then writes nothing and raises the sticky flag.
+__global__ void k_set_class_check(const uint64_t *__restrict__ ids, const uint8_t *__restrict__ cls, uint64_t n,
+                                  uint64_t n_keys, uint32_t n_classes, uint32_t *__restrict__ bad) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        if (ids[i] >= n_keys || cls[i] >= n_classes) *bad = 1u;
+}
+
+__global__ void k_set_class_write(uint8_t *__restrict__ key_cls, const uint64_t *__restrict__ ids,
+                                  const uint8_t *__restrict__ cls, uint64_t n, const uint32_t *__restrict__ bad,
+                                  uint32_t *__restrict__ sticky) {
+    if (*bad) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) *sticky = 1u;
+        return;
+    }
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) key_cls[ids[i]] = cls[i];
+}
+
+// out[i] = class of ids[i]; an id >= n_keys sets *bad and the sticky flag (its byte reads 0).
+// key_cls == nullptr: an engine without extra classes, every key in class 0.
+__global__ void k_get_class(const uint8_t *__restrict__ key_cls, const uint64_t *__restrict__ ids, uint64_t n,
+                            uint64_t n_keys, uint8_t *__restrict__ out, uint32_t *__restrict__ sticky) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t k = ids[i];
+        if (k >= n_keys) *sticky = 1u;
+        out[i] = (k < n_keys && key_cls) ? key_cls[k] : (uint8_t)0;
+    }
+}
+
+// Every key of a new engine in class 0 (the padding up to whole buckets too), 16 bytes per
+// lane; n16 = bytes / 16.
+__global__ void k_init_cls(uint8_t *__restrict__ key_cls, uint64_t n16) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    u32x4 *p = reinterpret_cast<u32x4 *>(key_cls);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) p[i] = u32x4{0, 0, 0, 0};
 }
 
 // ---- approximate kind: idle scan, reset and portable snapshots of the {v, p, t} tier
@@ -4325,6 +4441,14 @@ struct tbe_engine {
     HotSet *hot[3] = {nullptr, nullptr, nullptr};
     uint64_t nbatch = 0;
     Slot *table = nullptr;
+    // limit classes (tbe_create_classes; token bucket, wide records): class 0 is `params`.
+    // cls is one byte per key padded to whole buckets, cls_par the device copy of class_par;
+    // both exist only on an engine created with extra classes.
+    std::vector<tbe_class> class_opts;   // every class's options, class 0 first
+    std::vector<TbParams> class_par;
+    uint8_t *cls = nullptr;
+    TbParams *cls_par = nullptr;
+    ClsView cls_view() const { return ClsView{cls, cls_par}; }
     // queueing kind
     QParams qp{};
     uint64_t *qhdr = nullptr;      // per-key queue header (32-bit words when qh32: qh_store)
@@ -4921,6 +5045,14 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
             k_fold_sparse<true><<<sgrid, kSpBlock, 0, sf>>>(
                 nullptr, nullptr, nullptr, sorted.rec, ts, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
                 e->table, e->params, w.res[0], w.err, e->narrow ? 1u : 0u, tb_wmin, G, rec0, walk);
+        } else if (e->cls) {
+            k_fold_wide<false, -1, true><<<dgrid, kWideBlock, 0, sf>>>(
+                sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,
+                e->cfg.n_keys, e->table, e->params, w.res[0], w.err, nullptr, 0u, tb_wmin, G, rec0, w.dlist,
+                e->cls_view());
+            k_fold_sparse<false, true><<<sgrid, kSpBlock, 0, sf>>>(
+                sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,
+                e->cfg.n_keys, e->table, e->params, w.res[0], w.err, 0u, tb_wmin, G, rec0, walk, e->cls_view());
         } else {
             k_fold_wide<false><<<dgrid, kWideBlock, 0, sf>>>(
                 sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,
@@ -4931,6 +5063,11 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
         }
     } else if (e->packed) {   // a dense batch: k_fold_wide takes every bucket
         LAUNCH_WIDE(fold_grid, nullptr);
+    } else if (e->cls) {
+        k_fold_wide<false, -1, true><<<e->nbuckets, kWideBlock, 0, sf>>>(
+            sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,
+            e->cfg.n_keys, e->table, e->params, w.res[0], w.err, nullptr, 0u, tb_wmin, G, rec0, nullptr,
+            e->cls_view());
     } else {
         k_fold_wide<false><<<e->nbuckets, kWideBlock, 0, sf>>>(
             sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,
@@ -5097,7 +5234,58 @@ static tbe_status create_fail(tbe_status st, const char *msg) {
     return st;
 }
 
+// The constructor checks on one class's options (TB:29-37) and its script parameters: the
+// fill rate as tbe_fill_rate gives it and the EXPIRE seconds of TB:234.  NULL when they are
+// fine, else the message.
+static const char *class_params(int32_t token_limit, int32_t tokens_per_period, int64_t period_ticks, TbParams *out) {
+    if (token_limit <= 0 || tokens_per_period <= 0)                           // TB:29-32
+        return "Both TokenLimit and TokensPerPeriod must be set to values greater than 0.";
+    if (period_ticks <= 0)                                                    // TB:34-37 (+ "inf")
+        return "ReplenishmentPeriod must be greater than TimeSpan.Zero";
+    const double rate = tbe_fill_rate(tokens_per_period, period_ticks);
+    if (!std::isfinite(rate) || !(rate > 0.0)) return "fill rate is not finite and positive";
+    out->cap = (double)token_limit;
+    out->rate = rate;
+    // TB:234: math.ceil(math.min(math.max(capacity / fill_rate, 1), 31536000))
+    double q = (double)token_limit / rate;
+    q = (1.0 > q) ? 1.0 : q;
+    q = (31536000.0 < q) ? 31536000.0 : q;
+    out->ttl_ms = (int64_t)std::ceil(q) * 1000;
+    return nullptr;
+}
+
+static tbe_status create_engine(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
+                                tbe_engine **out_engine);
+
 tbe_status tbe_create(const tbe_config *config, tbe_engine **out_engine) {
+    return create_engine(config, nullptr, 0, out_engine);
+}
+
+tbe_status tbe_create_classes(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
+                              tbe_engine **out_engine) {
+    if (!out_engine) return create_fail(TBE_EINVAL, "out_engine is NULL");
+    *out_engine = nullptr;
+    if (n_extra == 0) return create_engine(config, nullptr, 0, out_engine);
+    static_assert(kMaxClasses == 256, "class bytes");
+    if (n_extra > kMaxClasses - 1) return create_fail(TBE_EINVAL, "an engine holds at most 256 limit classes (255 extra)");
+    if (!extra) return create_fail(TBE_EINVAL, "extra is NULL with n_extra > 0");
+    if (!config || config->struct_size < offsetof(tbe_config, zero_wait_slots))
+        return create_fail(TBE_EINVAL, "config is NULL or struct_size too small");
+    if (config->kind != TBE_KIND_TOKEN_BUCKET)
+        return create_fail(TBE_EINVAL, "limit classes: token-bucket kind only");
+    for (uint32_t i = 0; i < n_extra; ++i) {
+        TbParams p;
+        if (const char *msg = class_params(extra[i].token_limit, extra[i].tokens_per_period,
+                                           extra[i].replenishment_period_ticks, &p))
+            return create_fail(TBE_EINVAL, msg);
+    }
+    return create_engine(config, extra, n_extra, out_engine);
+}
+
+// extra != NULL: a classed engine, laid out as TBE_FLAG_NO_PACK | NO_HOT | NO_NARROW (wide
+// records, 4-byte replies, no hot runs: the forms whose folds know about classes).
+static tbe_status create_engine(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
+                                tbe_engine **out_engine) {
     if (!out_engine) return create_fail(TBE_EINVAL, "out_engine is NULL");
     *out_engine = nullptr;
     // struct_size versions the config: a caller built against the round-1 header (which
@@ -5108,6 +5296,7 @@ tbe_status tbe_create(const tbe_config *config, tbe_engine **out_engine) {
     tbe_config c_in;
     std::memset(&c_in, 0, sizeof c_in);
     std::memcpy(&c_in, config, std::min<size_t>(config->struct_size, sizeof c_in));
+    if (extra) c_in.flags |= TBE_FLAG_NO_PACK | TBE_FLAG_NO_HOT | TBE_FLAG_NO_NARROW;
     const tbe_config &c = c_in;
     if (c.kind != TBE_KIND_TOKEN_BUCKET && c.kind != TBE_KIND_QUEUEING &&
         c.kind != TBE_KIND_APPROXIMATE)
@@ -5148,6 +5337,14 @@ tbe_status tbe_create(const tbe_config *config, tbe_engine **out_engine) {
     const int kb = ceil_log2(c.n_keys);
     e->r_bits = std::min(kMaxRBits, std::max(4, kb - 10));
     e->nbuckets = (uint32_t)((c.n_keys + (1ull << e->r_bits) - 1) >> e->r_bits);
+    e->class_opts.push_back(tbe_class{c.token_limit, c.tokens_per_period, c.replenishment_period_ticks});
+    e->class_par.push_back(e->params);
+    for (uint32_t i = 0; i < n_extra; ++i) {   // (validated by tbe_create_classes)
+        TbParams p{};
+        (void)class_params(extra[i].token_limit, extra[i].tokens_per_period, extra[i].replenishment_period_ticks, &p);
+        e->class_opts.push_back(extra[i]);
+        e->class_par.push_back(p);
+    }
     const int bbits = ceil_log2(e->nbuckets);
     e->passes = std::max(1, (bbits + kDigitBits - 1) / kDigitBits);
     e->timing = (c.flags & (TBE_FLAG_STAGE_TIMING | TBE_FLAG_FOLD_TIMING)) != 0;
@@ -5230,6 +5427,11 @@ tbe_status tbe_create(const tbe_config *config, tbe_engine **out_engine) {
     const uint64_t qhdr_n = (c.n_keys + 3) & ~3ull;   // k_fold_q loads headers 16 bytes per lane
     uint64_t ring_n = 0;
     if (dalloc(&e->table, c.n_keys * sizeof(Slot)) != hipSuccess) return bail(TBE_ENOMEM);
+    const uint64_t cls_bytes = (uint64_t)e->nbuckets << e->r_bits;   // whole buckets (r_bits >= 4: 16-byte units)
+    if (extra) {
+        if (dalloc(&e->cls, cls_bytes) != hipSuccess) return bail(TBE_ENOMEM);
+        if (dalloc(&e->cls_par, kMaxClasses * sizeof(TbParams)) != hipSuccess) return bail(TBE_ENOMEM);
+    }
     if (e->hot_cap)
         for (auto &hs : e->hot)
             if (dalloc(&hs, sizeof(HotSet)) != hipSuccess) return bail(TBE_ENOMEM);
@@ -5281,6 +5483,15 @@ tbe_status tbe_create(const tbe_config *config, tbe_engine **out_engine) {
         }
     if (ie != hipSuccess) return bail(TBE_EDEVICE);
     k_init_table<<<2048, 256, 0, e->stream>>>(e->table, c.n_keys, e->params.cap);
+    if (extra) {
+        zero(e->cls_par, kMaxClasses * sizeof(TbParams));
+        if (ie != hipSuccess) return bail(TBE_EDEVICE);
+        k_init_cls<<<2048, 256, 0, e->stream>>>(e->cls, cls_bytes / 16);
+        // (class_par outlives the copy: the stream is synchronised below)
+        if (hipMemcpyAsync(e->cls_par, e->class_par.data(), e->class_par.size() * sizeof(TbParams),
+                           hipMemcpyHostToDevice, e->stream) != hipSuccess)
+            return bail(TBE_EDEVICE);
+    }
     if (c.kind == TBE_KIND_APPROXIMATE)
         k_init_approx<<<2048, 256, 0, e->stream>>>(c.n_keys, e->alocal, e->aclient, e->gv, e->gp, e->gt,
                                                    c.token_limit);
@@ -5301,6 +5512,8 @@ void tbe_destroy(tbe_engine *e) {
     free_workspace(e->ws[1]);
     free_staging(e);
     dfree(e->table);
+    dfree(e->cls);
+    dfree(e->cls_par);
     dfree(e->alocal);
     dfree(e->aclient);
     dfree(e->gv);
@@ -5524,13 +5737,16 @@ tbe_status tbe_query(tbe_engine *e, uint64_t key, int64_t ts_us, double *v, doub
     if (key >= e->cfg.n_keys) return fail(e, TBE_EINVAL, "key out of range");
     HIP_TRY(e, hipSetDevice(e->device));
     Slot s;
+    uint8_t kc = 0;   // the key's class (classed engines), whose ttl_ms judges the lapse
     HIP_TRY(e, hipMemcpyAsync(&s, e->table + key, sizeof(Slot), hipMemcpyDeviceToHost, e->stream));
+    if (e->cls) HIP_TRY(e, hipMemcpyAsync(&kc, e->cls + key, 1, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     *present = 0;
     *v = 0.0;
     *t = 0.0;
     if (s.t_us == kAbsent) return TBE_OK;
-    if (ts_us >= 0 && (ts_us / 1000) > (s.t_us / 1000) + e->params.ttl_ms) return TBE_OK;
+    const int64_t ttl_ms = e->cls ? e->class_par[kc].ttl_ms : e->params.ttl_ms;
+    if (ts_us >= 0 && (ts_us / 1000) > (s.t_us / 1000) + ttl_ms) return TBE_OK;
     *present = 1;
     *v = s.v;
     const int64_t sec = s.t_us / 1000000, usec = s.t_us - sec * 1000000;
@@ -5576,7 +5792,10 @@ tbe_status tbe_expired_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint
     }
     const int64_t exp_lt = (ts_us / 1000 - e->params.ttl_ms) * 1000;
     const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
-    if (e->cfg.kind == TBE_KIND_QUEUEING)
+    if (e->cls)   // per key: the kernel takes each key's ttl_ms from its class
+        k_expired<<<blocks, kBlock, 0, st>>>(e->table, (const uint64_t *)nullptr, first, count, ts_us / 1000,
+                                             e->params.cap, clear, d_dead, e->cls_view());
+    else if (e->cfg.kind == TBE_KIND_QUEUEING)
         with_qhdr(e, [&](auto *qh) {
             k_expired<<<blocks, kBlock, 0, st>>>(e->table, qh, first, count, exp_lt, e->params.cap, clear, d_dead);
         });
@@ -5616,11 +5835,20 @@ tbe_status tbe_export_live_device(tbe_engine *e, int64_t ts_us, uint64_t first, 
     } else {
         const int64_t exp_lt = ts_us < 0 ? kAbsent : (ts_us / 1000 - e->params.ttl_ms) * 1000;   // < 0: no row lapses
         const uint64_t ntiles = (count + kLiveTile - 1) / kLiveTile;
-        k_live_count<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, exp_lt, e->live_tiles);
+        // classed engine with a lapse test: per key, from ts_us / 1000 and the key's class
+        const bool by_class = e->cls && ts_us >= 0;
+        if (by_class)
+            k_live_count<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, ts_us / 1000, e->live_tiles,
+                                                              e->cls_view());
+        else
+            k_live_count<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, exp_lt, e->live_tiles);
         k_live_scan<<<1, kLiveScan, 0, st>>>(e->live_tiles, ntiles, reinterpret_cast<unsigned long long *>(d_n_live));
-        if (capacity)
-            k_live_write<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, exp_lt, e->live_tiles, capacity,
-                                                              d_ids, d_v, d_t_us);
+        if (capacity && by_class)
+            k_live_write<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, ts_us / 1000, e->live_tiles,
+                                                              capacity, d_ids, d_v, d_t_us, e->cls_view());
+        else if (capacity)
+            k_live_write<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, exp_lt, e->live_tiles,
+                                                              capacity, d_ids, d_v, d_t_us);
         HIP_TRY(e, hipGetLastError());
     }
     if (caller && caller != st) {
@@ -5713,6 +5941,122 @@ tbe_status tbe_import_rows(tbe_engine *e, const uint64_t *ids, const double *v, 
     tbe_status rc = TBE_OK;
     if (hrc == hipSuccess) rc = tbe_import_rows_device(e, d_ids, d_v, d_t, n, nullptr);
     if (hrc == hipSuccess && rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
+    return TBE_OK;
+}
+
+// ---- limit classes
+tbe_status tbe_classes(const tbe_engine *e, tbe_class *out, uint32_t capacity, uint32_t *n_classes) {
+    if (!e || !n_classes) return TBE_EINVAL;
+    *n_classes = (uint32_t)e->class_opts.size();
+    for (uint32_t i = 0; out && i < capacity && i < e->class_opts.size(); ++i) out[i] = e->class_opts[i];
+    return TBE_OK;
+}
+
+// On the engine's stream, where every kernel that touches table or classes runs, a caller's
+// stream joined before and after: tbe_import_rows_device's ordering.
+tbe_status tbe_set_class_device(tbe_engine *e, const uint64_t *d_ids, const uint8_t *d_cls, uint64_t n,
+                                void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_TOKEN_BUCKET) return fail(e, TBE_EINVAL, "limit classes: token-bucket kind only");
+    if (n == 0) return TBE_OK;
+    if (!d_ids || !d_cls) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (!e->rows_bad) HIP_TRY(e, hipMalloc(&e->rows_bad, sizeof(uint32_t)));
+    hipStream_t st = e->stream, caller = (hipStream_t)stream;
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_in, caller));
+        HIP_TRY(e, hipStreamWaitEvent(st, e->ev_in, 0));
+    }
+    HIP_TRY(e, hipMemsetAsync(e->rows_bad, 0, sizeof(uint32_t), st));
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192);
+    // the validating pass ends before the first class is written (one stream)
+    k_set_class_check<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys, (uint32_t)e->class_par.size(),
+                                                 e->rows_bad);
+    if (e->cls)
+        k_set_class_write<<<blocks, kBlock, 0, st>>>(e->cls, d_ids, d_cls, n, e->rows_bad, e->sticky);
+    else   // no extra classes: class 0 is all a valid call can ask for, so there is nothing to write
+        k_set_class_write<<<1, 1, 0, st>>>(nullptr, d_ids, d_cls, 0, e->rows_bad, e->sticky);
+    HIP_TRY(e, hipGetLastError());
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_out, st));
+        HIP_TRY(e, hipStreamWaitEvent(caller, e->ev_out, 0));
+    }
+    return TBE_OK;
+}
+
+tbe_status tbe_set_class(tbe_engine *e, const uint64_t *ids, const uint8_t *cls, uint64_t n) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_TOKEN_BUCKET) return fail(e, TBE_EINVAL, "limit classes: token-bucket kind only");
+    if (n == 0) return TBE_OK;
+    if (!ids || !cls) return fail(e, TBE_EINVAL, "null buffer");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (ids[i] >= e->cfg.n_keys) return fail(e, TBE_EINVAL, "id out of range");
+        if (cls[i] >= e->class_par.size()) return fail(e, TBE_EINVAL, "class out of range");
+    }
+    if (!e->cls) return TBE_OK;   // every class is 0 and stays so
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch, whatever its stream
+    void *buf = nullptr;
+    HIP_TRY(e, hipMalloc(&buf, n * 9));
+    uint64_t *d_ids = static_cast<uint64_t *>(buf);
+    uint8_t *d_cls = reinterpret_cast<uint8_t *>(d_ids + n);
+    hipError_t hrc = hipMemcpy(d_ids, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (hrc == hipSuccess) hrc = hipMemcpy(d_cls, cls, n, hipMemcpyHostToDevice);
+    tbe_status rc = TBE_OK;
+    if (hrc == hipSuccess) rc = tbe_set_class_device(e, d_ids, d_cls, n, nullptr);
+    if (hrc == hipSuccess && rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
+    return TBE_OK;
+}
+
+tbe_status tbe_get_class_device(tbe_engine *e, const uint64_t *d_ids, uint64_t n, uint8_t *d_cls, void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_TOKEN_BUCKET) return fail(e, TBE_EINVAL, "limit classes: token-bucket kind only");
+    if (n == 0) return TBE_OK;
+    if (!d_ids || !d_cls) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    hipStream_t st = e->stream, caller = (hipStream_t)stream;
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_in, caller));
+        HIP_TRY(e, hipStreamWaitEvent(st, e->ev_in, 0));
+    }
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192);
+    k_get_class<<<blocks, kBlock, 0, st>>>(e->cls, d_ids, n, e->cfg.n_keys, d_cls, e->sticky);
+    HIP_TRY(e, hipGetLastError());
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_out, st));
+        HIP_TRY(e, hipStreamWaitEvent(caller, e->ev_out, 0));
+    }
+    return TBE_OK;
+}
+
+tbe_status tbe_get_class(tbe_engine *e, const uint64_t *ids, uint64_t n, uint8_t *cls) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_TOKEN_BUCKET) return fail(e, TBE_EINVAL, "limit classes: token-bucket kind only");
+    if (n == 0) return TBE_OK;
+    if (!ids || !cls) return fail(e, TBE_EINVAL, "null buffer");
+    for (uint64_t i = 0; i < n; ++i)
+        if (ids[i] >= e->cfg.n_keys) return fail(e, TBE_EINVAL, "id out of range");
+    if (!e->cls) {
+        std::memset(cls, 0, n);
+        return TBE_OK;
+    }
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());
+    void *buf = nullptr;
+    HIP_TRY(e, hipMalloc(&buf, n * 9));
+    uint64_t *d_ids = static_cast<uint64_t *>(buf);
+    uint8_t *d_cls = reinterpret_cast<uint8_t *>(d_ids + n);
+    hipError_t hrc = hipMemcpy(d_ids, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice);
+    tbe_status rc = TBE_OK;
+    if (hrc == hipSuccess) rc = tbe_get_class_device(e, d_ids, n, d_cls, nullptr);
+    if (hrc == hipSuccess && rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
+    if (hrc == hipSuccess && rc == TBE_OK) hrc = hipMemcpy(cls, d_cls, n, hipMemcpyDeviceToHost);
     (void)hipFree(buf);
     if (rc != TBE_OK) return rc;
     HIP_TRY(e, hrc);

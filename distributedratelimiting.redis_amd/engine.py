@@ -59,7 +59,10 @@ class TokenBucketEngine:
                  device: int = -1, stage_timing: bool = False, max_batch: int = 0,
                  queue_limit: int = 0, queue_order: int = 0, pack: bool = True, hot: bool = True,
                  pipeline: bool = True, narrow: bool = True, zero_wait_slots: int = 0,
-                 fold_records: bool = True, digit_stream: bool = True, rerank: bool = False):
+                 fold_records: bool = True, digit_stream: bool = True, rerank: bool = False,
+                 classes=None):
+        """classes: extra limit classes 1.. as (token_limit, tokens_per_period, period_ticks)
+        (tbe_create_classes; class 0 is this engine's own three options)."""
         self._lib = _capi.load()
         # stage_timing: True (every stage), "fold" (the fold alone) or False
         flags = (_capi.TBE_FLAG_FOLD_TIMING if stage_timing == "fold"
@@ -83,11 +86,16 @@ class TokenBucketEngine:
                                         queue_order=queue_order, device=device, flags=flags,
                                         max_batch=max_batch, zero_wait_slots=zero_wait_slots)
         h = c_void_p()
-        st = self._lib.tbe_create(byref(self.config), byref(h))
+        if classes:
+            extra = (_capi.TbeClass * len(classes))(*[_capi.TbeClass(int(a), int(b), int(c)) for a, b, c in classes])
+            st = self._lib.tbe_create_classes(byref(self.config), extra, len(classes), byref(h))
+        else:
+            st = self._lib.tbe_create(byref(self.config), byref(h))
         if st != _capi.TBE_OK:
-            raise TbeError(st, "tbe_create failed")
+            raise TbeError(st, "tbe_create failed: " + self._lib.tbe_last_error(None).decode())
         self._h = h
         self.n_keys = n_keys
+        self.classed = bool(classes)
 
     # ------------------------------------------------------------------ lifetime
     def close(self) -> None:
@@ -237,6 +245,48 @@ class TokenBucketEngine:
         self._check(self._lib.tbe_import_rows_device(self.handle, d_ids.data_ptr(), d_v.data_ptr(),
                                                      d_t_us.data_ptr(), n, stream))
         self._rows_in_flight = (d_ids, d_v, d_t_us)   # read by the enqueued kernels
+
+    # ------------------------------------------------------------------ limit classes
+    def classes(self):
+        """Every class's (token_limit, tokens_per_period, period_ticks), class 0 first (tbe_classes)."""
+        n = c_uint32()
+        self._check(self._lib.tbe_classes(self.handle, None, 0, byref(n)))
+        out = (_capi.TbeClass * n.value)()
+        self._check(self._lib.tbe_classes(self.handle, out, n.value, byref(n)))
+        return [(c.token_limit, c.tokens_per_period, c.replenishment_period_ticks) for c in out]
+
+    def set_class(self, ids, cls) -> None:
+        """cls[ids[i]] = cls[i] from host arrays; synchronous, an invalid pair raises and writes
+        nothing (tbe_set_class)."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        cls = np.ascontiguousarray(cls, dtype=np.uint8)
+        if ids.shape != cls.shape:
+            raise ValueError("ids and cls must have the same length")
+        self._check(self._lib.tbe_set_class(self.handle, ids.ctypes.data, cls.ctypes.data, ids.shape[0]))
+
+    def set_class_device(self, d_ids, d_cls, stream: Optional[int] = None) -> None:
+        """The same from device tensors (int64 or uint64 ids, uint8 classes); enqueued, an invalid
+        pair voids the call and raises at ``synchronize()`` (tbe_set_class_device)."""
+        n = d_ids.numel()
+        if d_cls.numel() != n:
+            raise ValueError("d_ids and d_cls must have the same length")
+        d_ids, d_cls = d_ids.contiguous(), d_cls.contiguous()
+        self._check(self._lib.tbe_set_class_device(self.handle, d_ids.data_ptr(), d_cls.data_ptr(), n, stream))
+        self._cls_in_flight = (d_ids, d_cls)   # read by the enqueued kernels
+
+    def get_class(self, ids) -> np.ndarray:
+        """The classes of ids (host arrays; synchronous; tbe_get_class)."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        out = np.empty(ids.shape[0], dtype=np.uint8)
+        self._check(self._lib.tbe_get_class(self.handle, ids.ctypes.data, ids.shape[0], out.ctypes.data))
+        return out
+
+    def get_class_device(self, d_ids, d_cls, stream: Optional[int] = None) -> None:
+        """d_cls[i] = class of d_ids[i], device tensors; enqueued (tbe_get_class_device)."""
+        n = d_ids.numel()
+        if d_cls.numel() != n or not d_ids.is_contiguous() or not d_cls.is_contiguous():
+            raise ValueError("d_ids and d_cls must be contiguous and of the same length")
+        self._check(self._lib.tbe_get_class_device(self.handle, d_ids.data_ptr(), n, d_cls.data_ptr(), stream))
 
     def layout(self) -> dict:
         """{passes, r_bits, packed, hot, pipeline, narrow, medium, fold_records, digit_stream, rerank,

@@ -161,6 +161,23 @@ public:
         if (partitioned && o.PartitionLimit == 0)
             throw ArgumentException("PartitionLimit must be greater than 0.", "options");
         if (o.MaxBatch == 0) throw ArgumentException("MaxBatch must be greater than 0.", "options");
+        if (!o.Classes.empty() && !(kind == TBE_KIND_TOKEN_BUCKET && partitioned))
+            throw ArgumentException("Classes: only PartitionedRedisTokenBucketRateLimiter takes limit classes.",
+                                    "options");
+        // class 0 is the options' own three fields; each class gets the constructor checks
+        std::vector<tbe_class> extra;
+        class_limit_.push_back(o.TokenLimit);
+        for (const TokenBucketClass &k : o.Classes) {
+            if (k.TokenLimit <= 0 || k.TokensPerPeriod <= 0)
+                throw ArgumentException("Classes: both TokenLimit and TokensPerPeriod must be greater than 0.",
+                                        "options");
+            if (k.ReplenishmentPeriod.ticks < 0)
+                throw ArgumentException("Classes: ReplenishmentPeriod must be greater than or equal to TimeSpan.Zero.",
+                                        "options");
+            extra.push_back(tbe_class{k.TokenLimit, k.TokensPerPeriod, k.ReplenishmentPeriod.ticks});
+            class_limit_.push_back(k.TokenLimit);
+        }
+        if (extra.size() > 255) throw ArgumentException("Classes: at most 255 extra classes.", "options");
         clock_ = o.TimeSource ? o.TimeSource : Clock(SystemClockMicros);
         tbe_config c{};
         c.struct_size = sizeof c;
@@ -174,9 +191,19 @@ public:
         c.device = o.Device;
         c.max_batch = o.MaxBatch;
         c.zero_wait_slots = kind == TBE_KIND_APPROXIMATE ? o.ZeroWaitSlots : 0;
-        const tbe_status st = tbe_create(&c, &eng_);
+        const tbe_status st = tbe_create_classes(&c, extra.data(), (uint32_t)extra.size(), &eng_);
         if (st == TBE_EINVAL) throw ArgumentException(std::string("invalid limiter options: ") + tbe_last_error(nullptr), "options");
         if (st != TBE_OK) throw RateLimiterEngineException(st, std::string("tbe_create failed: ") + tbe_last_error(nullptr));
+        // TB:234 per class: EXPIRE ceil(min(max(capacity / fill_rate, 1), 31536000)) seconds
+        for (size_t i = 0; i < class_limit_.size(); ++i) {
+            const double rate = i == 0 ? o.FillRatePerSecond()
+                                       : tbe_fill_rate(extra[i - 1].tokens_per_period,
+                                                       extra[i - 1].replenishment_period_ticks);
+            double q = (double)class_limit_[i] / rate;
+            q = (1.0 > q) ? 1.0 : q;
+            q = (31536000.0 < q) ? 31536000.0 : q;
+            class_ttl_ms_.push_back((int64_t)std::ceil(q) * 1000);
+        }
         inbox_->core = this;
         submitter_ = std::thread([this] { Loop(); });
         if (kind != TBE_KIND_TOKEN_BUCKET && o.AutoReplenishment && o.ReplenishmentPeriod.ticks > 0)
@@ -212,8 +239,32 @@ public:
         }
     }
 
+    // The class of a resourceID (the partitioner, PartitionedRateLimiter.Create): 0 without
+    // ClassOf; a result outside [0, Classes.size()] throws to the caller.
+    int ClassOfResource(const std::string &resource) const {
+        if (!opt_.ClassOf) return 0;
+        const int c = opt_.ClassOf(resource);
+        if (c < 0 || (size_t)c >= class_limit_.size())
+            throw ArgumentOutOfRangeException("ClassOf('" + resource + "') = " + std::to_string(c) +
+                                                  " is not a class in [0, " + std::to_string(class_limit_.size() - 1) +
+                                                  "]", "resourceID");
+        return c;
+    }
+    int ClassLimit(int c) const { return class_limit_[(size_t)c]; }
+
     bool TryKeyOf(const std::string &resource, uint64_t &key) {
         const std::string bucket = opt_.InstanceName + resource;
+        {
+            std::lock_guard<std::mutex> g(dir_mu_);
+            auto it = dir_.find(bucket);
+            if (it != dir_.end()) {
+                key = it->second;
+                return true;
+            }
+        }
+        // a new name: ask the partitioner first (outside the lock; it may throw, and then no
+        // key is assigned), then look again
+        const int cls = ClassOfResource(resource);
         std::lock_guard<std::mutex> g(dir_mu_);
         auto it = dir_.find(bucket);
         if (it != dir_.end()) {
@@ -232,6 +283,22 @@ public:
         names_[key] = bucket;
         dir_.emplace(bucket, key);
         if (kind_ == TBE_KIND_APPROXIMATE) fresh_keys_.push_back(key);
+        if (class_limit_.size() > 1) {
+            // The key's class goes through the submitter's queue, enqueued while the directory
+            // is still locked: every request for this name is enqueued after it (its own caller
+            // submits next, any other caller finds the name only after this lock is released),
+            // so the class is set before the micro-batch that holds the name's first request.
+            if (key_cls_.size() <= key) key_cls_.resize(key + 1, 0);
+            key_cls_[key] = (uint8_t)cls;
+            std::lock_guard<std::mutex> gq(mu_);
+            if (!stop_) {
+                const uint8_t c8 = (uint8_t)cls;
+                q_.emplace_back(Cmd{[this, key, c8] {
+                    // (an engine error here also fails the batch that follows)
+                    (void)tbe_set_class(eng_, &key, &c8, 1);
+                }});
+            }
+        }
         return true;
     }
 
@@ -267,11 +334,8 @@ public:
         if (n == 0) return 0;
         if (kind_ == TBE_KIND_APPROXIMATE) return ReclaimIdle(n, busy);
         // TB:234: EXPIRE ceil(min(max(capacity / fill_rate, 1), 31536000)) seconds; the
-        // engine's expiry test is tbe_query's (millisecond resolution).
-        double q = (double)opt_.TokenLimit / opt_.FillRatePerSecond();
-        q = (1.0 > q) ? 1.0 : q;
-        q = (31536000.0 < q) ? 31536000.0 : q;
-        const int64_t ttl_ms = (int64_t)std::ceil(q) * 1000;
+        // engine's expiry test is tbe_query's (millisecond resolution).  With limit classes a
+        // key lapses by the TTL of its own class (class_ttl_ms_).
         const int64_t now_ms = clock_() / 1000;
         std::vector<uint8_t> is_free(n, 0);
         for (uint64_t k : free_ids_) is_free[k] = 1;
@@ -289,6 +353,7 @@ public:
             for (uint64_t j = 0; j < m; ++j) {
                 const uint64_t k = k0 + j;
                 if (is_free[k] || busy.count(k)) continue;
+                const int64_t ttl_ms = class_ttl_ms_[k < key_cls_.size() ? key_cls_[k] : 0];
                 if (t[j] != INT64_MIN && now_ms <= t[j] / 1000 + ttl_ms) continue;  // still present
                 dir_.erase(names_[k]);
                 names_[k].clear();
@@ -392,7 +457,8 @@ public:
     int LastReply(uint64_t key) {
         std::lock_guard<std::mutex> g(dir_mu_);
         auto it = last_reply_.find(key);
-        return it == last_reply_.end() ? opt_.TokenLimit : it->second;
+        if (it != last_reply_.end()) return it->second;
+        return class_limit_[key < key_cls_.size() ? key_cls_[key] : 0];   // no reply yet: a full bucket
     }
 
     struct ApproxState {
@@ -738,6 +804,9 @@ private:
     std::vector<std::string> names_;       // key -> bucket string
     std::vector<uint64_t> free_ids_;       // reclaimed keys, reused first
     std::vector<uint64_t> fresh_keys_;     // approximate kind: keys assigned since the last batch
+    std::vector<uint8_t> key_cls_;         // limit classes: key -> class (under dir_mu_; empty without classes)
+    std::vector<int> class_limit_;         // TokenLimit of every class, class 0 first
+    std::vector<int64_t> class_ttl_ms_;    // EXPIRE of every class (TB:234), in ms
     std::shared_mutex reclaim_mu_;
     std::atomic<uint64_t> reclaimed_{0};
     std::unordered_map<uint64_t, int32_t> last_reply_;
@@ -800,7 +869,7 @@ PartitionedRedisTokenBucketRateLimiter::~PartitionedRedisTokenBucketRateLimiter(
 int PartitionedRedisTokenBucketRateLimiter::GetAvailablePermits(const std::string &id) {
     core_->ThrowIfDisposed();
     uint64_t k;
-    return core_->KnownKey(id, k) ? core_->LastReply(k) : core_->options().TokenLimit;
+    return core_->KnownKey(id, k) ? core_->LastReply(k) : core_->ClassLimit(core_->ClassOfResource(id));
 }
 RateLimitLease PartitionedRedisTokenBucketRateLimiter::AttemptAcquireCore(const std::string &id, int p) {
     core_->ThrowIfDisposed();

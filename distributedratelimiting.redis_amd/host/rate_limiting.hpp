@@ -155,6 +155,15 @@ enum BatchMode { kTbAcquire = 0, kQueueWait = 1, kQueueAttempt = 2, kApproxWait 
 // RedisTokenBucketRateLimiterOptions (TBO:9-85).  The Redis connection settings
 // (Configuration, ConfigurationOptions, ConnectionMultiplexerFactory, ProfilingSession)
 // become the engine settings below: the "connection" is a GPU.
+// One limit class of a partitioned token-bucket limiter: the three options that the
+// reference interpolates into a limiter's script (TB:184-185), so that differently configured
+// limiters share one store (per-endpoint policies, plans).
+struct TokenBucketClass {
+    int TokenLimit = 0;
+    int TokensPerPeriod = 0;
+    TimeSpan ReplenishmentPeriod = TimeSpan::FromSeconds(1);
+};
+
 struct RedisTokenBucketRateLimiterOptions {
     TimeSpan ReplenishmentPeriod = TimeSpan::FromSeconds(1);      // TBO:14-22
     int TokensPerPeriod = 0;                                      // TBO:24-32
@@ -165,6 +174,15 @@ struct RedisTokenBucketRateLimiterOptions {
     uint64_t MaxBatch = 1u << 16;  // largest micro-batch one engine call takes
     Clock TimeSource;              // default SystemClockMicros
     std::function<void(const BatchTrace &)> OnBatch;  // diagnostics (tests)
+    // PartitionedRedisTokenBucketRateLimiter only (every other limiter throws
+    // ArgumentException when Classes is non-empty): the extra limit classes 1, 2, ...; class 0
+    // is the three options above.  ClassOf is the partitioner of PartitionedRateLimiter.Create:
+    // called when a resourceID takes a key (a key reused after ReclaimExpired included), its
+    // result in [0, Classes.size()] is that bucket's class; anything else throws
+    // ArgumentOutOfRangeException to that caller and assigns no key.  Without ClassOf every
+    // resourceID is in class 0.
+    std::vector<TokenBucketClass> Classes;
+    std::function<int(const std::string &resourceID)> ClassOf;
     double FillRatePerSecond() const;                             // TBO:82-85
 };
 
@@ -247,7 +265,8 @@ private:
 
 // PTB:7-212.  BucketId = InstanceName + resourceID (PTB:42), mapped to a dense key.
 // GetAvailablePermits(resourceID) reports the last script reply for that bucket (the
-// reference returns 0, PTB:25-28).
+// reference returns 0, PTB:25-28); for a resourceID that holds no key, the TokenLimit of its
+// class (ClassOf), without assigning a key.
 class PartitionedRedisTokenBucketRateLimiter final : public PartitionedRateLimiter<std::string> {
 public:
     explicit PartitionedRedisTokenBucketRateLimiter(const RedisTokenBucketRateLimiterOptions &options);

@@ -266,6 +266,10 @@ def save(path, engine, ts_us: int, directory=None, stream: Optional[int] = None)
     ``export_live``).  Returns the number of rows written.  An ``ApproximateEngine``'s file
     holds its {v, p, t} tier rows (array ``p`` beside ``v``) for the ids the directory
     holds; local tiers and client views are in-process state and not saved."""
+    if getattr(engine, "classed", False):
+        raise ValueError("snapshot.save: the engine holds limit classes, and a snapshot file carries one "
+                         "limiter's options and no per-key class; save a classed engine's rows with "
+                         "export_live and its classes with get_class")
     approx = int(engine.config.kind) == KIND_APPROXIMATE
     if approx:
         # every synced id holds a tier row, held by a name or not: skip the ids the directory

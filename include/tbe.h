@@ -124,6 +124,53 @@ double tbe_fill_rate(int32_t tokens_per_period, int64_t replenishment_period_tic
  * table (16 B per key) on the device, every key absent. */
 tbe_status tbe_create(const tbe_config *config, tbe_engine **out_engine);
 
+/* ---- Limit classes: one token-bucket engine, up to 256 differently
+ * configured limiters.  In the reference TokenLimit and FillRatePerSecond are interpolated
+ * into the script text (TB:184-185), so any number of limiters share one Redis; here every
+ * key belongs to one class and is decided by the unchanged script arithmetic with its
+ * class's {capacity, fill_rate, EXPIRE seconds}. */
+typedef struct tbe_class {
+    int32_t token_limit;                  /* TokenLimit (TBO:43), > 0 */
+    int32_t tokens_per_period;            /* TokensPerPeriod (TBO:30), > 0 */
+    int64_t replenishment_period_ticks;   /* ReplenishmentPeriod in .NET ticks, > 0 */
+} tbe_class;
+
+/* tbe_create with extra[0..n_extra) as classes 1..n_extra; class 0 is the config's own
+ * three options and every key of a new engine is in class 0.  Each class gets the
+ * constructor checks and the parameters tbe_create derives (tbe_fill_rate, then the TB:234
+ * clamp).  n_extra == 0 is tbe_create.  TBE_EINVAL, before the device is touched: n_extra >
+ * 255, extra == NULL with n_extra > 0, a class that fails the checks, kind !=
+ * TBE_KIND_TOKEN_BUCKET.  A classed engine is laid out as with TBE_FLAG_NO_PACK |
+ * TBE_FLAG_NO_HOT | TBE_FLAG_NO_NARROW (tbe_layout reports it): wide records, 4-byte
+ * replies, no hot-key runs.
+ * On a classed engine tbe_query, tbe_expired_device, tbe_export_live(_device) and the
+ * fold judge a key's lapse with its class's TTL, and an absent or lapsed row starts from its
+ * class's TokenLimit; field v of an absent row (tbe_export_state) is unspecified. */
+tbe_status tbe_create_classes(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
+                              tbe_engine **out_engine);
+
+/* The engine's classes, class 0 first: out[0..min(capacity, *n_classes)); out may be NULL. */
+tbe_status tbe_classes(const tbe_engine *engine, tbe_class *out, uint32_t capacity, uint32_t *n_classes);
+
+/* cls[d_ids[i]] = d_cls[i].  The row {v, t_us} stays: the key's next evaluation clamps with
+ * the new TokenLimit and refills at the new rate, as when another limiter's script runs on
+ * the same Redis hash; the lapse test uses the new class from here on (the reference keeps
+ * the last granting script's EXPIRE until the next grant).  Contract of
+ * tbe_import_rows_device: ordered after every batch enqueued before the call and before
+ * every batch after it, `stream` as in tbe_expired_device; unique ids; every pair is
+ * validated before any is written, and an id >= n_keys or a class >= the number of classes
+ * voids the whole call, reported by tbe_synchronize.  Without extra classes only class 0 is
+ * valid.  Token-bucket kind. */
+tbe_status tbe_set_class_device(tbe_engine *engine, const uint64_t *d_ids, const uint8_t *d_cls, uint64_t n,
+                                void *stream);
+/* The same from host buffers; synchronous, an invalid pair: TBE_EINVAL, nothing written. */
+tbe_status tbe_set_class(tbe_engine *engine, const uint64_t *ids, const uint8_t *cls, uint64_t n);
+/* d_cls[i] = class of d_ids[i] (ordering and `stream` as above); an id >= n_keys reads 0
+ * and is reported by tbe_synchronize (host form: TBE_EINVAL). */
+tbe_status tbe_get_class_device(tbe_engine *engine, const uint64_t *d_ids, uint64_t n, uint8_t *d_cls,
+                                void *stream);
+tbe_status tbe_get_class(tbe_engine *engine, const uint64_t *ids, uint64_t n, uint8_t *cls);
+
 /* Replaces Dispose / DisposeAsyncCore (TB:85-109).  NULL is ignored. */
 void tbe_destroy(tbe_engine *engine);
 
@@ -193,7 +240,9 @@ tbe_status tbe_import_state(tbe_engine *engine, uint64_t first, uint64_t count, 
  * requests is never dead.  Approximate kind: TBE_EINVAL (its local tier is in-process
  * state without an expiry).  clear != 0 also rewrites every lapsed row of the range
  * absent, which decides identically at ts_us and later but keeps a reused key id on a
- * full bucket even if a later timestamp steps back before the lapse.
+ * full bucket even if a later timestamp steps back before the lapse.  The keys' classes
+ * (tbe_set_class) are left alone: a caller that hands a reclaimed id to a new key sets its
+ * class before that key's first batch.
  * Ordered after every batch already enqueued on the engine (pipelined ones included),
  * as tbe_export_state is; `stream` as in tbe_acquire_batch_device: the scan waits for
  * work enqueued on it and it waits for the flags.  ts_us < 0 or a range past n_keys:

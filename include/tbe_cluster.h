@@ -160,7 +160,10 @@ tbe_status tbe_dir_reclaim_device(tbe_directory *dir, const uint8_t *d_dead,
  * tbe_expired_device refuses, included) is TBE_EINVAL and nothing changes.  The lapsed rows
  * are written back absent, so a reused id starts from a full bucket whatever timestamp
  * comes next.  keep_ids is a host array (may be NULL when n_keep is 0); *n_reclaimed =
- * keys removed.  One more byte per id of capacity is held for the flags. */
+ * keys removed.  One more byte per id of capacity is held for the flags.
+ * On an engine with limit classes (tbe_create_classes) each key lapses by its own class's
+ * TTL, and a reclaimed id keeps the class byte of the key that held it: the caller sets the
+ * class of the new key (tbe_set_class) before that key's first batch. */
 tbe_status tbe_dir_reclaim(tbe_directory *dir, tbe_engine *engine, int64_t ts_us,
                            const uint64_t *keep_ids, uint64_t n_keep, uint64_t *n_reclaimed);
 

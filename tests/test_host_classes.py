@@ -1,0 +1,56 @@
+"""Limit classes through the C++ host classes (tests/host/classes_test.cpp): Options.Classes
+and Options.ClassOf of PartitionedRedisTokenBucketRateLimiter.  CPU: option validation.  GPU,
+on an injected clock: two names in classes with TokenLimit 2 and 5 give hand-checked grant and
+deny sequences, GetAvailablePermits of an unseen name is per class, a key reclaimed and reused
+in another class starts from that class's full bucket, a ClassOf result out of range throws
+and assigns no key.  The program is built by __graft_entry__.build() (relative rpaths, so the
+binary built on the build machine runs on the GPU machine)."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "distributedratelimiting.redis_amd")
+SRC = os.path.join(ROOT, "tests", "host", "classes_test.cpp")
+BIN = os.path.join(ROOT, "tests", "host", "classes_test")
+
+
+def build_classes_test() -> str:
+    """Compile the test program against libtbe_host.so and libtbe.so."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_tbe_build", os.path.join(PKG, "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    mod.build_host()
+    deps = [SRC, mod.HOST_LIB, os.path.join(PKG, "host", "rate_limiting.hpp"), os.path.join(ROOT, "include", "tbe.h")]
+    if os.path.exists(BIN) and all(os.path.getmtime(d) <= os.path.getmtime(BIN) for d in deps):
+        return BIN
+    cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", os.path.join(ROOT, "include"),
+           "-I", os.path.join(PKG, "host"), "-o", BIN + ".tmp", SRC,
+           "-L", PKG, "-ltbe_host", "-ltbe", "-L", "/opt/rocm/lib",
+           "-Wl,-rpath,$ORIGIN/../../distributedratelimiting.redis_amd"]
+    subprocess.run(cmd, check=True)
+    os.replace(BIN + ".tmp", BIN)
+    return BIN
+
+
+def _run(exe: str, mode: str) -> str:
+    p = subprocess.run([exe, mode], capture_output=True, text=True, timeout=120)
+    print(p.stdout, p.stderr)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert " 0 failed" in p.stdout
+    return p.stdout
+
+
+def test_host_classes_cpu():
+    out = _run(build_classes_test(), "cpu")
+    assert "9 checks passed" in out
+
+
+@pytest.mark.gpu
+def test_host_classes_gpu(gpu):
+    if not os.path.exists(BIN):
+        pytest.fail("tests/host/classes_test is not built (run __graft_entry__.build())")
+    out = _run(BIN, "gpu")
+    assert "43 checks passed" in out
