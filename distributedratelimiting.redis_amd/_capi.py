@@ -27,6 +27,7 @@ TBE_FLAG_NO_NARROW = 0x10
 TBE_FLAG_UNSCATTER_ALL = 0x20
 TBE_FLAG_HIST_RECORDS = 0x40
 TBE_FLAG_RERANK = 0x80
+TBE_FLAG_STATS = 0x200
 STAGES = ("hist", "colscan", "scatter", "bounds", "fold", "unscatter", "hot")
 
 # Every symbol include/tbe.h declares (tests/test_capi_symbols.py checks the header too).
@@ -44,7 +45,11 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_approx_idle_device", "tbe_approx_reset_device", "tbe_approx_idle", "tbe_approx_reset",
             "tbe_approx_export_live_device", "tbe_approx_export_live", "tbe_approx_import_rows_device",
             "tbe_approx_import_rows", "tbe_create_classes", "tbe_classes", "tbe_set_class_device",
-            "tbe_set_class", "tbe_get_class_device", "tbe_get_class")
+            "tbe_set_class", "tbe_get_class_device", "tbe_get_class", "tbe_stats_batch_device",
+            "tbe_stats_batch", "tbe_stats_totals", "tbe_stats_export", "tbe_stats_import")
+# k_stats_batch's shape (csrc/tbe_stats.hpp): requests per workgroup trip and slots of its
+# LDS table; the tests size their cases by them
+STATS_TILE, STATS_SLOTS = 4096, 2048
 TBE_WAIT_FAILED, TBE_WAIT_GRANTED, TBE_WAIT_QUEUED, TBE_WAIT_REJECTED = 0, 1, 2, 3
 TBE_RETRY_NONE, TBE_RETRY_OVERFLOW = -1, 2**63 - 1   # retry_after_ticks of the approximate kind
 
@@ -298,6 +303,17 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_sdir_reclaim.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_uint64, POINTER(c_uint64)]
     lib.tbe_numfmt_device.restype = c_int32
     lib.tbe_numfmt_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
+    lib.tbe_stats_batch_device.restype = c_int32
+    lib.tbe_stats_batch_device.argtypes = [c_void_p, c_void_p, c_uint64, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]
+    lib.tbe_stats_batch.restype = c_int32
+    lib.tbe_stats_batch.argtypes = [c_void_p, c_void_p, c_uint64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.tbe_stats_totals.restype = c_int32
+    lib.tbe_stats_totals.argtypes = [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]
+    lib.tbe_stats_export.restype = c_int32
+    lib.tbe_stats_export.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]
+    lib.tbe_stats_import.restype = c_int32
+    lib.tbe_stats_import.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]
     lib.tbe_layout.restype = c_int32
     lib.tbe_layout.argtypes = [c_void_p, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]
     lib.tbe_stage_times.restype = c_int32

@@ -4350,6 +4350,9 @@ __global__ void k_arows_write(double *__restrict__ gv, double *__restrict__ gp, 
     }
 }
 
+// ----------------------------------------------------------------------------- lease statistics
+#include "tbe_stats.hpp"
+
 // ----------------------------------------------------------------------------- host side
 enum Stage { ST_HIST = 0, ST_COLSCAN, ST_SCATTER, ST_BOUNDS, ST_FOLD, ST_UNSCATTER, ST_HOT, ST_COUNT };
 
@@ -4497,6 +4500,11 @@ struct tbe_engine {
     // allocated by the first export) and k_rows_check's flag
     unsigned long long *live_tiles = nullptr;
     uint32_t *rows_bad = nullptr;
+    // lease statistics (TBE_FLAG_STATS): ok[k] and failed[k] per key and the
+    // engine's two totals, allocated at create on an engine with the flag and nowhere else
+    unsigned long long *st_ok = nullptr, *st_failed = nullptr, *st_tot = nullptr;
+    bool stats() const { return st_ok != nullptr; }
+    StatsView stats_view() const { return StatsView{st_ok, st_failed, st_tot}; }
     // host-buffer path staging
     hipStream_t cin = nullptr, cout = nullptr;   // chunked pinned path: copy-in / copy-out streams
     hipStream_t cin2 = nullptr;                  // second copy-in stream (TBE_CIN_STREAMS == 2)
@@ -5188,6 +5196,23 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
             w.err, e->sticky);
     stage_end(e, ST_UNSCATTER, sf);
     if (unrank) k_sticky<<<1, 64, 0, sf>>>(w.err, e->sticky);   // (otherwise the final unscatter did it)
+    if (e->stats()) {
+        // lease statistics: behind the batch's last reply-writing kernel and before the events
+        // that release the caller's stream and this workspace (the kernels read the caller's
+        // keys, the final reply bytes and w.err)
+        const unsigned sgrid = (unsigned)std::min<uint64_t>((n + kStatsTile - 1) / kStatsTile, kStatsMaxBlocks);
+        k_stats_batch<<<sgrid, kStatsBlock, 0, sf>>>(keys, granted, n, w.err, e->stats_view());
+        // NewestFirst evictions fail the evicted lease.  A chunk of a chunked host batch
+        // (in_ready) leaves them to its caller: the log runs on over the chunks.
+        const int32_t order = approx ? e->ap.order : e->qp.order;
+        if (wait && e->wait_mode == 1 && order == 1 && !in_ready && e->ev_cause)
+            k_stats_log<<<64, kStatsBlock, 0, sf>>>(e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu),
+                                                    e->ev_cause, keys, n, ai_base, nullptr, e->cfg.n_keys, w.err,
+                                                    e->st_failed, e->st_tot + 1);
+        if (e->qtick.ts >= 0 && e->qtick.count)  // the fused tick's grants (tbe_wait_batch_tick_device)
+            k_stats_log<<<64, kStatsBlock, 0, sf>>>(e->qtick.count, e->qtick.cap, nullptr, nullptr, 0, 0,
+                                                    e->qtick.keyseq, e->cfg.n_keys, w.err, e->st_ok, e->st_tot);
+    }
     HIP_TRY(e, hipGetLastError());
     if (pipe) {
         HIP_TRY(e, hipEventRecord(w.done, sf));
@@ -5436,6 +5461,11 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
         for (auto &hs : e->hot)
             if (dalloc(&hs, sizeof(HotSet)) != hipSuccess) return bail(TBE_ENOMEM);
     if (dalloc(&e->sticky, sizeof(uint32_t)) != hipSuccess) return bail(TBE_ENOMEM);
+    if (c.flags & TBE_FLAG_STATS) {   // 16 B per key
+        if (dalloc(&e->st_ok, c.n_keys * sizeof(unsigned long long)) != hipSuccess) return bail(TBE_ENOMEM);
+        if (dalloc(&e->st_failed, c.n_keys * sizeof(unsigned long long)) != hipSuccess) return bail(TBE_ENOMEM);
+        if (dalloc(&e->st_tot, 2 * sizeof(unsigned long long)) != hipSuccess) return bail(TBE_ENOMEM);
+    }
     if (c.kind == TBE_KIND_QUEUEING) {
         e->qp.token_limit = c.token_limit;
         e->qp.queue_limit = c.queue_limit;
@@ -5476,6 +5506,9 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
     zero(e->qhdr, qhdr_n * (e->qh32 ? sizeof(uint32_t) : sizeof(uint64_t)));
     zero(e->ring, ring_n * sizeof(uint64_t));
     zero(e->counters, 2 * sizeof(uint32_t));
+    zero(e->st_ok, c.n_keys * sizeof(unsigned long long));
+    zero(e->st_failed, c.n_keys * sizeof(unsigned long long));
+    zero(e->st_tot, 2 * sizeof(unsigned long long));
     for (auto &w : e->ws)
         if (w.bsflags && w.bs_fresh) {
             zero(w.bsflags, kBsMaxBlocks * sizeof(unsigned long long));
@@ -5532,6 +5565,9 @@ void tbe_destroy(tbe_engine *e) {
     dfree(e->sticky);
     dfree(e->live_tiles);
     dfree(e->rows_bad);
+    dfree(e->st_ok);
+    dfree(e->st_failed);
+    dfree(e->st_tot);
     for (auto &hs : e->hot) dfree(hs);
     for (auto &ev : e->ev_pool)
         if (ev) (void)hipEventDestroy(ev);
@@ -5802,6 +5838,8 @@ tbe_status tbe_expired_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint
     else
         k_expired<<<blocks, kBlock, 0, st>>>(e->table, (const uint64_t *)nullptr, first, count, exp_lt,
                                              e->params.cap, clear, d_dead);
+    // lease statistics are per id: a key flagged dead hands its id on with both counters at 0
+    if (clear && e->stats()) k_stats_zero<<<blocks, kBlock, 0, st>>>(d_dead, first, count, e->stats_view());
     HIP_TRY(e, hipGetLastError());
     if (caller && caller != st) {
         HIP_TRY(e, hipEventRecord(e->ev_out, st));
@@ -6063,6 +6101,16 @@ tbe_status tbe_get_class(tbe_engine *e, const uint64_t *ids, uint64_t n, uint8_t
     return TBE_OK;
 }
 
+// Lease statistics: every grant a drain logged counts ok on its key (keyseq >> 16), behind
+// the drain on its stream.  The drain logs never drop an entry (their capacities cover
+// tbe_refresh_bound), so the device-side count is the number of grants.
+static void stats_drained(tbe_engine *e, const uint64_t *keyseq, const uint32_t *count, uint32_t cap,
+                          hipStream_t st) {
+    if (!e->stats()) return;
+    k_stats_log<<<64, kStatsBlock, 0, st>>>(count, cap, nullptr, nullptr, 0, 0u, keyseq, e->cfg.n_keys, nullptr,
+                                            e->st_ok, e->st_tot);
+}
+
 // Ring entries of all keys: the most any sequence of batches can leave queued.
 static uint64_t ring_entries(const tbe_engine *e) {
     const uint32_t cap = e->cfg.kind == TBE_KIND_APPROXIMATE ? e->ap.cap : e->qp.cap;
@@ -6283,6 +6331,15 @@ static tbe_status status_chunked(tbe_engine *e, const uint64_t *keys, const int3
                                   e->cout));
     }
     HIP_TRY(e, hipMemcpyAsync(nev, e->counters, sizeof(uint32_t), hipMemcpyDeviceToHost, e->cout));
+    const int32_t order = e->cfg.kind == TBE_KIND_APPROXIMATE ? e->ap.order : e->qp.order;
+    if (e->stats() && e->wait_mode == 1 && order == 1) {
+        // the evictions of all chunks, once: their causes index the whole staged batch
+        k_stats_log<<<64, kStatsBlock, 0, e->stream>>>(e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu),
+                                                       e->ev_cause, e->d_keys, n, 0u, nullptr, e->cfg.n_keys, nullptr,
+                                                       e->st_failed, e->st_tot + 1);
+        HIP_TRY(e, hipGetLastError());
+        HIP_TRY(e, hipStreamSynchronize(e->stream));   // (it reads the staged keys the next call overwrites)
+    }
     HIP_TRY(e, hipStreamSynchronize(e->cout));
     return TBE_OK;
 }
@@ -6423,6 +6480,7 @@ tbe_status tbe_refresh(tbe_engine *e, int64_t ts_us, uint64_t *n_granted) {
                                                     e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
                                                     (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu));
     });
+    stats_drained(e, e->log_keyseq, e->counters + 1, (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), st);
     HIP_TRY(e, hipGetLastError());
     uint32_t cnt = 0;
     HIP_TRY(e, hipMemcpyAsync(&cnt, e->counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -6479,6 +6537,7 @@ tbe_status tbe_refresh_device(tbe_engine *e, int64_t ts_us, uint64_t *d_keyseq, 
                                                     d_keyseq, d_request_id, d_remaining, d_count,
                                                     (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu));
     });
+    stats_drained(e, d_keyseq, d_count, (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu), st);
     HIP_TRY(e, hipGetLastError());
     e->queued_exact = false;   // queued_total stays an upper bound
     return TBE_OK;
@@ -6582,6 +6641,7 @@ static tbe_status approx_sync(tbe_engine *e, const int32_t *d_all_counts, uint32
         e->cfg.n_keys, e->alocal, e->aclient, e->gv, e->gp, e->gt, e->ring, e->ap, d_all_counts,
         n_clients, my_client, ts_us, stagger_us, e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
         (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), n_clients != 1 ? 1u : 0u);
+    stats_drained(e, e->log_keyseq, e->counters + 1, (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), st);
     HIP_TRY(e, hipGetLastError());
     e->aclient_lazy = n_clients == 1;
     uint32_t cnt = 0;
@@ -6744,6 +6804,7 @@ tbe_status tbe_approx_reset_device(tbe_engine *e, uint64_t first, uint64_t count
     const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
     k_approx_reset<<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient, e->gv, e->gp, e->gt, first, count, d_flags,
                                                      e->ap.token_limit);
+    if (e->stats()) k_stats_zero<<<blocks, kBlock, 0, e->stream>>>(d_flags, first, count, e->stats_view());
     HIP_TRY(e, hipGetLastError());
     e->queued_exact = false;   // a flagged key's queue, if it had one, is gone: queued_total is a bound
     return join_out(e, caller);
@@ -7070,6 +7131,145 @@ tbe_status tbe_queue_cancel(tbe_engine *e, const uint64_t *keys, const int64_t *
     }
     e->queued_total -= std::min(e->queued_total, m);
     *n_cancelled = m;
+    return TBE_OK;
+}
+
+// ---- lease statistics.  The batched query runs on the engine's stream, a
+// caller's stream joined before and after: tbe_expired_device's ordering.
+static const char *kNoStats = "engine created without TBE_FLAG_STATS";
+
+tbe_status tbe_stats_batch_device(tbe_engine *e, const uint64_t *d_keys, uint64_t n, int64_t ts_us, uint64_t *d_ok,
+                                  uint64_t *d_failed, int32_t *d_available, uint32_t *d_queued, void *stream) {
+    if (!e) return TBE_EINVAL;
+    if ((d_ok || d_failed) && !e->stats()) return fail(e, TBE_EINVAL, kNoStats);
+    const bool approx = e->cfg.kind == TBE_KIND_APPROXIMATE;
+    if (!approx && ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+    if (n == 0) return TBE_OK;
+    if (!d_keys) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (!e->rows_bad) HIP_TRY(e, hipMalloc(&e->rows_bad, sizeof(uint32_t)));
+    hipStream_t st = e->stream, caller = (hipStream_t)stream;
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_in, caller));
+        HIP_TRY(e, hipStreamWaitEvent(st, e->ev_in, 0));
+    }
+    HIP_TRY(e, hipMemsetAsync(e->rows_bad, 0, sizeof(uint32_t), st));
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192);
+    // the validating pass ends before anything is written (one stream)
+    k_stats_check<<<blocks, kBlock, 0, st>>>(d_keys, n, e->cfg.n_keys, e->rows_bad);
+    auto *ok = reinterpret_cast<unsigned long long *>(d_ok);
+    auto *failed = reinterpret_cast<unsigned long long *>(d_failed);
+    const uint64_t *no_qhdr = nullptr;
+    if (approx)
+        k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)nullptr, e->params, no_qhdr, e->alocal,
+                                                e->stats_view(), ok, failed, d_available, d_queued, e->rows_bad,
+                                                e->sticky);
+    else if (e->cfg.kind == TBE_KIND_QUEUEING)
+        with_qhdr(e, [&](auto *qh) {
+            using HW = std::remove_pointer_t<decltype(qh)>;
+            k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)e->table, e->params,
+                                                    (const HW *)qh, (const ALocal *)nullptr, e->stats_view(), ok,
+                                                    failed, d_available, d_queued, e->rows_bad, e->sticky);
+        });
+    else if (e->cls)   // per key: the kernel takes each key's parameters from its class
+        k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)e->table, e->params, no_qhdr,
+                                                (const ALocal *)nullptr, e->stats_view(), ok, failed, d_available,
+                                                d_queued, e->rows_bad, e->sticky, e->cls_view());
+    else
+        k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)e->table, e->params, no_qhdr,
+                                                (const ALocal *)nullptr, e->stats_view(), ok, failed, d_available,
+                                                d_queued, e->rows_bad, e->sticky);
+    HIP_TRY(e, hipGetLastError());
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_out, st));
+        HIP_TRY(e, hipStreamWaitEvent(caller, e->ev_out, 0));
+    }
+    return TBE_OK;
+}
+
+tbe_status tbe_stats_batch(tbe_engine *e, const uint64_t *keys, uint64_t n, int64_t ts_us, uint64_t *ok,
+                           uint64_t *failed, int32_t *available, uint32_t *queued) {
+    if (!e) return TBE_EINVAL;
+    if ((ok || failed) && !e->stats()) return fail(e, TBE_EINVAL, kNoStats);
+    if (e->cfg.kind != TBE_KIND_APPROXIMATE && ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+    if (n == 0) return TBE_OK;
+    if (!keys) return fail(e, TBE_EINVAL, "null buffer");
+    for (uint64_t i = 0; i < n; ++i)
+        if (keys[i] >= e->cfg.n_keys) return fail(e, TBE_EINVAL, "key out of range");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch, whatever its stream
+    void *buf = nullptr;
+    HIP_TRY(e, hipMalloc(&buf, n * 32));
+    uint64_t *d_keys = static_cast<uint64_t *>(buf);
+    uint64_t *d_ok = d_keys + n, *d_failed = d_ok + n;
+    int32_t *d_av = reinterpret_cast<int32_t *>(d_failed + n);
+    uint32_t *d_q = reinterpret_cast<uint32_t *>(d_av + n);
+    hipError_t hrc = hipMemcpy(d_keys, keys, n * sizeof(uint64_t), hipMemcpyHostToDevice);
+    tbe_status rc = TBE_OK;
+    if (hrc == hipSuccess)
+        rc = tbe_stats_batch_device(e, d_keys, n, ts_us, ok ? d_ok : nullptr, failed ? d_failed : nullptr,
+                                    available ? d_av : nullptr, queued ? d_q : nullptr, nullptr);
+    if (hrc == hipSuccess && rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
+    if (hrc == hipSuccess && rc == TBE_OK && ok) hrc = hipMemcpy(ok, d_ok, n * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if (hrc == hipSuccess && rc == TBE_OK && failed)
+        hrc = hipMemcpy(failed, d_failed, n * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if (hrc == hipSuccess && rc == TBE_OK && available)
+        hrc = hipMemcpy(available, d_av, n * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (hrc == hipSuccess && rc == TBE_OK && queued)
+        hrc = hipMemcpy(queued, d_q, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
+    return TBE_OK;
+}
+
+tbe_status tbe_stats_totals(tbe_engine *e, uint64_t *ok, uint64_t *failed) {
+    if (!e || !ok || !failed) return TBE_EINVAL;
+    if (!e->stats()) return fail(e, TBE_EINVAL, kNoStats);
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch, whatever its stream
+    unsigned long long t[2] = {0, 0};
+    HIP_TRY(e, hipMemcpy(t, e->st_tot, sizeof t, hipMemcpyDeviceToHost));
+    *ok = t[0];
+    *failed = t[1];
+    return TBE_OK;
+}
+
+tbe_status tbe_stats_export(tbe_engine *e, uint64_t first, uint64_t count, uint64_t *ok, uint64_t *failed) {
+    if (!e) return TBE_EINVAL;
+    if (!e->stats()) return fail(e, TBE_EINVAL, kNoStats);
+    if (first > e->cfg.n_keys || count > e->cfg.n_keys - first)
+        return fail(e, TBE_EINVAL, "range out of bounds");
+    if (count == 0) return TBE_OK;
+    if (!ok || !failed) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());
+    HIP_TRY(e, hipMemcpy(ok, e->st_ok + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(failed, e->st_failed + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return TBE_OK;
+}
+
+tbe_status tbe_stats_import(tbe_engine *e, uint64_t first, uint64_t count, const uint64_t *ok,
+                            const uint64_t *failed) {
+    if (!e) return TBE_EINVAL;
+    if (!e->stats()) return fail(e, TBE_EINVAL, kNoStats);
+    if (first > e->cfg.n_keys || count > e->cfg.n_keys - first)
+        return fail(e, TBE_EINVAL, "range out of bounds");
+    if (count == 0) return TBE_OK;
+    if (!ok || !failed) return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());
+    // the totals move by the difference (modulo 2^64, as the counters themselves count)
+    std::vector<uint64_t> old(count);
+    unsigned long long t[2] = {0, 0};
+    HIP_TRY(e, hipMemcpy(t, e->st_tot, sizeof t, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(old.data(), e->st_ok + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < count; ++i) t[0] += ok[i] - old[i];
+    HIP_TRY(e, hipMemcpy(old.data(), e->st_failed + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < count; ++i) t[1] += failed[i] - old[i];
+    HIP_TRY(e, hipMemcpy(e->st_ok + first, ok, count * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(e, hipMemcpy(e->st_failed + first, failed, count * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(e, hipMemcpy(e->st_tot, t, sizeof t, hipMemcpyHostToDevice));
     return TBE_OK;
 }
 

@@ -60,9 +60,10 @@ class TokenBucketEngine:
                  queue_limit: int = 0, queue_order: int = 0, pack: bool = True, hot: bool = True,
                  pipeline: bool = True, narrow: bool = True, zero_wait_slots: int = 0,
                  fold_records: bool = True, digit_stream: bool = True, rerank: bool = False,
-                 classes=None):
+                 classes=None, stats: bool = False):
         """classes: extra limit classes 1.. as (token_limit, tokens_per_period, period_ticks)
-        (tbe_create_classes; class 0 is this engine's own three options)."""
+        (tbe_create_classes; class 0 is this engine's own three options).
+        stats: keep lease statistics (TBE_FLAG_STATS; ``statistics``, ``stats_totals``)."""
         self._lib = _capi.load()
         # stage_timing: True (every stage), "fold" (the fold alone) or False
         flags = (_capi.TBE_FLAG_FOLD_TIMING if stage_timing == "fold"
@@ -81,6 +82,9 @@ class TokenBucketEngine:
             flags |= _capi.TBE_FLAG_HIST_RECORDS
         if rerank:
             flags |= _capi.TBE_FLAG_RERANK
+        if stats:
+            flags |= _capi.TBE_FLAG_STATS
+        self.stats = bool(stats)
         self.config = _capi.make_config(n_keys, token_limit, tokens_per_period, period_ticks,
                                         kind=self.KIND, queue_limit=queue_limit,
                                         queue_order=queue_order, device=device, flags=flags,
@@ -287,6 +291,57 @@ class TokenBucketEngine:
         if d_cls.numel() != n or not d_ids.is_contiguous() or not d_cls.is_contiguous():
             raise ValueError("d_ids and d_cls must be contiguous and of the same length")
         self._check(self._lib.tbe_get_class_device(self.handle, d_ids.data_ptr(), n, d_cls.data_ptr(), stream))
+
+    # ------------------------------------------------------------------ lease statistics
+    def statistics(self, keys, ts_us: int = 0):
+        """(ok u64, failed u64, available i32, queued u32) of `keys` (host array; keys may
+        repeat): the GA ``GetStatistics()`` fields per key (tbe_stats_batch; synchronous).
+        Without ``stats=True`` ok and failed are None; available and queued work on every
+        engine.  ts_us: when `available` is evaluated (ignored by the approximate kind)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        n = keys.shape[0]
+        ok = np.empty(n, dtype=np.uint64) if self.stats else None
+        failed = np.empty(n, dtype=np.uint64) if self.stats else None
+        avail = np.empty(n, dtype=np.int32)
+        queued = np.empty(n, dtype=np.uint32)
+        ptr = (lambda a: None if a is None else a.ctypes.data)
+        self._check(self._lib.tbe_stats_batch(self.handle, keys.ctypes.data, n, ts_us, ptr(ok), ptr(failed),
+                                              avail.ctypes.data, queued.ctypes.data))
+        return ok, failed, avail, queued
+
+    def statistics_device(self, d_keys, ts_us: int = 0, d_ok=None, d_failed=None, d_available=None,
+                          d_queued=None, stream: Optional[int] = None) -> None:
+        """The same into device tensors (int64 ok / failed, int32 available and queued), any of
+        which may be None; enqueued, a key >= n_keys voids the call and raises at
+        ``synchronize()`` (tbe_stats_batch_device)."""
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        self._check(self._lib.tbe_stats_batch_device(self.handle, d_keys.data_ptr(), d_keys.numel(), ts_us,
+                                                     ptr(d_ok), ptr(d_failed), ptr(d_available), ptr(d_queued),
+                                                     stream))
+
+    def stats_totals(self) -> Tuple[int, int]:
+        """(TotalSuccessfulLeases, TotalFailedLeases) of the whole engine (tbe_stats_totals)."""
+        ok, failed = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.tbe_stats_totals(self.handle, byref(ok), byref(failed)))
+        return ok.value, failed.value
+
+    def stats_export(self, first: int = 0, count: Optional[int] = None):
+        """(ok u64, failed u64) of keys [first, first + count) (tbe_stats_export)."""
+        if count is None:
+            count = self.n_keys - first
+        ok = np.empty(count, dtype=np.uint64)
+        failed = np.empty(count, dtype=np.uint64)
+        self._check(self._lib.tbe_stats_export(self.handle, first, count, ok.ctypes.data, failed.ctypes.data))
+        return ok, failed
+
+    def stats_import(self, ok, failed, first: int = 0) -> None:
+        """Counters of keys [first, first + len) from host arrays; the totals move by the
+        difference (tbe_stats_import)."""
+        ok = np.ascontiguousarray(ok, dtype=np.uint64)
+        failed = np.ascontiguousarray(failed, dtype=np.uint64)
+        if ok.shape != failed.shape:
+            raise ValueError("ok and failed must have the same length")
+        self._check(self._lib.tbe_stats_import(self.handle, first, ok.shape[0], ok.ctypes.data, failed.ctypes.data))
 
     def layout(self) -> dict:
         """{passes, r_bits, packed, hot, pipeline, narrow, medium, fold_records, digit_stream, rerank,

@@ -191,6 +191,7 @@ public:
         c.device = o.Device;
         c.max_batch = o.MaxBatch;
         c.zero_wait_slots = kind == TBE_KIND_APPROXIMATE ? o.ZeroWaitSlots : 0;
+        if (o.TrackStatistics) c.flags |= TBE_FLAG_STATS;
         const tbe_status st = tbe_create_classes(&c, extra.data(), (uint32_t)extra.size(), &eng_);
         if (st == TBE_EINVAL) throw ArgumentException(std::string("invalid limiter options: ") + tbe_last_error(nullptr), "options");
         if (st != TBE_OK) throw RateLimiterEngineException(st, std::string("tbe_create failed: ") + tbe_last_error(nullptr));
@@ -350,6 +351,7 @@ public:
             const uint64_t m = std::min(kChunk, n - k0);
             Check(tbe_export_state(eng_, k0, m, v.data(), t.data()));
             bool cleared = false;
+            std::vector<uint64_t> freed_here;   // offsets in this chunk
             for (uint64_t j = 0; j < m; ++j) {
                 const uint64_t k = k0 + j;
                 if (is_free[k] || busy.count(k)) continue;
@@ -359,6 +361,7 @@ public:
                 names_[k].clear();
                 last_reply_.erase(k);
                 free_ids_.push_back(k);
+                freed_here.push_back(j);
                 if (t[j] != INT64_MIN) {
                     t[j] = INT64_MIN;
                     cleared = true;
@@ -367,6 +370,13 @@ public:
             }
             // this thread is the engine's only submitter: the other rows go back unchanged
             if (cleared) Check(tbe_import_state(eng_, k0, m, v.data(), t.data()));
+            // lease statistics are per key id: a freed id goes to its next name at zero
+            if (opt_.TrackStatistics && !freed_here.empty()) {
+                std::vector<uint64_t> ok(m), failed(m);
+                Check(tbe_stats_export(eng_, k0, m, ok.data(), failed.data()));
+                for (uint64_t j : freed_here) ok[j] = failed[j] = 0;
+                Check(tbe_stats_import(eng_, k0, m, ok.data(), failed.data()));
+            }
         }
         reclaimed_ += freed;
         return freed;
@@ -478,6 +488,16 @@ public:
             for (uint32_t j = 0; j < cnt && j < s.queued; ++j) s.queued_permits += ps[j];
         }
         return s;
+    }
+
+    // GetStatistics of one key (submitter thread only, so every request submitted before the
+    // call has been counted): the queued permits and the two lease totals, read on the device.
+    bool TracksStatistics() const { return opt_.TrackStatistics; }
+    RateLimiterStatistics QueryStatistics(uint64_t key, int64_t available) {
+        uint64_t ok = 0, failed = 0;
+        uint32_t queued = 0;
+        Check(tbe_stats_batch(eng_, &key, 1, clock_(), &ok, &failed, nullptr, &queued));
+        return RateLimiterStatistics{available, (int64_t)queued, (int64_t)failed, (int64_t)ok};
     }
 
     // One replenish tick (Q:237-271) / RefreshAsync (A:412-508), on the submitter thread.
@@ -856,6 +876,11 @@ RedisTokenBucketRateLimiter::RedisTokenBucketRateLimiter(const RedisTokenBucketR
                                           "RedisTokenBucketRateLimiter")) {}
 RedisTokenBucketRateLimiter::~RedisTokenBucketRateLimiter() = default;
 int RedisTokenBucketRateLimiter::GetAvailablePermits() { return core_->EstimatedRemaining(); }
+std::optional<RateLimiterStatistics> RedisTokenBucketRateLimiter::GetStatistics() {
+    if (!core_->TracksStatistics()) return std::nullopt;
+    core_->ThrowIfDisposed();
+    return core_->Run([this] { return core_->QueryStatistics(0, core_->EstimatedRemaining()); });
+}
 RateLimitLease RedisTokenBucketRateLimiter::AttemptAcquireCore(int p) { return core_->Submit(0, p, kTbAcquire).get(); }
 std::future<RateLimitLease> RedisTokenBucketRateLimiter::AcquireAsyncCore(int p, const CancellationToken &) {
     return core_->Submit(0, p, kTbAcquire);  // never queues: nothing to cancel (TB:58-82)
@@ -870,6 +895,17 @@ int PartitionedRedisTokenBucketRateLimiter::GetAvailablePermits(const std::strin
     core_->ThrowIfDisposed();
     uint64_t k;
     return core_->KnownKey(id, k) ? core_->LastReply(k) : core_->ClassLimit(core_->ClassOfResource(id));
+}
+std::optional<RateLimiterStatistics> PartitionedRedisTokenBucketRateLimiter::GetStatistics(const std::string &id) {
+    if (!core_->TracksStatistics()) return std::nullopt;
+    core_->ThrowIfDisposed();
+    // on the submitter thread, where reclaims run: the name cannot lose its key in between
+    return core_->Run([this, &id] {
+        uint64_t k;
+        if (!core_->KnownKey(id, k))
+            return RateLimiterStatistics{core_->ClassLimit(core_->ClassOfResource(id)), 0, 0, 0};
+        return core_->QueryStatistics(k, core_->LastReply(k));
+    });
 }
 RateLimitLease PartitionedRedisTokenBucketRateLimiter::AttemptAcquireCore(const std::string &id, int p) {
     core_->ThrowIfDisposed();
@@ -897,6 +933,11 @@ RedisQueueingTokenBucketRateLimiter::RedisQueueingTokenBucketRateLimiter(const R
     : core_(std::make_unique<LimiterCore>(TBE_KIND_QUEUEING, o, false, "RedisQueueingTokenBucketRateLimiter")) {}
 RedisQueueingTokenBucketRateLimiter::~RedisQueueingTokenBucketRateLimiter() = default;
 int RedisQueueingTokenBucketRateLimiter::GetAvailablePermits() { return core_->EstimatedRemaining(); }
+std::optional<RateLimiterStatistics> RedisQueueingTokenBucketRateLimiter::GetStatistics() {
+    if (!core_->TracksStatistics()) return std::nullopt;
+    core_->ThrowIfDisposed();
+    return core_->Run([this] { return core_->QueryStatistics(0, core_->EstimatedRemaining()); });
+}
 bool RedisQueueingTokenBucketRateLimiter::TryReplenish() {
     if (core_->options().AutoReplenishment) return false;
     core_->ThrowIfDisposed();
@@ -922,6 +963,11 @@ std::optional<TimeSpan> RedisApproximateTokenBucketRateLimiter::IdleDuration() c
 int RedisApproximateTokenBucketRateLimiter::GetAvailablePermits() {
     core_->ThrowIfDisposed();
     return core_->Run([this] { return core_->QueryApprox(0).available; });
+}
+std::optional<RateLimiterStatistics> RedisApproximateTokenBucketRateLimiter::GetStatistics() {
+    if (!core_->TracksStatistics()) return std::nullopt;
+    core_->ThrowIfDisposed();
+    return core_->Run([this] { return core_->QueryStatistics(0, core_->QueryApprox(0).available); });
 }
 bool RedisApproximateTokenBucketRateLimiter::TryReplenish() {
     if (core_->options().AutoReplenishment) return false;
@@ -968,6 +1014,16 @@ int PartitionedRedisApproximateTokenBucketRateLimiter::GetAvailablePermits(const
     return core_->Run([this, &id] {
         uint64_t k;
         return core_->KnownKey(id, k) ? core_->QueryApprox(k).available : core_->options().TokenLimit;
+    });
+}
+std::optional<RateLimiterStatistics> PartitionedRedisApproximateTokenBucketRateLimiter::GetStatistics(
+    const std::string &id) {
+    if (!core_->TracksStatistics()) return std::nullopt;
+    core_->ThrowIfDisposed();
+    return core_->Run([this, &id] {
+        uint64_t k;
+        if (!core_->KnownKey(id, k)) return RateLimiterStatistics{core_->options().TokenLimit, 0, 0, 0};
+        return core_->QueryStatistics(k, core_->QueryApprox(k).available);
     });
 }
 bool PartitionedRedisApproximateTokenBucketRateLimiter::TryReplenish() {

@@ -133,6 +133,18 @@ private:
     std::optional<TimeSpan> retry_after_;
 };
 
+// System.Threading.RateLimiting.RateLimiterStatistics (the GA surface: GetStatistics()
+// replaced GetAvailablePermits).  The two totals are counted on the device per key
+// (TBE_FLAG_STATS): a granted lease, at once or at a replenish tick, is
+// successful; a failed one and a queued one evicted by a newer request are failed; a canceled
+// wait and an ArgumentOutOfRangeException count nothing.
+struct RateLimiterStatistics {
+    int64_t CurrentAvailablePermits = 0;
+    int64_t CurrentQueuedCount = 0;      // _queueCount: the queued permits
+    int64_t TotalFailedLeases = 0;
+    int64_t TotalSuccessfulLeases = 0;
+};
+
 // The role of Redis TIME (TB:202): microseconds since the Unix epoch.  Injectable so
 // tests can drive the limiters deterministically.
 using Clock = std::function<int64_t()>;
@@ -174,6 +186,10 @@ struct RedisTokenBucketRateLimiterOptions {
     uint64_t MaxBatch = 1u << 16;  // largest micro-batch one engine call takes
     Clock TimeSource;              // default SystemClockMicros
     std::function<void(const BatchTrace &)> OnBatch;  // diagnostics (tests)
+    // Lease statistics: the engine counts every key's successful and failed leases on the
+    // device (16 B per key) and GetStatistics() reports them; false: GetStatistics() returns
+    // nullopt and nothing is counted or allocated.
+    bool TrackStatistics = false;
     // PartitionedRedisTokenBucketRateLimiter only (every other limiter throws
     // ArgumentException when Classes is non-empty): the extra limit classes 1, 2, ...; class 0
     // is the three options above.  ClassOf is the partitioner of PartitionedRateLimiter.Create:
@@ -208,6 +224,10 @@ public:
     virtual ~RateLimiter() = default;
     virtual std::optional<TimeSpan> IdleDuration() const = 0;
     virtual int GetAvailablePermits() = 0;
+    // nullopt unless the limiter was built with TrackStatistics.  CurrentAvailablePermits is
+    // GetAvailablePermits(); the other three come from the device through the submitter's
+    // queue, so they include every request submitted before the call.
+    virtual std::optional<RateLimiterStatistics> GetStatistics() { return std::nullopt; }
     // Base-class argument validation: permitCount < 0 -> ArgumentOutOfRangeException.
     RateLimitLease AttemptAcquire(int permitCount = 1);
     // A queued request whose token is canceled completes with OperationCanceledException
@@ -225,6 +245,9 @@ class PartitionedRateLimiter {  // System.Threading.RateLimiting.PartitionedRate
 public:
     virtual ~PartitionedRateLimiter() = default;
     virtual int GetAvailablePermits(const TResource &resource) = 0;
+    // As RateLimiter::GetStatistics, for one resource.  A resource that holds no key reads
+    // {GetAvailablePermits(resource), 0, 0, 0} and takes no key.
+    virtual std::optional<RateLimiterStatistics> GetStatistics(const TResource &) { return std::nullopt; }
     RateLimitLease AttemptAcquire(const TResource &resource, int permitCount = 1) {
         if (permitCount < 0) throw ArgumentOutOfRangeException("permitCount must be >= 0", "permitCount");
         return AttemptAcquireCore(resource, permitCount);
@@ -255,6 +278,7 @@ public:
     ~RedisTokenBucketRateLimiter() override;
     std::optional<TimeSpan> IdleDuration() const override { return std::nullopt; }  // TB:20
     int GetAvailablePermits() override;                                               // TB:48-51
+    std::optional<RateLimiterStatistics> GetStatistics() override;
 protected:
     RateLimitLease AttemptAcquireCore(int permitCount) override;
     std::future<RateLimitLease> AcquireAsyncCore(int permitCount, const CancellationToken &ct) override;          // TB:58-82
@@ -272,6 +296,7 @@ public:
     explicit PartitionedRedisTokenBucketRateLimiter(const RedisTokenBucketRateLimiterOptions &options);
     ~PartitionedRedisTokenBucketRateLimiter() override;
     int GetAvailablePermits(const std::string &resourceID) override;
+    std::optional<RateLimiterStatistics> GetStatistics(const std::string &resourceID) override;
     // Frees the keys of buckets Redis would have expired (TB:232-235) for new resource
     // ids; runs by itself when all PartitionLimit keys are taken.  Returns the number freed.
     uint64_t ReclaimExpired();
@@ -294,6 +319,7 @@ public:
     ~RedisQueueingTokenBucketRateLimiter() override;
     std::optional<TimeSpan> IdleDuration() const override { return std::nullopt; }  // Q:29
     int GetAvailablePermits() override;                                               // Q:57-60
+    std::optional<RateLimiterStatistics> GetStatistics() override;
     bool TryReplenish();  // one replenish tick now; false when AutoReplenishment is on
 protected:
     RateLimitLease AttemptAcquireCore(int permitCount) override;
@@ -313,6 +339,7 @@ public:
     ~RedisApproximateTokenBucketRateLimiter() override;
     std::optional<TimeSpan> IdleDuration() const override;                            // A:34
     int GetAvailablePermits() override;                                               // A:81
+    std::optional<RateLimiterStatistics> GetStatistics() override;
     bool TryReplenish();  // one RefreshAsync (A:412-508) now; false when AutoReplenishment is on
     std::string ToString();                                                           // A:510-513
 protected:
@@ -339,6 +366,7 @@ public:
     // A:81 for a name that holds a key; TokenLimit for one that does not (what its limiter
     // would report once constructed), without assigning a key.
     int GetAvailablePermits(const std::string &resourceID) override;
+    std::optional<RateLimiterStatistics> GetStatistics(const std::string &resourceID) override;
     bool TryReplenish();  // one RefreshAsync of every name now; false when AutoReplenishment is on
     uint64_t ReclaimIdle();  // frees the keys of idle names; returns the number freed
 protected:

@@ -112,6 +112,12 @@ typedef struct tbe_config {
                                              records.  By default the first pass also writes each
                                              request's second digit as one byte beside its record,
                                              and that histogram reads those */
+#define TBE_FLAG_STATS 0x200u             /* every kind: lease statistics, two
+                                             uint64 counters per key (16 B per key, allocated at
+                                             create: TBE_ENOMEM when that fails) and two engine
+                                             totals, counted on the device behind every batch.
+                                             No decision, reply, row or layout changes; without
+                                             the flag nothing is allocated or launched for them */
 
 typedef struct tbe_engine tbe_engine;
 
@@ -242,7 +248,9 @@ tbe_status tbe_import_state(tbe_engine *engine, uint64_t first, uint64_t count, 
  * absent, which decides identically at ts_us and later but keeps a reused key id on a
  * full bucket even if a later timestamp steps back before the lapse.  The keys' classes
  * (tbe_set_class) are left alone: a caller that hands a reclaimed id to a new key sets its
- * class before that key's first batch.
+ * class before that key's first batch.  On an engine with TBE_FLAG_STATS, clear != 0 also
+ * zeroes both lease counters of every key flagged dead (the counters are per id; the engine
+ * totals stay); clear == 0 zeroes none.
  * Ordered after every batch already enqueued on the engine (pipelined ones included),
  * as tbe_export_state is; `stream` as in tbe_acquire_batch_device: the scan waits for
  * work enqueued on it and it waits for the flags.  ts_us < 0 or a range past n_keys:
@@ -516,7 +524,9 @@ tbe_status tbe_approx_idle_device(tbe_engine *engine, int64_t ts_us, uint64_t fi
  * local tier {cap TokenLimit, local 0, empty queue}, client view {est 1, global 0}, tier
  * row absent (v = p = 0).  A reused id is then what the reference has for a new resourceID:
  * a freshly constructed limiter over an absent Redis key, the estimator's warm-up included.
- * Unflagged rows are not written.  After a one-client sync the client views of all keys are
+ * Unflagged rows are not written.  On an engine with TBE_FLAG_STATS both lease counters of
+ * every flagged key are zeroed too (the engine totals stay).
+ * After a one-client sync the client views of all keys are
  * first written (as tbe_approx_import_state does).  Ordering, `stream` and argument checks
  * as above.
  * Known departure: a name that is reclaimed and returns within a day finds, in the
@@ -554,6 +564,50 @@ tbe_status tbe_approx_import_rows_device(tbe_engine *engine, const uint64_t *d_i
 /* The same from host buffers; synchronous, invalid rows: TBE_EINVAL, nothing written. */
 tbe_status tbe_approx_import_rows(tbe_engine *engine, const uint64_t *ids, const double *v, const double *p,
                                   const int64_t *t_us, uint64_t n);
+
+/* ---------------------------------------------------------------- Lease statistics
+ * The GA System.Threading.RateLimiting surface: GetStatistics() returns RateLimiterStatistics
+ * {CurrentAvailablePermits, CurrentQueuedCount, TotalFailedLeases, TotalSuccessfulLeases}
+ * (DESIGN.md §2d).  An engine created with TBE_FLAG_STATS keeps ok[k] and failed[k] per key
+ * and the two engine totals, which are the sums of the per-key events:
+ *   tbe_acquire_batch(_device): granted[i] == 1 -> ok[key_i] += 1; == 0 -> failed[key_i] += 1.
+ *   tbe_wait_batch*, tbe_queue_attempt_batch, tbe_approx_acquire_batch* (_retry included):
+ *     TBE_WAIT_GRANTED -> ok; TBE_WAIT_FAILED -> failed; TBE_WAIT_QUEUED nothing yet (it counts
+ *     when it completes); TBE_WAIT_REJECTED nothing (an exception in the reference, not a
+ *     lease); each NewestFirst eviction (Q:94-109, A:143-158) -> failed on the evicted
+ *     entry's key.
+ *   tbe_refresh(_device), the tick of tbe_wait_batch_tick_device, tbe_approx_sync(_stream),
+ *     tbe_approx_refresh: each drained grant -> ok on its key.
+ *   tbe_queue_cancel and a batch skipped as invalid count nothing.
+ * The counters are per id: tbe_expired_device(clear != 0) and tbe_approx_reset(_device) zero
+ * them for the keys they flag; tbe_set_class*, imports and exports of rows leave them alone.
+ *
+ * Batched query.  Any output pointer may be NULL; keys may repeat.
+ *   ok[i], failed[i]  the counters of keys[i] (TBE_EINVAL on an engine without the flag).
+ *   available[i]      token-bucket and queueing kinds: trunc(x), x the script's refilled,
+ *                     clamped value (TB:218-221) of the key at ts_us -- the `remaining` a
+ *                     denied request at ts_us would be told; an absent or lapsed row gives
+ *                     the TokenLimit of the key's class; the row is not touched.
+ *                     Approximate kind: AvailableTokens (A:37); ts_us is ignored.
+ *   queued[i]         _queueCount, the queued permits; 0 on the token-bucket kind.
+ * available and queued work on every engine: they are the batched GetAvailablePermits.
+ * ts_us < 0 on the two clocked kinds: TBE_EINVAL.  A key >= n_keys voids the device call
+ * (nothing is written) and is reported by tbe_synchronize; the host form returns TBE_EINVAL.
+ * Ordered after every batch enqueued before the call; `stream` as in tbe_expired_device. */
+tbe_status tbe_stats_batch_device(tbe_engine *engine, const uint64_t *d_keys, uint64_t n, int64_t ts_us,
+                                  uint64_t *d_ok, uint64_t *d_failed, int32_t *d_available,
+                                  uint32_t *d_queued, void *stream);
+/* The same with host buffers; synchronous. */
+tbe_status tbe_stats_batch(tbe_engine *engine, const uint64_t *keys, uint64_t n, int64_t ts_us, uint64_t *ok,
+                           uint64_t *failed, int32_t *available, uint32_t *queued);
+/* The engine totals, kept apart from the per-key counters so that reading them scans
+ * nothing; synchronous.  TBE_EINVAL on an engine without TBE_FLAG_STATS (as the two below). */
+tbe_status tbe_stats_totals(tbe_engine *engine, uint64_t *ok, uint64_t *failed);
+/* Range forms, for restore and for tests; synchronous.  An import moves the engine totals by
+ * the difference between the imported and the replaced counters. */
+tbe_status tbe_stats_export(tbe_engine *engine, uint64_t first, uint64_t count, uint64_t *ok, uint64_t *failed);
+tbe_status tbe_stats_import(tbe_engine *engine, uint64_t first, uint64_t count, const uint64_t *ok,
+                            const uint64_t *failed);
 
 /* How the engine lays a batch out (for reports and tests): *passes = 8-bit partition
  * passes over the bucket id, *r_bits = log2 of the keys per bucket (one workgroup
