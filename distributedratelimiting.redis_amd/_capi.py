@@ -46,7 +46,8 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_approx_export_live_device", "tbe_approx_export_live", "tbe_approx_import_rows_device",
             "tbe_approx_import_rows", "tbe_create_classes", "tbe_classes", "tbe_set_class_device",
             "tbe_set_class", "tbe_get_class_device", "tbe_get_class", "tbe_stats_batch_device",
-            "tbe_stats_batch", "tbe_stats_totals", "tbe_stats_export", "tbe_stats_import")
+            "tbe_stats_batch", "tbe_stats_totals", "tbe_stats_export", "tbe_stats_import",
+            "tbe_create_queue_classes", "tbe_queue_classes")
 # k_stats_batch's shape (csrc/tbe_stats.hpp): requests per workgroup trip and slots of its
 # LDS table; the tests size their cases by them
 STATS_TILE, STATS_SLOTS = 4096, 2048
@@ -81,6 +82,17 @@ class TbeClass(Structure):
     ]
 
 
+class TbeQueueClass(Structure):
+    """One queueing limit class: tbe_queue_class of include/tbe.h (24 bytes)."""
+    _fields_ = [
+        ("token_limit", c_int32),
+        ("tokens_per_period", c_int32),
+        ("replenishment_period_ticks", c_int64),
+        ("queue_limit", c_int32),
+        ("queue_order", c_int32),
+    ]
+
+
 class TbeError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"{STATUS_NAMES.get(status, status)}: {message}")
@@ -109,6 +121,10 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_create_classes.argtypes = [POINTER(TbeConfig), POINTER(TbeClass), c_uint32, POINTER(c_void_p)]
     lib.tbe_classes.restype = c_int32
     lib.tbe_classes.argtypes = [c_void_p, POINTER(TbeClass), c_uint32, POINTER(c_uint32)]
+    lib.tbe_create_queue_classes.restype = c_int32
+    lib.tbe_create_queue_classes.argtypes = [POINTER(TbeConfig), POINTER(TbeQueueClass), c_uint32, POINTER(c_void_p)]
+    lib.tbe_queue_classes.restype = c_int32
+    lib.tbe_queue_classes.argtypes = [c_void_p, POINTER(TbeQueueClass), c_uint32, POINTER(c_uint32)]
     lib.tbe_set_class_device.restype = c_int32
     lib.tbe_set_class_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]
     lib.tbe_set_class.restype = c_int32

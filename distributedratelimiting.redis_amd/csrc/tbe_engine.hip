@@ -2854,15 +2854,38 @@ __global__ __launch_bounds__(1024) void k_hot_sample(const uint64_t *__restrict_
 // ----------------------------------------------------------------------------- queueing kind
 // Per-key queue header (u64): bits 0-15 head, 16-31 count, 32-63 qsum (= _queueCount).
 // Ring entry (u64): bits 16-63 request id, 0-15 permits.  Ring of key k: ring[k*C .. k*C+C).
-struct QParams {
+// The options one key's decisions depend on (q_step, drain_key): the engine's, or with
+// limit classes those of the key's class.
+struct QOpt {
     int32_t token_limit;
     int32_t queue_limit;
     int32_t order;       // 0 OldestFirst, 1 NewestFirst
-    uint32_t cap;        // ring entries per key (max(1, QueueLimit))
+    uint32_t cap;        // ring entries the key uses (max(1, QueueLimit)): where head and tail wrap
+};
+// A batch's parameters: the engine's options (class 0's; `cap` is also the ring stride, with
+// classes the largest cap of any class) and what belongs to the batch.
+struct QParams : QOpt {
     int32_t wait;        // 1 = WaitAsyncCore (may queue), 0 = AcquireCore (lease or fail)
     uint32_t ai_base;    // added to eviction causes (a chunk's offset in its host batch)
     int64_t id_base;     // request id of arrival index 0 of this batch
 };
+// Queueing limit classes (tbe_create_queue_classes): one class on the device
+// is the script parameters plus the options above.  The CLS = true instantiations of k_fold_q
+// and k_drain hand q_step / drain_key references into the record of the key's class, so each
+// field is loaded where it is used: a plain engine keeps these ten words in SGPRs, and a
+// form that copied the record into registers per decision compiled to 8-20 bytes of scratch
+// at k_fold_q's 80-VGPR budget (CHANGELOG.md has the resource table of the form kept, scratch
+// 0).  The CLS = false ones pass their own P and Q and never see a view.
+struct QClsPar {
+    TbParams p;
+    QOpt o;
+};
+static_assert(sizeof(QClsPar) == 40, "five 8-byte words per class");
+struct QClsView {
+    const uint8_t *cls;    // one byte per key, padded to whole buckets (ClsView::cls)
+    const QClsPar *par;    // kMaxClasses entries
+};
+struct NoQCls {};          // what a CLS = false kernel takes in the view's place
 __device__ __forceinline__ uint64_t qh_pack(uint32_t head, uint32_t cnt, int64_t qsum) {
     return (uint64_t)(head & 0xFFFFu) | ((uint64_t)(cnt & 0xFFFFu) << 16) | ((uint64_t)qsum << 32);
 }
@@ -2906,10 +2929,11 @@ constexpr int kQItems = TBE_Q_ITEMS;
 constexpr int kQChunk = kQBlock * kQItems;         // 2048 requests per chunk
 // One request of one key (WaitAsyncCore Q:67-134 / TryLeaseUnsynchronized Q:136-165)
 // against the key's row `st` and queue header `hdr`; `kr` is the key's ring.  Sets the
-// reply fields and ORs smod / hmod when the row / header changed.
+// reply fields and ORs smod / hmod when the row / header changed.  P and O are the key's
+// parameters and options (the engine's, or its class's), Q the batch's.
 __device__ __forceinline__ void q_step(Slot &st, uint64_t &hdr, bool &smod, bool &hmod, int32_t p, const ReqTime &rq,
                                        const TimeBase &TB, uint32_t ai, uint64_t *__restrict__ kr, const TbParams &P,
-                                       const QParams &Q,
+                                       const QParams &Q, const QOpt &O,
                                        uint32_t *__restrict__ ev_cause, int64_t *__restrict__ ev_id,
                                        uint32_t *__restrict__ ev_count, uint32_t ev_cap, uint32_t &status,
                                        uint32_t &rem, bool &evaluated) {
@@ -2917,12 +2941,12 @@ __device__ __forceinline__ void q_step(Slot &st, uint64_t &hdr, bool &smod, bool
     int64_t qsum = (int64_t)(hdr >> 32);
     rem = 0;
     evaluated = false;
-    if (p > Q.token_limit) {                                   // Q:70-73
+    if (p > O.token_limit) {                                   // Q:70-73
         status = TBE_WAIT_REJECTED;
         return;
     }
     bool granted = false;
-    if (p == 0 || !(cnt > 0 && Q.order == 0)) {                // Q:153
+    if (p == 0 || !(cnt > 0 && O.order == 0)) {                // Q:153
         bool m;
         const double ft = req_time_rel(st.t_us == kAbsent ? absent_t(TB) : st.t_us, TB, 0).new_t;   // the row's field t
         const uint32_t reply = tb_step_ft(st, ft, p, rq, P, m);
@@ -2939,12 +2963,12 @@ __device__ __forceinline__ void q_step(Slot &st, uint64_t &hdr, bool &smod, bool
         status = TBE_WAIT_FAILED;                              // TryLease only
         return;
     }
-    if ((int64_t)Q.queue_limit - qsum < p) {                   // Q:92
-        if (!(Q.order == 1 && p <= Q.queue_limit)) {
+    if ((int64_t)O.queue_limit - qsum < p) {                   // Q:92
+        if (!(O.order == 1 && p <= O.queue_limit)) {
             status = TBE_WAIT_FAILED;                          // Q:113
             return;
         }
-        while ((int64_t)Q.queue_limit - qsum < p) {            // Q:94-109
+        while ((int64_t)O.queue_limit - qsum < p) {            // Q:94-109
             const uint64_t ent = kr[head];
             const uint32_t at = atomicAdd(ev_count, 1u);
             if (at < ev_cap) {
@@ -2952,12 +2976,12 @@ __device__ __forceinline__ void q_step(Slot &st, uint64_t &hdr, bool &smod, bool
                 ev_id[at] = (int64_t)(ent >> 16);
             }
             qsum -= (int64_t)(ent & 0xFFFFu);
-            head = (head + 1 == Q.cap) ? 0 : head + 1;
+            head = (head + 1 == O.cap) ? 0 : head + 1;
             --cnt;
         }
     }
     uint32_t tail = head + cnt;                                // Q:117-132
-    if (tail >= Q.cap) tail -= Q.cap;
+    if (tail >= O.cap) tail -= O.cap;
 #if defined(TBE_Q_RING_SECTOR_AB)
     {   // A/B timing only (wrong queues): a whole aligned 32-byte sector per enqueue, so
         // the store needs no read-modify-write below L2
@@ -3010,7 +3034,7 @@ __device__ __forceinline__ uint32_t tick_step(Slot &row, int32_t permits, const 
 template <bool WRITE>
 __device__ __forceinline__ uint32_t drain_key(uint64_t key, Slot &st, uint64_t &h, bool &smod,
                                               const uint64_t *__restrict__ kr, const ReqTime &rqT, const TimeBase &TB,
-                                              const TbParams &P, const QParams &Q, const DrainLog &L, uint32_t at) {
+                                              const TbParams &P, const QOpt &O, const DrainLog &L, uint32_t at) {
     uint32_t cnt = (uint32_t)((h >> 16) & 0xFFFFu);
     if (cnt == 0) return 0;
     uint32_t head = (uint32_t)(h & 0xFFFFu);
@@ -3029,9 +3053,9 @@ __device__ __forceinline__ uint32_t drain_key(uint64_t key, Slot &st, uint64_t &
             }
         }
         uint32_t idx = head;
-        if (Q.order == 1) {
+        if (O.order == 1) {
             idx = head + cnt - 1;
-            if (idx >= Q.cap) idx -= Q.cap;
+            if (idx >= O.cap) idx -= O.cap;
         }
         const uint64_t ent = kr[idx];
         const int32_t p = (int32_t)(ent & 0xFFFFu);
@@ -3046,7 +3070,7 @@ __device__ __forceinline__ uint32_t drain_key(uint64_t key, Slot &st, uint64_t &
         }
         ++seq;
         qsum -= p;
-        if (Q.order == 0) head = (head + 1 == Q.cap) ? 0 : head + 1;
+        if (O.order == 0) head = (head + 1 == O.cap) ? 0 : head + 1;
         --cnt;
     }
     if (WRITE) {
@@ -3091,7 +3115,12 @@ constexpr uint32_t kQTailRun = 32;       // longest run a walking thread sorts a
 // (workgroup-scope fence; one CU, one vector L1).
 // PACKED: requests arrive as packed records (PackFmt; permit code min(p, TokenLimit + 1),
 // which leaves REJECTED exactly where p > TokenLimit) beside their arrival indices.
-template <bool PACKED, typename HW>
+// CLS (wide records only): the bucket's class bytes sit in LDS beside its rows and headers,
+// and every decision -- a request's, a drained entry's -- takes {cap, rate, ttl_ms,
+// TokenLimit, QueueLimit, order, ring length} of its row's class: an LDS copy of the first
+// kClsLds class records, global loads for the others.  Q.wait, Q.ai_base and Q.id_base stay
+// the batch's, and Q.cap the ring stride.
+template <bool PACKED, typename HW, bool CLS = false>
 __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
     const uint32_t *__restrict__ skeys, const int32_t *__restrict__ sperm,
     const int64_t *__restrict__ sts, const uint32_t *__restrict__ sidx,
@@ -3100,9 +3129,33 @@ __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
     HW *__restrict__ qhdr, uint64_t *__restrict__ ring, TbParams P, QParams Q,
     uint32_t *__restrict__ res, uint32_t *__restrict__ ev_cause, int64_t *__restrict__ ev_id,
     uint32_t *__restrict__ ev_count, uint32_t ev_cap, const uint32_t *__restrict__ err, uint32_t narrow,
-    QTick T, FoldFmt G, const uint64_t *__restrict__ rec0) {
+    QTick T, FoldFmt G, const uint64_t *__restrict__ rec0, std::conditional_t<CLS, QClsView, NoQCls> QC = {}) {
+    static_assert(!CLS || !PACKED, "classes: wide records only");
     __shared__ __attribute__((aligned(16))) Slot slot[1 << kMaxRBits];   // LDS-DMA destinations
     __shared__ __attribute__((aligned(16))) HW qh[1 << kMaxRBits];
+    uint8_t *lcls = nullptr;    // CLS: the bucket's class bytes
+    QClsPar *lqpar = nullptr;   // CLS: the first kClsLds class records
+    if constexpr (CLS) {
+        __shared__ uint32_t lcls_w[kMaxRows / 4];
+        __shared__ QClsPar lqpar_s[kClsLds];
+        lcls = reinterpret_cast<uint8_t *>(lcls_w);
+        lqpar = lqpar_s;
+    }
+    // CLS: the record of row j's class, in LDS or in the class table
+    auto row_cls = [&](uint32_t j) -> const QClsPar * {
+        if constexpr (CLS) {
+            const uint32_t c = lcls[j];
+            return c < kClsLds ? lqpar + c : QC.par + c;
+        } else {
+            return nullptr;
+        }
+    };
+    // a request's times: wide records carry whole timestamps, and a classed row lapses by
+    // its class's ttl_ms (TimeBase::e0 is the engine's and is not used then)
+    auto req_of = [&](int64_t ts_us, const TimeBase &B, const TbParams &Pk) -> ReqTime {
+        if constexpr (CLS) return req_time(ts_us, Pk.ttl_ms);
+        else return req_time_rel(ts_us, B, P.ttl_ms);
+    };
     __shared__ uint32_t own[1 << kMaxRBits];      // election slots, or the walk's row counts / starts
     __shared__ uint32_t loaded[(1 << kMaxRBits) / 32];
     __shared__ uint32_t dirty[(1 << kMaxRBits) / 32];    // rows modified (smod)
@@ -3169,6 +3222,17 @@ __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
         loaded[j] = dense ? ~0u : 0u;
         dirty[j] = 0;
         hdirty[j] = 0;
+    }
+    if constexpr (CLS) {
+        // R class bytes, four per lane, coalesced (cls is padded to whole buckets, so the
+        // copies past nrows of a short last bucket have bytes too); the class records as
+        // 8-byte words
+        static_assert(kMaxRows <= 4 * kQBlock, "one class word per thread");
+        if ((uint32_t)tid * 4u < R)
+            reinterpret_cast<uint32_t *>(lcls)[tid] = reinterpret_cast<const uint32_t *>(QC.cls + row0)[tid];
+        static_assert(kClsLds * 5 <= kQBlock, "class records as 8-byte words");
+        if ((uint32_t)tid < kClsLds * 5u)
+            reinterpret_cast<uint64_t *>(lqpar)[tid] = reinterpret_cast<const uint64_t *>(QC.par)[tid];
     }
     lds_dma_wait();    // this wave's slice and header DMA landed
     __syncthreads();
@@ -3269,8 +3333,11 @@ __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
                 bool smod = false, hmod = false, evaluated;
                 uint32_t status, rem;
                 // request times derived by the winner (not held across rounds: registers)
-                const ReqTime rqr = req_time_rel(ts[r], TB, P.ttl_ms);
-                q_step(st, h, smod, hmod, pm[r], rqr, TB, ai[r], ring + (row0 + kl[r]) * (uint64_t)Q.cap, P, Q,
+                const QClsPar *kc = row_cls(kl[r]);
+                const TbParams &Pk = CLS ? kc->p : P;
+                const QOpt &Ok = CLS ? kc->o : static_cast<const QOpt &>(Q);
+                const ReqTime rqr = req_of(ts[r], TB, Pk);
+                q_step(st, h, smod, hmod, pm[r], rqr, TB, ai[r], ring + (row0 + kl[r]) * (uint64_t)Q.cap, Pk, Q, Ok,
                        ev_cause, ev_id, ev_count, ev_cap, status, rem, evaluated);
                 put_wait(res, pos[r], status, evaluated, rem, narrow);
                 if (smod) slot[kl[r]] = st;
@@ -3359,12 +3426,15 @@ __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
                                 uint64_t h = qh_widen(qh[row]);
                                 bool smod = false, hmod = false;
                                 uint64_t *__restrict__ kr = ring + (row0 + row) * (uint64_t)Q.cap;
+                                const QClsPar *kc = row_cls(row);   // (one row's run: its class is read once)
+                                const TbParams &Pk = CLS ? kc->p : P;
+                                const QOpt &Ok = CLS ? kc->o : static_cast<const QOpt &>(Q);
                                 for (uint32_t x = start; x < stop; ++x) {
                                     const uint32_t en = tw_sorted[x];
                                     uint32_t status, rem;
                                     bool evaluated;
-                                    const ReqTime rq1 = req_time_rel(tw_ts[en], TB, P.ttl_ms);
-                                    q_step(st, h, smod, hmod, tw_pm[en], rq1, TB, tw_ai[en], kr, P, Q, ev_cause, ev_id,
+                                    const ReqTime rq1 = req_of(tw_ts[en], TB, Pk);
+                                    q_step(st, h, smod, hmod, tw_pm[en], rq1, TB, tw_ai[en], kr, Pk, Q, Ok, ev_cause, ev_id,
                                            ev_count, ev_cap, status, rem, evaluated);
                                     put_wait(res, tw_pos[en], status, evaluated, rem, narrow);
                                 }
@@ -3414,6 +3484,12 @@ __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
         // count this workgroup's grants, reserve them in the log with one atomic, then
         // drain and log (drain_key).
         const ReqTime rqT = req_time(T.ts, P.ttl_ms);
+        // the tick as one row sees it: a classed row lapses by its class's ttl_ms
+        auto tick_of = [&](const TbParams &Pk) -> ReqTime {
+            ReqTime rq = rqT;
+            if constexpr (CLS) rq.exp_lt = (T.ts / 1000 - Pk.ttl_ms) * 1000;
+            return rq;
+        };
         const DrainLog L{T.keyseq, T.id, T.rem, T.cap};
         constexpr uint32_t kRowsPer = (kMaxRows + kQBlock - 1) / kQBlock;
         static_assert(kRowsPer <= 32, "one bit per row of this thread");
@@ -3429,8 +3505,11 @@ __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
                 Slot st = slot[j];
                 uint64_t h = qh_widen(qh[j]);
                 bool sm = false;
-                const uint32_t g = drain_key<false>(row0 + j, st, h, sm, ring + (row0 + j) * (uint64_t)Q.cap, rqT, TB, P,
-                                                    Q, L, 0);
+                const QClsPar *kc = row_cls(j);
+                const TbParams &Pk = CLS ? kc->p : P;
+                const QOpt &Ok = CLS ? kc->o : static_cast<const QOpt &>(Q);
+                const uint32_t g = drain_key<false>(row0 + j, st, h, sm, ring + (row0 + j) * (uint64_t)Q.cap,
+                                                    tick_of(Pk), TB, Pk, Ok, L, 0);
                 mine += g;
                 if (g || sm) need |= 1u << u;
             }
@@ -3450,8 +3529,11 @@ __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
                 uint64_t h = qh_widen(qh[j]);
                 const uint64_t h0 = h;
                 bool smod = false;
-                const uint32_t g = drain_key<true>(row0 + j, st, h, smod, ring + (row0 + j) * (uint64_t)Q.cap, rqT, TB, P,
-                                                   Q, L, at);
+                const QClsPar *kc = row_cls(j);
+                const TbParams &Pk = CLS ? kc->p : P;
+                const QOpt &Ok = CLS ? kc->o : static_cast<const QOpt &>(Q);
+                const uint32_t g = drain_key<true>(row0 + j, st, h, smod, ring + (row0 + j) * (uint64_t)Q.cap,
+                                                   tick_of(Pk), TB, Pk, Ok, L, at);
                 at += g;
                 if (smod) slot[j] = st;
                 if (h != h0) qh[j] = qh_store<HW>(h);
@@ -3479,12 +3561,14 @@ __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
 // One replenish tick (Q:237-271) over every key: drain the head (OldestFirst) or tail
 // (NewestFirst) while the acquire script grants.  One thread per key.  Grants are logged
 // as (key, drain position, request id, remaining); the host orders them by key.
-template <typename HW>
+// CLS: each key is drained with its class's parameters (cls[key] and the class table in
+// global memory: one lookup per queued key).
+template <typename HW, bool CLS = false>
 __global__ __launch_bounds__(kBlock) void k_drain(
     uint64_t n_keys, Slot *__restrict__ table, HW *__restrict__ qhdr,
     const uint64_t *__restrict__ ring, TbParams P, QParams Q, int64_t ts_us,
     uint64_t *__restrict__ log_keyseq, int64_t *__restrict__ log_id, int32_t *__restrict__ log_rem,
-    uint32_t *__restrict__ log_count, uint32_t log_cap) {
+    uint32_t *__restrict__ log_count, uint32_t log_cap, std::conditional_t<CLS, QClsView, NoQCls> QC = {}) {
     __shared__ uint32_t wsum[kWaves];
     __shared__ uint32_t log_base;
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
@@ -3502,7 +3586,16 @@ __global__ __launch_bounds__(kBlock) void k_drain(
         bool sm = false;
         Slot st0 = st;
         uint64_t h0 = h;
-        const uint32_t mine = queued ? drain_key<false>(key, st0, h0, sm, kr, rqT, TB, P, Q, L, 0) : 0u;
+        const QClsPar *kc = nullptr;   // CLS: the record of the key's class (queued keys only)
+        ReqTime rqC = rqT;
+        if constexpr (CLS) {
+            kc = QC.par + (queued ? QC.cls[key] : 0);
+            rqC.exp_lt = (ts_us / 1000 - kc->p.ttl_ms) * 1000;   // the key lapses by its class's TTL
+        }
+        const TbParams &Pk = CLS ? kc->p : P;
+        const QOpt &Ok = CLS ? kc->o : static_cast<const QOpt &>(Q);
+        const ReqTime &rqK = CLS ? rqC : rqT;
+        const uint32_t mine = queued ? drain_key<false>(key, st0, h0, sm, kr, rqK, TB, Pk, Ok, L, 0) : 0u;
         uint32_t total;
         const uint32_t off = block_excl_scan<kBlock>(mine, wsum, &total);
         if (threadIdx.x == 0) log_base = total ? atomicAdd(log_count, total) : 0u;
@@ -3510,7 +3603,7 @@ __global__ __launch_bounds__(kBlock) void k_drain(
         if (queued && (mine != 0 || sm)) {   // (else the writing pass is a no-op)
             bool smod = false;
             const uint64_t hb = h;
-            drain_key<true>(key, st, h, smod, kr, rqT, TB, P, Q, L, log_base + off);
+            drain_key<true>(key, st, h, smod, kr, rqK, TB, Pk, Ok, L, log_base + off);
             if (smod) table[key] = st;
             if (h != hb) qhdr[key] = qh_store<HW>(h);
         }
@@ -4166,15 +4259,35 @@ __global__ void k_set_class_check(const uint64_t *__restrict__ ids, const uint8_
         if (ids[i] >= n_keys || cls[i] >= n_classes) *bad = 1u;
 }
 
+// The queueing kind's check: an id whose queue holds entries voids the call as well (a
+// shorter ring or another order under live entries has no counterpart in the reference).
+template <typename HW>
+__global__ void k_set_class_check_q(const uint64_t *__restrict__ ids, const uint8_t *__restrict__ cls, uint64_t n,
+                                    uint64_t n_keys, uint32_t n_classes, const HW *__restrict__ qhdr,
+                                    uint32_t *__restrict__ bad) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t k = ids[i];
+        if (k >= n_keys || cls[i] >= n_classes || ((qh_widen(qhdr[k]) >> 16) & 0xFFFFu) != 0) *bad = 1u;
+    }
+}
+
+// qhdr (queueing kind, a pointer to its stored width): every written id's header becomes the
+// empty queue with head 0 -- the queue is empty (k_set_class_check_q), and the head an
+// earlier class left may lie past the new class's ring length.
+template <typename HW = uint64_t>
 __global__ void k_set_class_write(uint8_t *__restrict__ key_cls, const uint64_t *__restrict__ ids,
                                   const uint8_t *__restrict__ cls, uint64_t n, const uint32_t *__restrict__ bad,
-                                  uint32_t *__restrict__ sticky) {
+                                  uint32_t *__restrict__ sticky, HW *__restrict__ qhdr = nullptr) {
     if (*bad) {
         if (blockIdx.x == 0 && threadIdx.x == 0) *sticky = 1u;
         return;
     }
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) key_cls[ids[i]] = cls[i];
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        key_cls[ids[i]] = cls[i];
+        if (qhdr) qhdr[ids[i]] = 0;
+    }
 }
 
 // out[i] = class of ids[i]; an id >= n_keys sets *bad and the sticky flag (its byte reads 0).
@@ -4452,6 +4565,16 @@ struct tbe_engine {
     uint8_t *cls = nullptr;
     TbParams *cls_par = nullptr;
     ClsView cls_view() const { return ClsView{cls, cls_par}; }
+    // queueing limit classes (tbe_create_queue_classes; wide records): the lists above plus
+    // every class's five options and its device record; qcls_par is the device copy
+    // (kMaxClasses entries).  cls, cls_par and qcls_par exist only with extra classes; then
+    // qp.cap is the ring stride, the largest ring length of any class.
+    std::vector<tbe_queue_class> qclass_opts;
+    std::vector<QClsPar> qclass_par;
+    QClsPar *qcls_par = nullptr;
+    QClsView qcls_view() const { return QClsView{cls, qcls_par}; }
+    uint64_t q_per_key = 0;   // max over classes of min(ring length, TokenLimit): tbe_refresh_bound
+    bool q_newest = false;    // some class is NewestFirst: a wait batch may evict
     // queueing kind
     QParams qp{};
     uint64_t *qhdr = nullptr;      // per-key queue header (32-bit words when qh32: qh_store)
@@ -5035,6 +5158,12 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
                     e->cfg.n_keys, e->table, qh, e->ring, e->params, q, w.res[0], e->ev_cause, e->ev_id,
                     e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(),
                     e->qtick, G, rec0);
+            else if (e->qcls_par)
+                k_fold_q<false, HW, true><<<e->nbuckets, kQBlock, 0, sf>>>(
+                    sorted.keys, sorted.permits, sorted.ts, sorted.idx, nullptr, nullptr, e->pf, w.bstart,
+                    e->r_bits, e->cfg.n_keys, e->table, qh, e->ring, e->params, q, w.res[0], e->ev_cause,
+                    e->ev_id, e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err,
+                    e->wait_rw(), e->qtick, G, rec0, e->qcls_view());
             else
                 k_fold_q<false, HW><<<e->nbuckets, kQBlock, 0, sf>>>(
                     sorted.keys, sorted.permits, sorted.ts, sorted.idx, nullptr, nullptr, e->pf, w.bstart,
@@ -5204,7 +5333,7 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
         k_stats_batch<<<sgrid, kStatsBlock, 0, sf>>>(keys, granted, n, w.err, e->stats_view());
         // NewestFirst evictions fail the evicted lease.  A chunk of a chunked host batch
         // (in_ready) leaves them to its caller: the log runs on over the chunks.
-        const int32_t order = approx ? e->ap.order : e->qp.order;
+        const int32_t order = approx ? e->ap.order : (int32_t)e->q_newest;   // (some class evicts)
         if (wait && e->wait_mode == 1 && order == 1 && !in_ready && e->ev_cause)
             k_stats_log<<<64, kStatsBlock, 0, sf>>>(e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu),
                                                     e->ev_cause, keys, n, ai_base, nullptr, e->cfg.n_keys, w.err,
@@ -5280,10 +5409,39 @@ static const char *class_params(int32_t token_limit, int32_t tokens_per_period, 
 }
 
 static tbe_status create_engine(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
-                                tbe_engine **out_engine);
+                                tbe_engine **out_engine, const tbe_queue_class *qextra = nullptr);
 
 tbe_status tbe_create(const tbe_config *config, tbe_engine **out_engine) {
     return create_engine(config, nullptr, 0, out_engine);
+}
+
+// The checks tbe_create makes on a queueing config's own options, on one class.
+static const char *queue_class_params(const tbe_queue_class &q, TbParams *out) {
+    if (const char *msg = class_params(q.token_limit, q.tokens_per_period, q.replenishment_period_ticks, out))
+        return msg;
+    if (q.queue_limit < 0 || q.queue_limit > 0xFFFF) return "QueueLimit must lie in [0, 65535]";
+    if (q.queue_order != 0 && q.queue_order != 1)
+        return "QueueProcessingOrder must be OldestFirst (0) or NewestFirst (1)";
+    if (q.token_limit >= (int32_t)kRemNone) return "TokenLimit must be < 2^30 - 1 for queueing limiters";
+    return nullptr;
+}
+
+tbe_status tbe_create_queue_classes(const tbe_config *config, const tbe_queue_class *extra, uint32_t n_extra,
+                                    tbe_engine **out_engine) {
+    if (!out_engine) return create_fail(TBE_EINVAL, "out_engine is NULL");
+    *out_engine = nullptr;
+    if (!config || config->struct_size < offsetof(tbe_config, zero_wait_slots))
+        return create_fail(TBE_EINVAL, "config is NULL or struct_size too small");
+    if (config->kind != TBE_KIND_QUEUEING)
+        return create_fail(TBE_EINVAL, "queueing limit classes: queueing kind only");
+    if (n_extra == 0) return create_engine(config, nullptr, 0, out_engine);
+    if (n_extra > kMaxClasses - 1) return create_fail(TBE_EINVAL, "an engine holds at most 256 limit classes (255 extra)");
+    if (!extra) return create_fail(TBE_EINVAL, "extra is NULL with n_extra > 0");
+    for (uint32_t i = 0; i < n_extra; ++i) {
+        TbParams p;
+        if (const char *msg = queue_class_params(extra[i], &p)) return create_fail(TBE_EINVAL, msg);
+    }
+    return create_engine(config, nullptr, n_extra, out_engine, extra);
 }
 
 tbe_status tbe_create_classes(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
@@ -5309,8 +5467,9 @@ tbe_status tbe_create_classes(const tbe_config *config, const tbe_class *extra, 
 
 // extra != NULL: a classed engine, laid out as TBE_FLAG_NO_PACK | NO_HOT | NO_NARROW (wide
 // records, 4-byte replies, no hot runs: the forms whose folds know about classes).
+// qextra != NULL: a classed queueing engine, laid out as TBE_FLAG_NO_PACK | NO_NARROW.
 static tbe_status create_engine(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
-                                tbe_engine **out_engine) {
+                                tbe_engine **out_engine, const tbe_queue_class *qextra) {
     if (!out_engine) return create_fail(TBE_EINVAL, "out_engine is NULL");
     *out_engine = nullptr;
     // struct_size versions the config: a caller built against the round-1 header (which
@@ -5322,7 +5481,9 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
     std::memset(&c_in, 0, sizeof c_in);
     std::memcpy(&c_in, config, std::min<size_t>(config->struct_size, sizeof c_in));
     if (extra) c_in.flags |= TBE_FLAG_NO_PACK | TBE_FLAG_NO_HOT | TBE_FLAG_NO_NARROW;
+    if (qextra) c_in.flags |= TBE_FLAG_NO_PACK | TBE_FLAG_NO_NARROW;
     const tbe_config &c = c_in;
+    const bool classed = extra || qextra;
     if (c.kind != TBE_KIND_TOKEN_BUCKET && c.kind != TBE_KIND_QUEUEING &&
         c.kind != TBE_KIND_APPROXIMATE)
         return create_fail(TBE_EINVAL, "unknown kind");
@@ -5364,11 +5525,25 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
     e->nbuckets = (uint32_t)((c.n_keys + (1ull << e->r_bits) - 1) >> e->r_bits);
     e->class_opts.push_back(tbe_class{c.token_limit, c.tokens_per_period, c.replenishment_period_ticks});
     e->class_par.push_back(e->params);
-    for (uint32_t i = 0; i < n_extra; ++i) {   // (validated by tbe_create_classes)
+    for (uint32_t i = 0; i < n_extra; ++i) {   // (validated by tbe_create_classes / tbe_create_queue_classes)
         TbParams p{};
-        (void)class_params(extra[i].token_limit, extra[i].tokens_per_period, extra[i].replenishment_period_ticks, &p);
-        e->class_opts.push_back(extra[i]);
+        const tbe_class o = qextra ? tbe_class{qextra[i].token_limit, qextra[i].tokens_per_period,
+                                               qextra[i].replenishment_period_ticks}
+                                   : extra[i];
+        (void)class_params(o.token_limit, o.tokens_per_period, o.replenishment_period_ticks, &p);
+        e->class_opts.push_back(o);
         e->class_par.push_back(p);
+    }
+    if (c.kind == TBE_KIND_QUEUEING) {
+        // the five options per class and the records the CLS kernels read (class 0: the config's)
+        e->qclass_opts.push_back(tbe_queue_class{c.token_limit, c.tokens_per_period, c.replenishment_period_ticks,
+                                                 c.queue_limit, c.queue_order});
+        for (uint32_t i = 0; i < n_extra && qextra; ++i) e->qclass_opts.push_back(qextra[i]);
+        for (size_t i = 0; i < e->qclass_opts.size(); ++i) {
+            const tbe_queue_class &q = e->qclass_opts[i];
+            e->qclass_par.push_back(QClsPar{e->class_par[i], QOpt{q.token_limit, q.queue_limit, q.queue_order,
+                                                                     (uint32_t)std::max(1, q.queue_limit)}});
+        }
     }
     const int bbits = ceil_log2(e->nbuckets);
     e->passes = std::max(1, (bbits + kDigitBits - 1) / kDigitBits);
@@ -5453,10 +5628,11 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
     uint64_t ring_n = 0;
     if (dalloc(&e->table, c.n_keys * sizeof(Slot)) != hipSuccess) return bail(TBE_ENOMEM);
     const uint64_t cls_bytes = (uint64_t)e->nbuckets << e->r_bits;   // whole buckets (r_bits >= 4: 16-byte units)
-    if (extra) {
+    if (classed) {
         if (dalloc(&e->cls, cls_bytes) != hipSuccess) return bail(TBE_ENOMEM);
         if (dalloc(&e->cls_par, kMaxClasses * sizeof(TbParams)) != hipSuccess) return bail(TBE_ENOMEM);
     }
+    if (qextra && dalloc(&e->qcls_par, kMaxClasses * sizeof(QClsPar)) != hipSuccess) return bail(TBE_ENOMEM);
     if (e->hot_cap)
         for (auto &hs : e->hot)
             if (dalloc(&hs, sizeof(HotSet)) != hipSuccess) return bail(TBE_ENOMEM);
@@ -5470,9 +5646,19 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
         e->qp.token_limit = c.token_limit;
         e->qp.queue_limit = c.queue_limit;
         e->qp.order = c.queue_order;
-        e->qp.cap = (uint32_t)std::max(1, c.queue_limit);
+        // classes: the ring stride is the longest ring of any class, the header width follows
+        // the largest QueueLimit, and the drain bound the class that can grant most per key
+        e->qp.cap = 0;
+        uint32_t max_limit = 0;
+        for (const QClsPar &q : e->qclass_par) {
+            e->qp.cap = std::max(e->qp.cap, q.o.cap);
+            max_limit = std::max(max_limit, (uint32_t)q.o.queue_limit);
+            e->q_per_key = std::max<uint64_t>(e->q_per_key,
+                                              std::min<uint64_t>(q.o.cap, (uint64_t)std::max(q.o.token_limit, 1)));
+            e->q_newest |= q.o.order == 1;
+        }
         ring_n = c.n_keys * (uint64_t)e->qp.cap;
-        e->qh32 = TBE_QH32 && (uint32_t)c.queue_limit <= kQh32MaxLimit;
+        e->qh32 = TBE_QH32 && max_limit <= kQh32MaxLimit;
         if (dalloc(&e->qhdr, qhdr_n * (e->qh32 ? sizeof(uint32_t) : sizeof(uint64_t))) != hipSuccess)
             return bail(TBE_ENOMEM);
     } else if (c.kind == TBE_KIND_APPROXIMATE) {
@@ -5516,13 +5702,17 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
         }
     if (ie != hipSuccess) return bail(TBE_EDEVICE);
     k_init_table<<<2048, 256, 0, e->stream>>>(e->table, c.n_keys, e->params.cap);
-    if (extra) {
+    if (classed) {
         zero(e->cls_par, kMaxClasses * sizeof(TbParams));
+        zero(e->qcls_par, kMaxClasses * sizeof(QClsPar));
         if (ie != hipSuccess) return bail(TBE_EDEVICE);
         k_init_cls<<<2048, 256, 0, e->stream>>>(e->cls, cls_bytes / 16);
         // (class_par outlives the copy: the stream is synchronised below)
         if (hipMemcpyAsync(e->cls_par, e->class_par.data(), e->class_par.size() * sizeof(TbParams),
                            hipMemcpyHostToDevice, e->stream) != hipSuccess)
+            return bail(TBE_EDEVICE);
+        if (qextra && hipMemcpyAsync(e->qcls_par, e->qclass_par.data(), e->qclass_par.size() * sizeof(QClsPar),
+                                     hipMemcpyHostToDevice, e->stream) != hipSuccess)
             return bail(TBE_EDEVICE);
     }
     if (c.kind == TBE_KIND_APPROXIMATE)
@@ -5547,6 +5737,7 @@ void tbe_destroy(tbe_engine *e) {
     dfree(e->table);
     dfree(e->cls);
     dfree(e->cls_par);
+    dfree(e->qcls_par);
     dfree(e->alocal);
     dfree(e->aclient);
     dfree(e->gv);
@@ -5828,7 +6019,12 @@ tbe_status tbe_expired_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint
     }
     const int64_t exp_lt = (ts_us / 1000 - e->params.ttl_ms) * 1000;
     const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
-    if (e->cls)   // per key: the kernel takes each key's ttl_ms from its class
+    if (e->cls && e->cfg.kind == TBE_KIND_QUEUEING)   // per key, and a queued key is never dead
+        with_qhdr(e, [&](auto *qh) {
+            k_expired<<<blocks, kBlock, 0, st>>>(e->table, qh, first, count, ts_us / 1000, e->params.cap, clear,
+                                                 d_dead, e->cls_view());
+        });
+    else if (e->cls)   // per key: the kernel takes each key's ttl_ms from its class
         k_expired<<<blocks, kBlock, 0, st>>>(e->table, (const uint64_t *)nullptr, first, count, ts_us / 1000,
                                              e->params.cap, clear, d_dead, e->cls_view());
     else if (e->cfg.kind == TBE_KIND_QUEUEING)
@@ -5993,12 +6189,22 @@ tbe_status tbe_classes(const tbe_engine *e, tbe_class *out, uint32_t capacity, u
     return TBE_OK;
 }
 
+tbe_status tbe_queue_classes(const tbe_engine *e, tbe_queue_class *out, uint32_t capacity, uint32_t *n_classes) {
+    if (!e || !n_classes) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_QUEUEING) return TBE_EINVAL;
+    *n_classes = (uint32_t)e->qclass_opts.size();
+    for (uint32_t i = 0; out && i < capacity && i < e->qclass_opts.size(); ++i) out[i] = e->qclass_opts[i];
+    return TBE_OK;
+}
+
+static const char *kNoClasses = "limit classes: token-bucket and queueing kinds only";
+
 // On the engine's stream, where every kernel that touches table or classes runs, a caller's
 // stream joined before and after: tbe_import_rows_device's ordering.
 tbe_status tbe_set_class_device(tbe_engine *e, const uint64_t *d_ids, const uint8_t *d_cls, uint64_t n,
                                 void *stream) {
     if (!e) return TBE_EINVAL;
-    if (e->cfg.kind != TBE_KIND_TOKEN_BUCKET) return fail(e, TBE_EINVAL, "limit classes: token-bucket kind only");
+    if (e->cfg.kind == TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, kNoClasses);
     if (n == 0) return TBE_OK;
     if (!d_ids || !d_cls) return fail(e, TBE_EINVAL, "null buffer");
     HIP_TRY(e, hipSetDevice(e->device));
@@ -6011,12 +6217,21 @@ tbe_status tbe_set_class_device(tbe_engine *e, const uint64_t *d_ids, const uint
     HIP_TRY(e, hipMemsetAsync(e->rows_bad, 0, sizeof(uint32_t), st));
     const unsigned blocks = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192);
     // the validating pass ends before the first class is written (one stream)
-    k_set_class_check<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys, (uint32_t)e->class_par.size(),
-                                                 e->rows_bad);
-    if (e->cls)
+    if (e->qcls_par) {   // queueing classes: ids with queued entries void the call, written ids get head 0
+        with_qhdr(e, [&](auto *qh) {
+            k_set_class_check_q<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys,
+                                                           (uint32_t)e->class_par.size(), qh, e->rows_bad);
+            k_set_class_write<<<blocks, kBlock, 0, st>>>(e->cls, d_ids, d_cls, n, e->rows_bad, e->sticky, qh);
+        });
+    } else if (e->cls) {
+        k_set_class_check<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys, (uint32_t)e->class_par.size(),
+                                                     e->rows_bad);
         k_set_class_write<<<blocks, kBlock, 0, st>>>(e->cls, d_ids, d_cls, n, e->rows_bad, e->sticky);
-    else   // no extra classes: class 0 is all a valid call can ask for, so there is nothing to write
+    } else {   // no extra classes: class 0 is all a valid call can ask for, so there is nothing to write
+        k_set_class_check<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys, (uint32_t)e->class_par.size(),
+                                                     e->rows_bad);
         k_set_class_write<<<1, 1, 0, st>>>(nullptr, d_ids, d_cls, 0, e->rows_bad, e->sticky);
+    }
     HIP_TRY(e, hipGetLastError());
     if (caller && caller != st) {
         HIP_TRY(e, hipEventRecord(e->ev_out, st));
@@ -6027,7 +6242,7 @@ tbe_status tbe_set_class_device(tbe_engine *e, const uint64_t *d_ids, const uint
 
 tbe_status tbe_set_class(tbe_engine *e, const uint64_t *ids, const uint8_t *cls, uint64_t n) {
     if (!e) return TBE_EINVAL;
-    if (e->cfg.kind != TBE_KIND_TOKEN_BUCKET) return fail(e, TBE_EINVAL, "limit classes: token-bucket kind only");
+    if (e->cfg.kind == TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, kNoClasses);
     if (n == 0) return TBE_OK;
     if (!ids || !cls) return fail(e, TBE_EINVAL, "null buffer");
     for (uint64_t i = 0; i < n; ++i) {
@@ -6044,6 +6259,29 @@ tbe_status tbe_set_class(tbe_engine *e, const uint64_t *ids, const uint8_t *cls,
     hipError_t hrc = hipMemcpy(d_ids, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice);
     if (hrc == hipSuccess) hrc = hipMemcpy(d_cls, cls, n, hipMemcpyHostToDevice);
     tbe_status rc = TBE_OK;
+    if (hrc == hipSuccess && e->qcls_par) {
+        // queueing classes: the non-empty-queue rule is only known on the device.  The check
+        // alone runs first, so a void call returns TBE_EINVAL and leaves the sticky flag of
+        // earlier device batches as it is; the device form below checks once more (a second
+        // pass over n ids and a second synchronisation, on a call that is synchronous anyway).
+        uint32_t bad = 0;
+        if (!e->rows_bad) hrc = hipMalloc(&e->rows_bad, sizeof(uint32_t));
+        if (hrc == hipSuccess) hrc = hipMemsetAsync(e->rows_bad, 0, sizeof(uint32_t), e->stream);
+        if (hrc == hipSuccess) {
+            const unsigned blocks = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192);
+            with_qhdr(e, [&](auto *qh) {
+                k_set_class_check_q<<<blocks, kBlock, 0, e->stream>>>(d_ids, d_cls, n, e->cfg.n_keys,
+                                                                      (uint32_t)e->class_par.size(), qh, e->rows_bad);
+            });
+            hrc = hipGetLastError();
+        }
+        if (hrc == hipSuccess) hrc = hipMemcpyAsync(&bad, e->rows_bad, sizeof bad, hipMemcpyDeviceToHost, e->stream);
+        if (hrc == hipSuccess) hrc = hipStreamSynchronize(e->stream);
+        if (hrc == hipSuccess && bad) {
+            (void)hipFree(buf);
+            return fail(e, TBE_EINVAL, "an id's queue is not empty");
+        }
+    }
     if (hrc == hipSuccess) rc = tbe_set_class_device(e, d_ids, d_cls, n, nullptr);
     if (hrc == hipSuccess && rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
     (void)hipFree(buf);
@@ -6054,7 +6292,7 @@ tbe_status tbe_set_class(tbe_engine *e, const uint64_t *ids, const uint8_t *cls,
 
 tbe_status tbe_get_class_device(tbe_engine *e, const uint64_t *d_ids, uint64_t n, uint8_t *d_cls, void *stream) {
     if (!e) return TBE_EINVAL;
-    if (e->cfg.kind != TBE_KIND_TOKEN_BUCKET) return fail(e, TBE_EINVAL, "limit classes: token-bucket kind only");
+    if (e->cfg.kind == TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, kNoClasses);
     if (n == 0) return TBE_OK;
     if (!d_ids || !d_cls) return fail(e, TBE_EINVAL, "null buffer");
     HIP_TRY(e, hipSetDevice(e->device));
@@ -6075,7 +6313,7 @@ tbe_status tbe_get_class_device(tbe_engine *e, const uint64_t *d_ids, uint64_t n
 
 tbe_status tbe_get_class(tbe_engine *e, const uint64_t *ids, uint64_t n, uint8_t *cls) {
     if (!e) return TBE_EINVAL;
-    if (e->cfg.kind != TBE_KIND_TOKEN_BUCKET) return fail(e, TBE_EINVAL, "limit classes: token-bucket kind only");
+    if (e->cfg.kind == TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, kNoClasses);
     if (n == 0) return TBE_OK;
     if (!ids || !cls) return fail(e, TBE_EINVAL, "null buffer");
     for (uint64_t i = 0; i < n; ++i)
@@ -6175,7 +6413,7 @@ static tbe_status status_batch_device(tbe_engine *e, const uint64_t *d_keys, con
     if (id_base < 0 || (uint64_t)id_base + n > (1ull << 47))
         return fail(e, TBE_EINVAL, "request ids must lie in [0, 2^47)");
     HIP_TRY(e, hipSetDevice(e->device));
-    const int32_t order = e->cfg.kind == TBE_KIND_APPROXIMATE ? e->ap.order : e->qp.order;
+    const int32_t order = e->cfg.kind == TBE_KIND_APPROXIMATE ? e->ap.order : (int32_t)e->q_newest;
     const bool may_evict = e->wait_mode == 1 && order == 1;
     if (may_evict) {
         const uint64_t need_ev = e->queued_total + n;
@@ -6331,7 +6569,7 @@ static tbe_status status_chunked(tbe_engine *e, const uint64_t *keys, const int3
                                   e->cout));
     }
     HIP_TRY(e, hipMemcpyAsync(nev, e->counters, sizeof(uint32_t), hipMemcpyDeviceToHost, e->cout));
-    const int32_t order = e->cfg.kind == TBE_KIND_APPROXIMATE ? e->ap.order : e->qp.order;
+    const int32_t order = e->cfg.kind == TBE_KIND_APPROXIMATE ? e->ap.order : (int32_t)e->q_newest;
     if (e->stats() && e->wait_mode == 1 && order == 1) {
         // the evictions of all chunks, once: their causes index the whole staged batch
         k_stats_log<<<64, kStatsBlock, 0, e->stream>>>(e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu),
@@ -6476,9 +6714,15 @@ tbe_status tbe_refresh(tbe_engine *e, int64_t ts_us, uint64_t *n_granted) {
     HIP_TRY(e, hipMemsetAsync(e->counters + 1, 0, sizeof(uint32_t), st));
     const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
     with_qhdr(e, [&](auto *qh) {
-        k_drain<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us,
-                                                    e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
-                                                    (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu));
+        using HW = std::remove_pointer_t<decltype(qh)>;
+        if (e->qcls_par)
+            k_drain<HW, true><<<(unsigned)blocks, kBlock, 0, st>>>(
+                e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us, e->log_keyseq, e->log_id, e->log_rem,
+                e->counters + 1, (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), e->qcls_view());
+        else
+            k_drain<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us,
+                                                        e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
+                                                        (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu));
     });
     stats_drained(e, e->log_keyseq, e->counters + 1, (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), st);
     HIP_TRY(e, hipGetLastError());
@@ -6508,9 +6752,8 @@ tbe_status tbe_refresh_bound(tbe_engine *e, uint64_t *bound) {
     if (!e || !bound) return TBE_EINVAL;
     if (e->cfg.kind != TBE_KIND_QUEUEING) return fail(e, TBE_EINVAL, "not a queueing engine");
     // every drained entry holds >= 1 permit (zero-permit requests are never queued) and a
-    // tick grants at most TokenLimit tokens per key
-    const uint64_t per_key = std::min<uint64_t>(e->qp.cap, (uint64_t)std::max(e->qp.token_limit, 1));
-    *bound = std::min<uint64_t>(e->queued_total, e->cfg.n_keys * per_key);
+    // tick grants at most TokenLimit tokens per key (q_per_key: of the class that can grant most)
+    *bound = std::min<uint64_t>(e->queued_total, e->cfg.n_keys * e->q_per_key);
     return TBE_OK;
 }
 
@@ -6533,9 +6776,15 @@ tbe_status tbe_refresh_device(tbe_engine *e, int64_t ts_us, uint64_t *d_keyseq, 
     if (bound == 0) return TBE_OK;   // nothing queued
     const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
     with_qhdr(e, [&](auto *qh) {
-        k_drain<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us,
-                                                    d_keyseq, d_request_id, d_remaining, d_count,
-                                                    (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu));
+        using HW = std::remove_pointer_t<decltype(qh)>;
+        if (e->qcls_par)
+            k_drain<HW, true><<<(unsigned)blocks, kBlock, 0, st>>>(
+                e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us, d_keyseq, d_request_id, d_remaining,
+                d_count, (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu), e->qcls_view());
+        else
+            k_drain<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us,
+                                                        d_keyseq, d_request_id, d_remaining, d_count,
+                                                        (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu));
     });
     stats_drained(e, d_keyseq, d_count, (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu), st);
     HIP_TRY(e, hipGetLastError());
@@ -6555,7 +6804,7 @@ tbe_status tbe_wait_batch_tick_device(tbe_engine *e, const uint64_t *d_keys, con
                                           d_count, stream);
     if (!d_ts_us) return fail(e, TBE_EINVAL, "null buffer");
     // the drain log bound after this batch's possible enqueues (tbe_refresh_bound)
-    const uint64_t per_key = std::min<uint64_t>(e->qp.cap, (uint64_t)std::max(e->qp.token_limit, 1));
+    const uint64_t per_key = e->q_per_key;
     const uint64_t queued_after = wait ? std::min<uint64_t>(e->queued_total + n, ring_entries(e)) : e->queued_total;
     const uint64_t bound = std::min<uint64_t>(queued_after, e->cfg.n_keys * per_key);
     if (capacity < bound || bound > 0xFFFFFFFFull)
@@ -7002,12 +7251,18 @@ tbe_status tbe_queue_of(tbe_engine *e, uint64_t key, int64_t *request_id, int32_
         head = a.hc & 0xFFFFu;
         cnt = a.hc >> 16;
     }
+    uint32_t len = rcap;   // a classed queueing engine: the key wraps at its class's ring length
+    if (e->qcls_par) {
+        uint8_t kc = 0;
+        HIP_TRY(e, hipMemcpy(&kc, e->cls + key, 1, hipMemcpyDeviceToHost));
+        len = e->qclass_par[kc].o.cap;
+    }
     std::vector<uint64_t> ent(rcap);
     HIP_TRY(e, hipMemcpy(ent.data(), e->ring + key * (uint64_t)rcap, rcap * sizeof(uint64_t),
                          hipMemcpyDeviceToHost));
     if (cnt && (!request_id || !permits) && capacity) return fail(e, TBE_EINVAL, "null buffer");
     for (uint32_t j = 0; j < cnt && j < capacity; ++j) {
-        const uint64_t x = ent[(head + j) % rcap];
+        const uint64_t x = ent[(head + j) % len];
         request_id[j] = (int64_t)(x >> 16);
         permits[j] = (int32_t)(x & 0xFFFFu);
     }
@@ -7028,7 +7283,7 @@ __global__ __launch_bounds__(256) void k_cancel(
     const uint64_t *__restrict__ ckeys, const int64_t *__restrict__ cids,
     const uint32_t *__restrict__ run_start, uint32_t n_runs, int32_t approx,
     HW *__restrict__ qhdr, ALocal *__restrict__ alocal, uint64_t *__restrict__ ring,
-    uint32_t cap, uint8_t *__restrict__ hit) {
+    uint32_t cap, uint8_t *__restrict__ hit, QClsView QC) {   // (QC.cls == NULL: no queueing classes)
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_runs) return;
     const uint32_t c0 = run_start[r], c1 = run_start[r + 1];
@@ -7048,19 +7303,21 @@ __global__ __launch_bounds__(256) void k_cancel(
         qsum = (int64_t)(h >> 32);
     }
     uint64_t *__restrict__ kr = ring + key * (uint64_t)cap;
+    // a classed queueing engine: the key's entries wrap at its class's ring length
+    const uint32_t len = QC.cls ? QC.par[QC.cls[key]].o.cap : cap;
     bool changed = false;
     for (uint32_t c = c0; c < c1; ++c) {
         const int64_t id = cids[c];
         uint32_t j = 0;
         if (id < 0) j = cnt;   // never a request id: not queued
-        while (j < cnt && (int64_t)(kr[(head + j) % cap] >> 16) != id) ++j;
+        while (j < cnt && (int64_t)(kr[(head + j) % len] >> 16) != id) ++j;
         if (j == cnt) {
             hit[c] = 0;
             continue;
         }
-        qsum -= (int64_t)(kr[(head + j) % cap] & 0xFFFFu);
-        if (approx && (kr[(head + j) % cap] & 0xFFFFu) == 0) a.zc = (uint16_t)(a.zc - 1);
-        for (; j + 1 < cnt; ++j) kr[(head + j) % cap] = kr[(head + j + 1) % cap];
+        qsum -= (int64_t)(kr[(head + j) % len] & 0xFFFFu);
+        if (approx && (kr[(head + j) % len] & 0xFFFFu) == 0) a.zc = (uint16_t)(a.zc - 1);
+        for (; j + 1 < cnt; ++j) kr[(head + j) % len] = kr[(head + j + 1) % len];
         --cnt;
         hit[c] = 1;
         changed = true;
@@ -7118,7 +7375,8 @@ tbe_status tbe_queue_cancel(tbe_engine *e, const uint64_t *keys, const int64_t *
     with_qhdr(e, [&](auto *qh) {
         k_cancel<<<(n_runs + 255) / 256, 256, 0, e->stream>>>(
             (const uint64_t *)s.p, (const int64_t *)(s.p + off_ids), (const uint32_t *)(s.p + off_runs),
-            n_runs, approx ? 1 : 0, qh, e->alocal, e->ring, rcap, (uint8_t *)(s.p + off_hit));
+            n_runs, approx ? 1 : 0, qh, e->alocal, e->ring, rcap, (uint8_t *)(s.p + off_hit),
+            e->qcls_par ? e->qcls_view() : QClsView{nullptr, nullptr});
     });
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -7167,9 +7425,15 @@ tbe_status tbe_stats_batch_device(tbe_engine *e, const uint64_t *d_keys, uint64_
     else if (e->cfg.kind == TBE_KIND_QUEUEING)
         with_qhdr(e, [&](auto *qh) {
             using HW = std::remove_pointer_t<decltype(qh)>;
-            k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)e->table, e->params,
-                                                    (const HW *)qh, (const ALocal *)nullptr, e->stats_view(), ok,
-                                                    failed, d_available, d_queued, e->rows_bad, e->sticky);
+            if (e->cls)   // per key: `available` by the key's class
+                k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)e->table, e->params,
+                                                        (const HW *)qh, (const ALocal *)nullptr, e->stats_view(), ok,
+                                                        failed, d_available, d_queued, e->rows_bad, e->sticky,
+                                                        e->cls_view());
+            else
+                k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)e->table, e->params,
+                                                        (const HW *)qh, (const ALocal *)nullptr, e->stats_view(), ok,
+                                                        failed, d_available, d_queued, e->rows_bad, e->sticky);
         });
     else if (e->cls)   // per key: the kernel takes each key's parameters from its class
         k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)e->table, e->params, no_qhdr,

@@ -90,7 +90,13 @@ class TokenBucketEngine:
                                         queue_order=queue_order, device=device, flags=flags,
                                         max_batch=max_batch, zero_wait_slots=zero_wait_slots)
         h = c_void_p()
-        if classes:
+        if classes and self.KIND == _capi.TBE_KIND_APPROXIMATE:
+            raise ValueError("limit classes: token-bucket and queueing kinds only")
+        if classes and self.KIND == _capi.TBE_KIND_QUEUEING:
+            # five options per class: (token_limit, tokens_per_period, period_ticks, queue_limit, order)
+            extra = (_capi.TbeQueueClass * len(classes))(*[_capi.TbeQueueClass(*(int(x) for x in c)) for c in classes])
+            st = self._lib.tbe_create_queue_classes(byref(self.config), extra, len(classes), byref(h))
+        elif classes:
             extra = (_capi.TbeClass * len(classes))(*[_capi.TbeClass(int(a), int(b), int(c)) for a, b, c in classes])
             st = self._lib.tbe_create_classes(byref(self.config), extra, len(classes), byref(h))
         else:
@@ -381,6 +387,19 @@ class QueueingTokenBucketEngine(TokenBucketEngine):
         super().__init__(n_keys, token_limit, tokens_per_period, period_ticks,
                          queue_limit=queue_limit, queue_order=queue_order, **kw)
         self.queue_limit = queue_limit
+        # queue_of's buffer size: the longest ring of any class (the engine validated them)
+        self._ring_len = max([max(1, queue_limit)] +
+                             [max(1, q[3]) for q in (self.queue_classes() if self.classed else [])])
+
+    def queue_classes(self):
+        """Every class's (token_limit, tokens_per_period, period_ticks, queue_limit, order),
+        class 0 first (tbe_queue_classes)."""
+        n = c_uint32()
+        self._check(self._lib.tbe_queue_classes(self.handle, None, 0, byref(n)))
+        out = (_capi.TbeQueueClass * n.value)()
+        self._check(self._lib.tbe_queue_classes(self.handle, out, n.value, byref(n)))
+        return [(c.token_limit, c.tokens_per_period, c.replenishment_period_ticks, c.queue_limit, c.queue_order)
+                for c in out]
 
     def wait_batch(self, keys, permits, ts_us, id_base: int, status=None, remaining=None):
         """Returns (status u8, remaining i32, evicted (cause index u64, request id i64)).
@@ -481,7 +500,7 @@ class QueueingTokenBucketEngine(TokenBucketEngine):
         return keys, ids, rem
 
     def queue_of(self, key: int):
-        cap = max(1, self.queue_limit) + getattr(self, "zero_wait_slots", 0)
+        cap = self._ring_len + getattr(self, "zero_wait_slots", 0)
         ids = np.empty(cap, dtype=np.int64)
         ps = np.empty(cap, dtype=np.int32)
         cnt = c_uint32()

@@ -155,8 +155,50 @@ typedef struct tbe_class {
 tbe_status tbe_create_classes(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
                               tbe_engine **out_engine);
 
-/* The engine's classes, class 0 first: out[0..min(capacity, *n_classes)); out may be NULL. */
+/* The engine's classes, class 0 first: out[0..min(capacity, *n_classes)); out may be NULL.
+ * On a queueing engine: the first three options of each of its classes. */
 tbe_status tbe_classes(const tbe_engine *engine, tbe_class *out, uint32_t capacity, uint32_t *n_classes);
+
+/* ---- Queueing limit classes: one queueing engine, up to 256 differently
+ * configured TokenBucketWithQueue limiters.  A class is the five options of
+ * RedisQueueingTokenBucketRateLimiterOptions; the reference interpolates them into each
+ * limiter's script text and queue code (Q:405-461, TB:184-185), so any number of limiters
+ * share one Redis.  Every request, and every drained entry of a tick, is decided exactly as
+ * on a plain engine with the options of its key's class: the REJECTED test (Q:70-73), the
+ * script call, the Q:153 test, admission and NewestFirst eviction (Q:92-109), and the head
+ * or tail the drain peeks (Q:237-271).  A tick drains every key of every class. */
+typedef struct tbe_queue_class {
+    int32_t token_limit;                  /* TokenLimit (TBO:43), > 0 and < 2^30 - 1 */
+    int32_t tokens_per_period;            /* TokensPerPeriod (TBO:30), > 0 */
+    int64_t replenishment_period_ticks;   /* ReplenishmentPeriod in .NET ticks, > 0 */
+    int32_t queue_limit;                  /* QueueLimit, 0..65535 */
+    int32_t queue_order;                  /* 0 = OldestFirst, 1 = NewestFirst */
+} tbe_queue_class;                        /* 24 bytes */
+
+/* tbe_create for the queueing kind with extra[0..n_extra) as classes 1..n_extra; class 0 is
+ * the config's own five options and every key of a new engine is in class 0.  Each class gets
+ * the checks tbe_create makes on the config's options and the parameters it derives
+ * (tbe_fill_rate, then the TB:234 clamp).  n_extra == 0 is tbe_create.  TBE_EINVAL, before
+ * the device is touched: kind != TBE_KIND_QUEUEING, n_extra > 255, extra == NULL with
+ * n_extra > 0, a class that fails a check.
+ * Layout: as with TBE_FLAG_NO_PACK | TBE_FLAG_NO_NARROW (wide records, 4-byte replies;
+ * tbe_layout bits 0, 3 and 4 clear).  The ring of key k is ring[k*C .. k*C+C), C the largest
+ * max(1, QueueLimit) of any class; a key uses the first max(1, QueueLimit) slots of its own
+ * class and wraps there.  Queue headers take 32 bits when the largest QueueLimit of any class
+ * is <= 1024 (tbe_layout bit 9), else 64.  tbe_refresh_bound is min(entries possibly queued,
+ * n_keys * max over classes of min(max(1, QueueLimit), TokenLimit)).
+ * tbe_query, tbe_expired_device, tbe_export_live(_device) and `available` of
+ * tbe_stats_batch(_device) judge a key by its class's TTL, TokenLimit and fill rate; a key
+ * with queued requests is never dead.  tbe_queue_attempt_batch, tbe_queue_cancel,
+ * tbe_queue_of, tbe_evicted, TBE_FLAG_STATS counting and the row imports work as on a plain
+ * engine. */
+tbe_status tbe_create_queue_classes(const tbe_config *config, const tbe_queue_class *extra,
+                                    uint32_t n_extra, tbe_engine **out_engine);
+
+/* The classes of a queueing engine with all five options, class 0 first (as tbe_classes);
+ * another kind of engine: TBE_EINVAL. */
+tbe_status tbe_queue_classes(const tbe_engine *engine, tbe_queue_class *out, uint32_t capacity,
+                             uint32_t *n_classes);
 
 /* cls[d_ids[i]] = d_cls[i].  The row {v, t_us} stays: the key's next evaluation clamps with
  * the new TokenLimit and refills at the new rate, as when another limiter's script runs on
@@ -166,10 +208,14 @@ tbe_status tbe_classes(const tbe_engine *engine, tbe_class *out, uint32_t capaci
  * every batch after it, `stream` as in tbe_expired_device; unique ids; every pair is
  * validated before any is written, and an id >= n_keys or a class >= the number of classes
  * voids the whole call, reported by tbe_synchronize.  Without extra classes only class 0 is
- * valid.  Token-bucket kind. */
+ * valid.  Token-bucket and queueing kinds (approximate kind: TBE_EINVAL).
+ * Queueing engine with extra classes: an id whose queue is not empty voids the whole call in
+ * the same way (a shorter ring or another order under live entries has no counterpart in the
+ * reference); the queue of a written id stays empty. */
 tbe_status tbe_set_class_device(tbe_engine *engine, const uint64_t *d_ids, const uint8_t *d_cls, uint64_t n,
                                 void *stream);
-/* The same from host buffers; synchronous, an invalid pair: TBE_EINVAL, nothing written. */
+/* The same from host buffers; synchronous, an invalid pair (or, as above, a non-empty
+ * queue): TBE_EINVAL, nothing written. */
 tbe_status tbe_set_class(tbe_engine *engine, const uint64_t *ids, const uint8_t *cls, uint64_t n);
 /* d_cls[i] = class of d_ids[i] (ordering and `stream` as above); an id >= n_keys reads 0
  * and is reported by tbe_synchronize (host form: TBE_EINVAL). */
@@ -345,7 +391,8 @@ tbe_status tbe_wait_batch_device(tbe_engine *engine, const uint64_t *d_keys, con
 
 /* Upper bound on the grants one tbe_refresh_device can log: min(entries possibly queued,
  * n_keys * min(max(1, QueueLimit), TokenLimit)) -- a queued entry holds >= 1 permit and
- * a tick grants at most TokenLimit tokens per key. */
+ * a tick grants at most TokenLimit tokens per key.  With queueing classes the per-key factor
+ * is the largest min(max(1, QueueLimit), TokenLimit) of any class. */
 tbe_status tbe_refresh_bound(tbe_engine *engine, uint64_t *bound);
 
 /* Device-pointer tbe_refresh (Q:237-271): enqueues one replenish tick at ts_us.  Grants
@@ -370,7 +417,9 @@ tbe_status tbe_wait_batch_tick_device(tbe_engine *engine, const uint64_t *d_keys
                                       uint64_t *d_keyseq, int64_t *d_request_id, int32_t *d_log_remaining,
                                       uint64_t capacity, uint32_t *d_count, void *stream);
 
-/* Queue of one key, oldest first (Deque enumeration order, DQ:116-125). */
+/* Queue of one key, oldest first (Deque enumeration order, DQ:116-125).  A diagnostic call:
+ * synchronous, and on an engine with queueing classes it also reads the key's class byte
+ * (one more blocking one-byte copy) to know where the key's ring wraps. */
 tbe_status tbe_queue_of(tbe_engine *engine, uint64_t key, int64_t *request_id, int32_t *permits,
                         uint32_t capacity, uint32_t *count);
 
@@ -624,7 +673,7 @@ tbe_status tbe_stats_import(tbe_engine *engine, uint64_t first, uint64_t count, 
  * it), bit 8 set when pass 0 writes narrow 4-byte records (token bucket and queueing kinds
  * with fold records and the digit stream, and the approximate kind's AcquireCore batches; a
  * batch uses them when it uses fold records), bit 9 set when the queueing kind stores its
- * per-key queue headers in 32 bits (QueueLimit <= 1024). */
+ * per-key queue headers in 32 bits (QueueLimit <= 1024, of every class). */
 tbe_status tbe_layout(const tbe_engine *engine, uint32_t *passes, uint32_t *r_bits, uint32_t *packed);
 
 /* The record layout a batch of n requests takes (diagnostics and tests):
