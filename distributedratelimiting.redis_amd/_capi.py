@@ -47,7 +47,9 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_approx_import_rows", "tbe_create_classes", "tbe_classes", "tbe_set_class_device",
             "tbe_set_class", "tbe_get_class_device", "tbe_get_class", "tbe_stats_batch_device",
             "tbe_stats_batch", "tbe_stats_totals", "tbe_stats_export", "tbe_stats_import",
-            "tbe_create_queue_classes", "tbe_queue_classes")
+            "tbe_create_queue_classes", "tbe_queue_classes", "tbe_create_approx_classes", "tbe_approx_classes",
+            "tbe_approx_collect_classes", "tbe_approx_sync_classes", "tbe_approx_sync_classes_stream",
+            "tbe_approx_refresh_classes")
 # k_stats_batch's shape (csrc/tbe_stats.hpp): requests per workgroup trip and slots of its
 # LDS table; the tests size their cases by them
 STATS_TILE, STATS_SLOTS = 4096, 2048
@@ -93,6 +95,18 @@ class TbeQueueClass(Structure):
     ]
 
 
+def class_mask(classes):
+    """The 256-bit mask of the tbe_approx_*_classes calls (bit c = class c) from an iterable of
+    class numbers."""
+    m = (c_uint64 * 4)()
+    for c in classes:
+        c = int(c)
+        if not 0 <= c < 256:
+            raise ValueError("class numbers lie in [0, 256)")
+        m[c >> 6] |= 1 << (c & 63)
+    return m
+
+
 class TbeError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"{STATUS_NAMES.get(status, status)}: {message}")
@@ -125,6 +139,20 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_create_queue_classes.argtypes = [POINTER(TbeConfig), POINTER(TbeQueueClass), c_uint32, POINTER(c_void_p)]
     lib.tbe_queue_classes.restype = c_int32
     lib.tbe_queue_classes.argtypes = [c_void_p, POINTER(TbeQueueClass), c_uint32, POINTER(c_uint32)]
+    lib.tbe_create_approx_classes.restype = c_int32
+    lib.tbe_create_approx_classes.argtypes = [POINTER(TbeConfig), POINTER(TbeQueueClass), c_uint32, POINTER(c_void_p)]
+    lib.tbe_approx_classes.restype = c_int32
+    lib.tbe_approx_classes.argtypes = [c_void_p, POINTER(TbeQueueClass), c_uint32, POINTER(c_uint32)]
+    lib.tbe_approx_collect_classes.restype = c_int32
+    lib.tbe_approx_collect_classes.argtypes = [c_void_p, c_void_p, POINTER(c_uint64), c_void_p]
+    lib.tbe_approx_sync_classes.restype = c_int32
+    lib.tbe_approx_sync_classes.argtypes = [c_void_p, c_void_p, c_uint32, c_uint32, c_int64, c_int64,
+                                            POINTER(c_uint64), POINTER(c_uint64)]
+    lib.tbe_approx_sync_classes_stream.restype = c_int32
+    lib.tbe_approx_sync_classes_stream.argtypes = [c_void_p, c_void_p, c_uint32, c_uint32, c_int64, c_int64,
+                                                   POINTER(c_uint64), c_void_p, POINTER(c_uint64)]
+    lib.tbe_approx_refresh_classes.restype = c_int32
+    lib.tbe_approx_refresh_classes.argtypes = [c_void_p, c_int64, POINTER(c_uint64), POINTER(c_uint64)]
     lib.tbe_set_class_device.restype = c_int32
     lib.tbe_set_class_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]
     lib.tbe_set_class.restype = c_int32

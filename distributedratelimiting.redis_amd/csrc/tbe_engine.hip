@@ -1985,7 +1985,17 @@ __device__ __forceinline__ uint32_t wait_status(uint32_t v) {
 // FAILED request travels with its reply -- def_out[i] = def_in[perm[i]] for the lanes whose
 // gathered status is FAILED -- and the final pass stores retry[i] in arrival order: the
 // ticks of that deficit (retry_ticks, tbe_retry.hpp), TBE_RETRY_NONE for every other status.
-template <bool FINAL, bool WAIT, int W = 4, bool RETRY = false>
+// CLS (approximate limit classes, final RETRY pass): the rate is that of the class of the
+// request's key, looked up from the caller's key array at the reply's arrival position, for
+// FAILED replies only.
+struct RetryCls {
+    const uint8_t *cls;       // one byte per key
+    const double *rate;       // kMaxClasses fill rates (FillRatePerSecond of each class)
+    const uint64_t *keys;     // the batch's keys in arrival order
+    uint64_t n_keys;          // (a key >= n_keys voided the batch: its reply is never read)
+};
+struct NoRetryCls {};
+template <bool FINAL, bool WAIT, int W = 4, bool RETRY = false, bool CLS = false>
 __global__ __launch_bounds__(kUnBlock) void k_unscatter(uint64_t n, const uint32_t *__restrict__ perm,
                                                           const uint32_t *__restrict__ res_in,
                                                           uint32_t *__restrict__ res_out,
@@ -1996,7 +2006,9 @@ __global__ __launch_bounds__(kUnBlock) void k_unscatter(uint64_t n, const uint32
                                                           const uint32_t *__restrict__ def_in = nullptr,
                                                           uint32_t *__restrict__ def_out = nullptr,
                                                           int64_t *__restrict__ retry = nullptr,
-                                                          double rate = 0.0) {
+                                                          double rate = 0.0,
+                                                          std::conditional_t<CLS, RetryCls, NoRetryCls> RC = {}) {
+    static_assert(!CLS || (FINAL && RETRY), "class rates: the final RETRY pass only");
     // One workgroup per 8192 positions, XCD-aware like k_scatter: the tile's gathers land
     // in the digit runs of the partition tiles it covers, which stay in this XCD's L2.
     const int tid = threadIdx.x;
@@ -2041,6 +2053,12 @@ __global__ __launch_bounds__(kUnBlock) void k_unscatter(uint64_t n, const uint32
             const int e = it * kUnBlock + tid;
             if (e >= nvalid) continue;
             const bool failed = wait_status<W>(r[it]) == TBE_WAIT_FAILED;
+            if constexpr (CLS) {
+                if (failed) {
+                    const uint64_t key = RC.keys[base + e];
+                    rate = RC.rate[key < RC.n_keys ? RC.cls[key] : 0];
+                }
+            }
             if (FINAL) ST_U(retry + base + e, failed ? retry_ticks(df[it], rate) : (int64_t)TBE_RETRY_NONE);
             else if (failed) def_out[base + e] = df[it];
         }
@@ -3626,11 +3644,17 @@ struct AClient {
     int32_t global;  // _globalThrottleScore
     int32_t pad;
 };
-struct AParams {
+// The options one key's decisions depend on: the engine's, or with limit classes those of the
+// key's class (as QOpt for the queueing kind).
+struct AOpt {
     int32_t token_limit;
     int32_t queue_limit;
     int32_t order;          // 0 OldestFirst, 1 NewestFirst
-    uint32_t cap;           // ring entries per key: max(1, QueueLimit) + zero_slots
+    uint32_t cap;           // ring entries the key uses: max(1, QueueLimit) + zero_slots
+};
+// A batch's or an epoch's parameters: the engine's options (class 0's; `cap` is also the ring
+// stride, with classes the largest ring length of any class) and what belongs to the call.
+struct AParams : AOpt {
     int64_t id_base;
     int32_t wait;           // 1: WaitAsyncCore (A:116-183), 0: AcquireCore (A:84-113)
     int32_t zero_slots;     // ring entries a key may give to zero-permit registrations
@@ -3640,6 +3664,34 @@ struct AParams {
     double period_s;        // ReplenishmentPeriod.TotalSeconds (A:443)
 };
 constexpr int64_t kApproxTtlMs = 86400LL * 1000;   // EXPIRE 86400 (A:268)
+// Approximate limit classes (tbe_create_approx_classes): one class on the
+// device is its options, its decay rate (A:224, A:258) and its period in seconds (A:443).  The
+// CLS = true kernels take references into the record of the key's class, so each field is
+// loaded where it is used (a copy of the record per decision spilled in k_fold_q's first
+// form, CHANGELOG.md); the CLS = false ones read AParams from their kernel arguments as before
+// and never see a view.
+struct AClsPar {
+    AOpt o;
+    double decay_rate;
+    double period_s;
+};
+static_assert(sizeof(AClsPar) == 32, "four 8-byte words per class");
+static_assert(sizeof(AOpt) == 16 && sizeof(AParams) == 56, "AParams keeps its argument layout");
+struct AClsView {
+    const uint8_t *cls;    // one byte per key, padded to whole buckets (ClsView::cls)
+    const AClsPar *par;    // kMaxClasses entries
+};
+// The view plus the classes a masked epoch touches (bit c of w[c >> 6]: class c).
+struct AClsMask {
+    const uint8_t *cls;
+    const AClsPar *par;
+    uint64_t w[4];
+    __device__ __forceinline__ bool has(uint32_t c) const {   // (selects: no indexed copy of the argument)
+        const uint64_t x = c < 64 ? w[0] : c < 128 ? w[1] : c < 192 ? w[2] : w[3];
+        return (x >> (c & 63)) & 1u;
+    }
+};
+struct NoACls {};          // what a CLS = false kernel takes in the view's place
 
 __device__ __forceinline__ int32_t wrap_sub(int32_t a, int32_t b) {
     return (int32_t)((uint32_t)a - (uint32_t)b);
@@ -3682,7 +3734,10 @@ static_assert(kAChunk <= 4096, "election tags");
 // written (the un-partition reads a deficit only beside a FAILED status).
 // The RETRY forms ask for 4 waves per SIMD (128 VGPRs, two workgroups per CU): the deficits
 // held across the owner rounds spill at 80.
-template <bool PACKED, bool RETRY = false>
+// CLS (wide records only): the bucket's class bytes sit in LDS beside its rows, and every
+// decision takes its four options from the record of the key's class (CV.par, read through
+// a reference, field by field); the ring stride stays A.cap, the wrap is the class's own.
+template <bool PACKED, bool RETRY = false, bool CLS = false>
 __global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
     const uint32_t *__restrict__ skeys, const int32_t *__restrict__ sperm,
     const uint32_t *__restrict__ sidx, const uint64_t *__restrict__ srec, PackFmt F,
@@ -3691,12 +3746,18 @@ __global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
     uint32_t *__restrict__ res, uint32_t *__restrict__ ev_cause, int64_t *__restrict__ ev_id,
     uint32_t *__restrict__ ev_count, uint32_t ev_cap, const uint32_t *__restrict__ err, uint32_t rw, FoldFmt G,
     const uint64_t *__restrict__ rec0, const AClient *__restrict__ aclient = nullptr,
-    uint32_t *__restrict__ deficit = nullptr) {
+    uint32_t *__restrict__ deficit = nullptr, std::conditional_t<CLS, AClsView, NoACls> CV = {}) {
+    static_assert(!CLS || !PACKED, "classes: wide records only");
     __shared__ ALocal sl[kMaxRows];
     __shared__ uint32_t own[kMaxRows];
     __shared__ uint32_t rbuf[kAChunk];
     __shared__ uint32_t loaded[kMaxRows / 32];
     __shared__ uint32_t dirty[kMaxRows / 32];
+    uint8_t *lcls = nullptr;   // CLS: the bucket's class bytes
+    if constexpr (CLS) {
+        __shared__ uint32_t lcls_w[kMaxRows / 4];
+        lcls = reinterpret_cast<uint8_t *>(lcls_w);
+    }
 
     if (*err) return;
     const int tid = threadIdx.x;
@@ -3727,6 +3788,11 @@ __global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
     for (uint32_t j = tid; j < (R + 31) / 32; j += kFoldBlock) {
         loaded[j] = dense ? ~0u : 0u;
         dirty[j] = 0;
+    }
+    if constexpr (CLS) {   // (cls is padded to whole buckets and r_bits >= 4: whole dwords; read after the
+                           // first chunk's barrier)
+        for (uint32_t j = tid; j < R / 4; j += kFoldBlock)
+            reinterpret_cast<uint32_t *>(lcls)[j] = reinterpret_cast<const uint32_t *>(CV.cls + row0)[j];
     }
 #if TBE_AFOLD_PREFETCH
     uint32_t pf_sink = 0;
@@ -3823,10 +3889,14 @@ __global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
                 pend &= ~(1u << r);
                 ALocal a = sl[kl[r]];
                 const int32_t p = pm[r];
+                // the options of the key's class, or the engine's own
+                const AOpt *kc = nullptr;
+                if constexpr (CLS) kc = &CV.par[lcls[kl[r]]].o;
+                const AOpt &O = CLS ? *kc : static_cast<const AOpt &>(A);
                 uint32_t status;
                 bool modified = false, evaluated = true;
                 const int32_t avail = avail_of(a);
-                if (p > A.token_limit) {                                   // A:87-90 / A:119-122
+                if (p > O.token_limit) {                                   // A:87-90 / A:119-122
                     status = TBE_WAIT_REJECTED;
                     evaluated = false;
                 } else if (p == 0 && (avail > 0 || !A.wait)) {            // A:93-102 / A:127-130
@@ -3841,7 +3911,7 @@ __global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
                     if (a.zc < A.zero_slots) {
                         uint32_t head = a.hc & 0xFFFFu, cnt = a.hc >> 16;
                         uint32_t tail = head + cnt;
-                        if (tail >= A.cap) tail -= A.cap;
+                        if (tail >= O.cap) tail -= O.cap;
                         ring[(row0 + kl[r]) * (uint64_t)A.cap + tail] = (uint64_t)(A.id_base + arrival(r)) << 16;
                         a.hc = (head & 0xFFFFu) | ((cnt + 1) << 16);
                         a.zc = (uint16_t)(a.zc + 1);
@@ -3850,7 +3920,7 @@ __global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
                     } else {
                         status = TBE_WAIT_FAILED;
                     }
-                } else if (avail >= p && avail != 0 && (a.qsum == 0 || A.order == 1)) {  // A:191-209
+                } else if (avail >= p && avail != 0 && (a.qsum == 0 || O.order == 1)) {  // A:191-209
                     a.local = (int32_t)((uint32_t)a.local + (uint32_t)p);
                     modified = true;
                     status = TBE_WAIT_GRANTED;
@@ -3860,9 +3930,9 @@ __global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
                     uint32_t head = a.hc & 0xFFFFu, cnt = a.hc >> 16;
                     uint64_t *__restrict__ kr = ring + (row0 + kl[r]) * (uint64_t)A.cap;
                     bool fail = false;
-                    if ((int64_t)A.queue_limit - a.qsum < p) {             // A:141
-                        if (A.order == 1 && p <= A.queue_limit) {          // A:143-158
-                            while ((int64_t)A.queue_limit - a.qsum < p) {
+                    if ((int64_t)O.queue_limit - a.qsum < p) {             // A:141
+                        if (O.order == 1 && p <= O.queue_limit) {          // A:143-158
+                            while ((int64_t)O.queue_limit - a.qsum < p) {
                                 const uint64_t ent = kr[head];
                                 const uint32_t at = atomicAdd(ev_count, 1u);
                                 if (at < ev_cap) {
@@ -3871,7 +3941,7 @@ __global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
                                 }
                                 a.qsum = (uint16_t)(a.qsum - (uint32_t)(ent & 0xFFFFu));
                                 if ((ent & 0xFFFFu) == 0) a.zc = (uint16_t)(a.zc - 1);   // DequeueHead takes it too
-                                head = (head + 1 == A.cap) ? 0 : head + 1;
+                                head = (head + 1 == O.cap) ? 0 : head + 1;
                                 --cnt;
                             }
                         } else {
@@ -3882,7 +3952,7 @@ __global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
                         status = TBE_WAIT_FAILED;
                     } else {                                               // A:166-181
                         uint32_t tail = head + cnt;
-                        if (tail >= A.cap) tail -= A.cap;
+                        if (tail >= O.cap) tail -= O.cap;
                         kr[tail] = ((uint64_t)(A.id_base + arrival(r)) << 16) | (uint32_t)p;
                         ++cnt;
                         a.qsum = (uint16_t)(a.qsum + (uint32_t)p);
@@ -3894,7 +3964,7 @@ __global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
                 rbuf[r * kFoldBlock + tid] = pack_wait(status, evaluated, (uint32_t)avail_of(a));
                 if constexpr (RETRY) {
                     if (status == TBE_WAIT_FAILED) {   // a failure modifies nothing: `a` is the state it met
-                        df[r] = retry_deficit(aclient[row0 + kl[r]].global, a.local, p, a.qsum, A.token_limit);
+                        df[r] = retry_deficit(aclient[row0 + kl[r]].global, a.local, p, a.qsum, O.token_limit);
                     }
                 }
                 if (modified) {
@@ -3936,10 +4006,19 @@ __global__ __launch_bounds__(kFoldBlock, RETRY ? 4 : TBE_A_WAVES) void k_fold_a(
 }
 
 // A:430-435: count = _localThrottleScore; _localThrottleScore = 0, for every key.
+// CLS: only for the keys of the classes in M; every other key gives 0 and keeps its count.
+template <bool CLS = false>
 __global__ __launch_bounds__(kBlock) void k_approx_collect(uint64_t n_keys, ALocal *__restrict__ alocal,
-                                                           int32_t *__restrict__ counts) {
+                                                           int32_t *__restrict__ counts,
+                                                           std::conditional_t<CLS, AClsMask, NoACls> M = {}) {
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < n_keys; k += stride) {
+        if constexpr (CLS) {
+            if (!M.has(M.cls[k])) {
+                counts[k] = 0;
+                continue;
+            }
+        }
         counts[k] = alocal[k].local;
         alocal[k].local = 0;
     }
@@ -3950,13 +4029,18 @@ __global__ __launch_bounds__(kBlock) void k_approx_collect(uint64_t n_keys, ALoc
 // engine's replica of the global tier (every engine replays the same calls, so the
 // replicas stay bit-identical); take client `my`'s reply (A:440-443: (int)v', and the
 // period through Lua "%.14g" and double.Parse); then drain the queue (A:462-501).
+// CLS: each key of a class in M is synced with its class's decay rate, period, TokenLimit,
+// order and ring length; a key of another class is not touched (nothing read-modify-written,
+// drained or logged).
+template <bool CLS = false>
 __global__ __launch_bounds__(kBlock) void k_approx_sync(
     uint64_t n_keys, ALocal *__restrict__ alocal, AClient *__restrict__ aclient,
     double *__restrict__ gv, double *__restrict__ gp, int64_t *__restrict__ gt,
     const uint64_t *__restrict__ ring, AParams A, const int32_t *__restrict__ all_counts,
     uint32_t n_clients, uint32_t my, int64_t ts_us, int64_t stagger_us,
     uint64_t *__restrict__ log_keyseq, int64_t *__restrict__ log_id, int32_t *__restrict__ log_rem,
-    uint32_t *__restrict__ log_count, uint32_t log_cap, uint32_t write_client) {
+    uint32_t *__restrict__ log_count, uint32_t log_cap, uint32_t write_client,
+    std::conditional_t<CLS, AClsMask, NoACls> M = {}) {
     // the sync times (TIME at A:241-242) of the first clients are the same for every key
     constexpr uint32_t kSyncTimes = 64;
     __shared__ ReqTime crq[kSyncTimes];
@@ -3967,6 +4051,15 @@ __global__ __launch_bounds__(kBlock) void k_approx_sync(
     for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < n_keys; k += stride) {
         // all_counts == nullptr: one client that collects here (A:430-435 fused into the
         // epoch: the local count is swapped to 0 and used as this client's count)
+        const AClsPar *kc = nullptr;   // CLS: the record of the key's class
+        if constexpr (CLS) {
+            const uint32_t c = M.cls[k];
+            if (!M.has(c)) continue;
+            kc = M.par + c;
+        }
+        const AOpt &O = CLS ? kc->o : static_cast<const AOpt &>(A);
+        const double decay_rate = CLS ? kc->decay_rate : A.decay_rate;
+        const double period_s = CLS ? kc->period_s : A.period_s;
         ALocal a = alocal[k];
         const int32_t own = a.local;
         if (!all_counts) a.local = 0;
@@ -3982,7 +4075,7 @@ __global__ __launch_bounds__(kBlock) void k_approx_sync(
             const double pp = present ? p : 0.0;
             const double pt = present ? new_t_of(t) : rq.new_t;
             const double dt = lua_max(0.0, rq.new_t - pt);                    // A:255
-            const double decay = dt * A.decay_rate;
+            const double decay = dt * decay_rate;
             const double nv = lua_max(0.0, pv - decay) +
                               (double)(all_counts ? all_counts[(uint64_t)r * n_keys + k] : own);   // A:258
             const double a8 = pp * 0.8;                                       // A:262
@@ -4000,7 +4093,7 @@ __global__ __launch_bounds__(kBlock) void k_approx_sync(
         gp[k] = p;
         gt[k] = t;
         // A:443: Math.Max(1, Math.Round(P / period)); P / 0 = +inf
-        const double q = A.period_s / my_period;
+        const double q = period_s / my_period;
         const double rnd = __builtin_rint(q);
         const double est = (rnd != rnd) ? rnd : (rnd > 1.0 ? rnd : 1.0);
         // The client view {est, global} only answers queries (the lease path reads the cap
@@ -4014,16 +4107,16 @@ __global__ __launch_bounds__(kBlock) void k_approx_sync(
             ac.pad = 0;
             aclient[k] = ac;
         }
-        const double lim = (double)wrap_sub(A.token_limit, my_global) / est;
+        const double lim = (double)wrap_sub(O.token_limit, my_global) / est;
         a.cap = dotnet_to_int(__builtin_ceil(lim));
         // drain (A:467-501)
         uint32_t head = a.hc & 0xFFFFu, cnt = a.hc >> 16, seq = 0;
         const uint64_t *__restrict__ kr = ring + k * (uint64_t)A.cap;
         while (cnt > 0) {
             uint32_t idx = head;
-            if (A.order == 1) {
+            if (O.order == 1) {
                 idx = head + cnt - 1;
-                if (idx >= A.cap) idx -= A.cap;
+                if (idx >= O.cap) idx -= O.cap;
             }
             const uint64_t ent = kr[idx];
             const int32_t c = (int32_t)(ent & 0xFFFFu);
@@ -4031,7 +4124,7 @@ __global__ __launch_bounds__(kBlock) void k_approx_sync(
             a.qsum = (uint16_t)(a.qsum - (uint32_t)c);
             if (c == 0) a.zc = (uint16_t)(a.zc - 1);
             a.local = (int32_t)((uint32_t)a.local + (uint32_t)c);
-            if (A.order == 0) head = (head + 1 == A.cap) ? 0 : head + 1;
+            if (O.order == 0) head = (head + 1 == O.cap) ? 0 : head + 1;
             --cnt;
             const uint32_t at = atomicAdd(log_count, 1u);
             if (at < log_cap) {
@@ -4290,6 +4383,38 @@ __global__ void k_set_class_write(uint8_t *__restrict__ key_cls, const uint64_t 
     }
 }
 
+// The approximate kind's pair: an id with anything queued (zero-permit registrations included)
+// voids the call, and a written id gets the client side of a limiter freshly constructed with
+// its new class's options over the existing Redis key (A:26-28): cap = TokenLimit, local 0, an
+// empty queue with head 0, est 1, global 0.  The tier row {v, p, t} stays; a local count not
+// yet synced is dropped with the old limiter object.
+__global__ void k_set_class_check_a(const uint64_t *__restrict__ ids, const uint8_t *__restrict__ cls, uint64_t n,
+                                    uint64_t n_keys, uint32_t n_classes, const ALocal *__restrict__ alocal,
+                                    uint32_t *__restrict__ bad) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t k = ids[i];
+        if (k >= n_keys || cls[i] >= n_classes || (alocal[k].hc >> 16) != 0) *bad = 1u;
+    }
+}
+
+__global__ void k_set_class_write_a(uint8_t *__restrict__ key_cls, const uint64_t *__restrict__ ids,
+                                    const uint8_t *__restrict__ cls, uint64_t n, const uint32_t *__restrict__ bad,
+                                    uint32_t *__restrict__ sticky, const AClsPar *__restrict__ par,
+                                    ALocal *__restrict__ alocal, AClient *__restrict__ aclient) {
+    if (*bad) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) *sticky = 1u;
+        return;
+    }
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t k = ids[i];
+        key_cls[k] = cls[i];
+        alocal[k] = ALocal{par[cls[i]].o.token_limit, 0, 0, 0, 0u};
+        aclient[k] = AClient{1.0, 0, 0};
+    }
+}
+
 // out[i] = class of ids[i]; an id >= n_keys sets *bad and the sticky flag (its byte reads 0).
 // key_cls == nullptr: an engine without extra classes, every key in class 0.
 __global__ void k_get_class(const uint8_t *__restrict__ key_cls, const uint64_t *__restrict__ ids, uint64_t n,
@@ -4332,14 +4457,18 @@ __device__ __forceinline__ ALocal alocal_load_nt(const ALocal *p) {
 // decayed to 0 by its own operations (A:255-258).  aclient == nullptr: the view is derived
 // (aclient_lazy), its global score is (int32)(int64)gv[k] and AClient is not read.  One key
 // per lane: 16 B of ALocal, 8 B each of v and t (coalesced), 4 of the 16 B of AClient.
+// CLS: rule 3 decays with the rate of the key's class.
+template <bool CLS = false>
 __global__ __launch_bounds__(kBlock) void k_approx_idle(const ALocal *__restrict__ alocal,
                                                         const AClient *__restrict__ aclient,
                                                         const double *__restrict__ gv, const int64_t *__restrict__ gt,
                                                         uint64_t first, uint64_t count, int64_t ts_us,
-                                                        double decay_rate, uint8_t *__restrict__ idle) {
+                                                        double decay_rate, uint8_t *__restrict__ idle,
+                                                        std::conditional_t<CLS, AClsView, NoACls> CV = {}) {
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= count) return;
     const uint64_t k = first + i;
+    if constexpr (CLS) decay_rate = CV.par[CV.cls[k]].decay_rate;
     const ReqTime rq = req_time(ts_us, kApproxTtlMs);
     const ALocal a = alocal_load_nt(alocal + k);
     const double v = ld_nt(gv + k);
@@ -4357,14 +4486,18 @@ __global__ __launch_bounds__(kBlock) void k_approx_idle(const ALocal *__restrict
 }
 
 // Every flagged key of the range gets k_init_approx's state; unflagged rows are not written.
+// CLS: cap = TokenLimit of the key's class; the class byte stays.
+template <bool CLS = false>
 __global__ __launch_bounds__(kBlock) void k_approx_reset(ALocal *__restrict__ alocal, AClient *__restrict__ aclient,
                                                          double *__restrict__ gv, double *__restrict__ gp,
                                                          int64_t *__restrict__ gt, uint64_t first, uint64_t count,
-                                                         const uint8_t *__restrict__ flags, int32_t token_limit) {
+                                                         const uint8_t *__restrict__ flags, int32_t token_limit,
+                                                         std::conditional_t<CLS, AClsView, NoACls> CV = {}) {
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= count) return;
     if (!ld_nt(flags + i)) return;
     const uint64_t k = first + i;
+    if constexpr (CLS) token_limit = CV.par[CV.cls[k]].o.token_limit;
     alocal[k] = ALocal{token_limit, 0, 0, 0, 0u};
     aclient[k] = AClient{1.0, 0, 0};
     gv[k] = 0.0;
@@ -4597,6 +4730,18 @@ struct tbe_engine {
     uint32_t *counters = nullptr;  // [0] eviction count, [1] refresh log count
     // approximate kind
     AParams ap{};
+    // approximate limit classes (tbe_create_approx_classes; wide records): every class's five
+    // options and its device record, class 0 the config's own (a plain engine holds that one
+    // entry on the host only).  cls, acls_par and acls_rate exist only with extra classes; then
+    // ap.cap is the ring stride, the largest ring length of any class, and the client views
+    // are written by every sync (never aclient_lazy).
+    std::vector<tbe_queue_class> aclass_opts;
+    std::vector<AClsPar> aclass_par;
+    AClsPar *acls_par = nullptr;
+    double *acls_rate = nullptr;   // the classes' fill rates alone (k_unscatter's RETRY form)
+    bool a_newest = false;         // some class is NewestFirst: a wait batch may evict
+    AClsView acls_view() const { return AClsView{cls, acls_par}; }
+    AClsMask acls_mask(const uint64_t *m) const { return AClsMask{cls, acls_par, {m[0], m[1], m[2], m[3]}}; }
     ALocal *alocal = nullptr;
     AClient *aclient = nullptr;
     bool aclient_lazy = false;    // the last sync had one client: aclient is derived on demand
@@ -5123,7 +5268,19 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
         a.id_base = id_base;
         a.wait = e->wait_mode;
         a.ai_base = ai_base;
-        if (retry && e->packed)
+        if (e->acls_par && retry)   // a classed engine moves wide records (create_engine)
+            k_fold_a<false, true, true><<<e->nbuckets, kFoldBlock, 0, sf>>>(
+                sorted.keys, sorted.permits, sorted.idx, nullptr, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
+                e->alocal, e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
+                (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(), G, rec0, e->aclient,
+                w.def[0], e->acls_view());
+        else if (e->acls_par)
+            k_fold_a<false, false, true><<<e->nbuckets, kFoldBlock, 0, sf>>>(
+                sorted.keys, sorted.permits, sorted.idx, nullptr, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
+                e->alocal, e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
+                (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(), G, rec0, nullptr,
+                nullptr, e->acls_view());
+        else if (retry && e->packed)
             k_fold_a<true, true><<<fold_grid, kFoldBlock, 0, sf>>>(
                 nullptr, nullptr, nullptr, sorted.rec, e->pf, w.bstart, e->r_bits, e->cfg.n_keys, e->alocal,
                 e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
@@ -5276,6 +5433,14 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
         k_unrank<4, true, true><<<ntiles, kPartBlock, 0, sf>>>(
             n, w.dig0, w.pass[0].tileprefix, w.pass[0].blockprefix, w.pass[0].digit_total, tpb, w.res[cur],
             granted, remaining, w.def[cur], retry, e->ap.decay_rate);
+    else if (retry && e->acls_par && e->medium)
+        k_unscatter<true, true, 2, true, true><<<untiles, kUnBlock, 0, sf>>>(
+            n, w.pass[0].perm, w.res[cur], nullptr, granted, remaining, w.err, e->sticky, w.def[cur], nullptr,
+            retry, 0.0, RetryCls{e->cls, e->acls_rate, keys, e->cfg.n_keys});
+    else if (retry && e->acls_par)
+        k_unscatter<true, true, 4, true, true><<<untiles, kUnBlock, 0, sf>>>(
+            n, w.pass[0].perm, w.res[cur], nullptr, granted, remaining, w.err, e->sticky, w.def[cur], nullptr,
+            retry, 0.0, RetryCls{e->cls, e->acls_rate, keys, e->cfg.n_keys});
     else if (retry && e->medium)
         k_unscatter<true, true, 2, true><<<untiles, kUnBlock, 0, sf>>>(
             n, w.pass[0].perm, w.res[cur], nullptr, granted, remaining, w.err, e->sticky, w.def[cur], nullptr,
@@ -5333,7 +5498,7 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
         k_stats_batch<<<sgrid, kStatsBlock, 0, sf>>>(keys, granted, n, w.err, e->stats_view());
         // NewestFirst evictions fail the evicted lease.  A chunk of a chunked host batch
         // (in_ready) leaves them to its caller: the log runs on over the chunks.
-        const int32_t order = approx ? e->ap.order : (int32_t)e->q_newest;   // (some class evicts)
+        const int32_t order = approx ? (int32_t)e->a_newest : (int32_t)e->q_newest;   // (some class evicts)
         if (wait && e->wait_mode == 1 && order == 1 && !in_ready && e->ev_cause)
             k_stats_log<<<64, kStatsBlock, 0, sf>>>(e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu),
                                                     e->ev_cause, keys, n, ai_base, nullptr, e->cfg.n_keys, w.err,
@@ -5409,7 +5574,8 @@ static const char *class_params(int32_t token_limit, int32_t tokens_per_period, 
 }
 
 static tbe_status create_engine(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
-                                tbe_engine **out_engine, const tbe_queue_class *qextra = nullptr);
+                                tbe_engine **out_engine, const tbe_queue_class *qextra = nullptr,
+                                const tbe_queue_class *aextra = nullptr);
 
 tbe_status tbe_create(const tbe_config *config, tbe_engine **out_engine) {
     return create_engine(config, nullptr, 0, out_engine);
@@ -5444,6 +5610,37 @@ tbe_status tbe_create_queue_classes(const tbe_config *config, const tbe_queue_cl
     return create_engine(config, nullptr, n_extra, out_engine, extra);
 }
 
+// The checks tbe_create makes on an approximate config's own options, on one class; the ring
+// length includes the engine-wide zero_wait_slots.
+static const char *approx_class_params(const tbe_queue_class &q, int32_t zero_wait_slots, TbParams *out) {
+    if (const char *msg = queue_class_params(q, out)) return msg;
+    if ((int64_t)std::max(1, q.queue_limit) + zero_wait_slots > 0xFFFF)
+        return "max(1, QueueLimit) + zero_wait_slots must be <= 65535";
+    return nullptr;
+}
+
+tbe_status tbe_create_approx_classes(const tbe_config *config, const tbe_queue_class *extra, uint32_t n_extra,
+                                     tbe_engine **out_engine) {
+    if (!out_engine) return create_fail(TBE_EINVAL, "out_engine is NULL");
+    *out_engine = nullptr;
+    if (!config || config->struct_size < offsetof(tbe_config, zero_wait_slots))
+        return create_fail(TBE_EINVAL, "config is NULL or struct_size too small");
+    if (config->kind != TBE_KIND_APPROXIMATE)
+        return create_fail(TBE_EINVAL, "approximate limit classes: approximate kind only");
+    if (n_extra == 0) return create_engine(config, nullptr, 0, out_engine);
+    if (n_extra > kMaxClasses - 1) return create_fail(TBE_EINVAL, "an engine holds at most 256 limit classes (255 extra)");
+    if (!extra) return create_fail(TBE_EINVAL, "extra is NULL with n_extra > 0");
+    // (a config from the round-1 header has no zero_wait_slots: it reads as 0)
+    const int32_t zs = config->struct_size >= offsetof(tbe_config, zero_wait_slots) + sizeof(int32_t)
+                           ? config->zero_wait_slots : 0;
+    if (zs < 0) return create_fail(TBE_EINVAL, "zero_wait_slots must be >= 0");
+    for (uint32_t i = 0; i < n_extra; ++i) {
+        TbParams p;
+        if (const char *msg = approx_class_params(extra[i], zs, &p)) return create_fail(TBE_EINVAL, msg);
+    }
+    return create_engine(config, nullptr, n_extra, out_engine, nullptr, extra);
+}
+
 tbe_status tbe_create_classes(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
                               tbe_engine **out_engine) {
     if (!out_engine) return create_fail(TBE_EINVAL, "out_engine is NULL");
@@ -5468,8 +5665,11 @@ tbe_status tbe_create_classes(const tbe_config *config, const tbe_class *extra, 
 // extra != NULL: a classed engine, laid out as TBE_FLAG_NO_PACK | NO_HOT | NO_NARROW (wide
 // records, 4-byte replies, no hot runs: the forms whose folds know about classes).
 // qextra != NULL: a classed queueing engine, laid out as TBE_FLAG_NO_PACK | NO_NARROW.
+// aextra != NULL: a classed approximate engine, laid out as TBE_FLAG_NO_PACK; its replies
+// take two bytes when the largest TokenLimit of any class allows it.
 static tbe_status create_engine(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
-                                tbe_engine **out_engine, const tbe_queue_class *qextra) {
+                                tbe_engine **out_engine, const tbe_queue_class *qextra,
+                                const tbe_queue_class *aextra) {
     if (!out_engine) return create_fail(TBE_EINVAL, "out_engine is NULL");
     *out_engine = nullptr;
     // struct_size versions the config: a caller built against the round-1 header (which
@@ -5482,8 +5682,12 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
     std::memcpy(&c_in, config, std::min<size_t>(config->struct_size, sizeof c_in));
     if (extra) c_in.flags |= TBE_FLAG_NO_PACK | TBE_FLAG_NO_HOT | TBE_FLAG_NO_NARROW;
     if (qextra) c_in.flags |= TBE_FLAG_NO_PACK | TBE_FLAG_NO_NARROW;
+    if (aextra) {
+        c_in.flags |= TBE_FLAG_NO_PACK;
+        qextra = nullptr;
+    }
     const tbe_config &c = c_in;
-    const bool classed = extra || qextra;
+    const bool classed = extra || qextra || aextra;
     if (c.kind != TBE_KIND_TOKEN_BUCKET && c.kind != TBE_KIND_QUEUEING &&
         c.kind != TBE_KIND_APPROXIMATE)
         return create_fail(TBE_EINVAL, "unknown kind");
@@ -5527,9 +5731,10 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
     e->class_par.push_back(e->params);
     for (uint32_t i = 0; i < n_extra; ++i) {   // (validated by tbe_create_classes / tbe_create_queue_classes)
         TbParams p{};
-        const tbe_class o = qextra ? tbe_class{qextra[i].token_limit, qextra[i].tokens_per_period,
-                                               qextra[i].replenishment_period_ticks}
-                                   : extra[i];
+        const tbe_queue_class *five = qextra ? qextra : aextra;
+        const tbe_class o = five ? tbe_class{five[i].token_limit, five[i].tokens_per_period,
+                                             five[i].replenishment_period_ticks}
+                                 : extra[i];
         (void)class_params(o.token_limit, o.tokens_per_period, o.replenishment_period_ticks, &p);
         e->class_opts.push_back(o);
         e->class_par.push_back(p);
@@ -5543,6 +5748,24 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
             const tbe_queue_class &q = e->qclass_opts[i];
             e->qclass_par.push_back(QClsPar{e->class_par[i], QOpt{q.token_limit, q.queue_limit, q.queue_order,
                                                                      (uint32_t)std::max(1, q.queue_limit)}});
+        }
+    }
+    int32_t max_token_limit = c.token_limit;   // of any class: the reply width of the approximate kind
+    if (c.kind == TBE_KIND_APPROXIMATE) {
+        e->aclass_opts.push_back(tbe_queue_class{c.token_limit, c.tokens_per_period, c.replenishment_period_ticks,
+                                                 c.queue_limit, c.queue_order});
+        for (uint32_t i = 0; i < n_extra && aextra; ++i) e->aclass_opts.push_back(aextra[i]);
+        for (size_t i = 0; i < e->aclass_opts.size(); ++i) {
+            const tbe_queue_class &q = e->aclass_opts[i];
+            e->aclass_par.push_back(AClsPar{AOpt{q.token_limit, q.queue_limit, q.queue_order,
+                                                 (uint32_t)(std::max(1, q.queue_limit) + c.zero_wait_slots)},
+                                            e->class_par[i].rate,
+                                            (double)q.replenishment_period_ticks / 10000000.0});
+            max_token_limit = std::max(max_token_limit, q.token_limit);
+            e->a_newest |= q.queue_order == 1;
+            e->q_per_key = std::max<uint64_t>(
+                e->q_per_key, std::min<uint64_t>(e->aclass_par.back().o.cap,
+                                                 (uint64_t)std::max(q.token_limit, 1) + (uint64_t)c.zero_wait_slots));
         }
     }
     const int bbits = ceil_log2(e->nbuckets);
@@ -5595,7 +5818,7 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
         e->narrow = (c.flags & TBE_FLAG_NO_NARROW) == 0 &&
                     ((e->packed && c.kind == TBE_KIND_TOKEN_BUCKET && c.token_limit <= 127) ||
                      (c.kind == TBE_KIND_QUEUEING && c.token_limit <= 62));
-        e->medium = (c.flags & TBE_FLAG_NO_NARROW) == 0 && !e->narrow && c.token_limit <= (int32_t)kRemNone16 - 1 &&
+        e->medium = (c.flags & TBE_FLAG_NO_NARROW) == 0 && !e->narrow && max_token_limit <= (int32_t)kRemNone16 - 1 &&
                     (c.kind == TBE_KIND_QUEUEING || c.kind == TBE_KIND_APPROXIMATE);
     }
 
@@ -5633,6 +5856,8 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
         if (dalloc(&e->cls_par, kMaxClasses * sizeof(TbParams)) != hipSuccess) return bail(TBE_ENOMEM);
     }
     if (qextra && dalloc(&e->qcls_par, kMaxClasses * sizeof(QClsPar)) != hipSuccess) return bail(TBE_ENOMEM);
+    if (aextra && dalloc(&e->acls_par, kMaxClasses * sizeof(AClsPar)) != hipSuccess) return bail(TBE_ENOMEM);
+    if (aextra && dalloc(&e->acls_rate, kMaxClasses * sizeof(double)) != hipSuccess) return bail(TBE_ENOMEM);
     if (e->hot_cap)
         for (auto &hs : e->hot)
             if (dalloc(&hs, sizeof(HotSet)) != hipSuccess) return bail(TBE_ENOMEM);
@@ -5666,7 +5891,8 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
         e->ap.queue_limit = c.queue_limit;
         e->ap.order = c.queue_order;
         e->ap.zero_slots = c.zero_wait_slots;
-        e->ap.cap = (uint32_t)(std::max(1, c.queue_limit) + c.zero_wait_slots);
+        e->ap.cap = 0;   // classes: the ring stride is the longest ring of any class
+        for (const AClsPar &a : e->aclass_par) e->ap.cap = std::max(e->ap.cap, a.o.cap);
         e->ap.decay_rate = rate;
         e->ap.period_s = (double)c.replenishment_period_ticks / 10000000.0;
         ring_n = c.n_keys * (uint64_t)e->ap.cap;
@@ -5705,6 +5931,8 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
     if (classed) {
         zero(e->cls_par, kMaxClasses * sizeof(TbParams));
         zero(e->qcls_par, kMaxClasses * sizeof(QClsPar));
+        zero(e->acls_par, kMaxClasses * sizeof(AClsPar));
+        zero(e->acls_rate, kMaxClasses * sizeof(double));
         if (ie != hipSuccess) return bail(TBE_EDEVICE);
         k_init_cls<<<2048, 256, 0, e->stream>>>(e->cls, cls_bytes / 16);
         // (class_par outlives the copy: the stream is synchronised below)
@@ -5714,6 +5942,17 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
         if (qextra && hipMemcpyAsync(e->qcls_par, e->qclass_par.data(), e->qclass_par.size() * sizeof(QClsPar),
                                      hipMemcpyHostToDevice, e->stream) != hipSuccess)
             return bail(TBE_EDEVICE);
+        if (aextra) {
+            std::vector<double> rates;
+            for (const AClsPar &a : e->aclass_par) rates.push_back(a.decay_rate);
+            // (pageable sources: the copies are staged before hipMemcpyAsync returns)
+            if (hipMemcpyAsync(e->acls_par, e->aclass_par.data(), e->aclass_par.size() * sizeof(AClsPar),
+                               hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+                hipMemcpyAsync(e->acls_rate, rates.data(), rates.size() * sizeof(double), hipMemcpyHostToDevice,
+                               e->stream) != hipSuccess ||
+                hipStreamSynchronize(e->stream) != hipSuccess)
+                return bail(TBE_EDEVICE);
+        }
     }
     if (c.kind == TBE_KIND_APPROXIMATE)
         k_init_approx<<<2048, 256, 0, e->stream>>>(c.n_keys, e->alocal, e->aclient, e->gv, e->gp, e->gt,
@@ -5738,6 +5977,8 @@ void tbe_destroy(tbe_engine *e) {
     dfree(e->cls);
     dfree(e->cls_par);
     dfree(e->qcls_par);
+    dfree(e->acls_par);
+    dfree(e->acls_rate);
     dfree(e->alocal);
     dfree(e->aclient);
     dfree(e->gv);
@@ -6197,14 +6438,19 @@ tbe_status tbe_queue_classes(const tbe_engine *e, tbe_queue_class *out, uint32_t
     return TBE_OK;
 }
 
-static const char *kNoClasses = "limit classes: token-bucket and queueing kinds only";
+tbe_status tbe_approx_classes(const tbe_engine *e, tbe_queue_class *out, uint32_t capacity, uint32_t *n_classes) {
+    if (!e || !n_classes) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_APPROXIMATE) return TBE_EINVAL;
+    *n_classes = (uint32_t)e->aclass_opts.size();
+    for (uint32_t i = 0; out && i < capacity && i < e->aclass_opts.size(); ++i) out[i] = e->aclass_opts[i];
+    return TBE_OK;
+}
 
 // On the engine's stream, where every kernel that touches table or classes runs, a caller's
 // stream joined before and after: tbe_import_rows_device's ordering.
 tbe_status tbe_set_class_device(tbe_engine *e, const uint64_t *d_ids, const uint8_t *d_cls, uint64_t n,
                                 void *stream) {
     if (!e) return TBE_EINVAL;
-    if (e->cfg.kind == TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, kNoClasses);
     if (n == 0) return TBE_OK;
     if (!d_ids || !d_cls) return fail(e, TBE_EINVAL, "null buffer");
     HIP_TRY(e, hipSetDevice(e->device));
@@ -6217,7 +6463,12 @@ tbe_status tbe_set_class_device(tbe_engine *e, const uint64_t *d_ids, const uint
     HIP_TRY(e, hipMemsetAsync(e->rows_bad, 0, sizeof(uint32_t), st));
     const unsigned blocks = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192);
     // the validating pass ends before the first class is written (one stream)
-    if (e->qcls_par) {   // queueing classes: ids with queued entries void the call, written ids get head 0
+    if (e->acls_par) {   // approximate classes: the same rule, written ids get a fresh limiter's client side
+        k_set_class_check_a<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys, (uint32_t)e->class_par.size(),
+                                                       e->alocal, e->rows_bad);
+        k_set_class_write_a<<<blocks, kBlock, 0, st>>>(e->cls, d_ids, d_cls, n, e->rows_bad, e->sticky, e->acls_par,
+                                                       e->alocal, e->aclient);
+    } else if (e->qcls_par) {   // queueing classes: ids with queued entries void the call, written ids get head 0
         with_qhdr(e, [&](auto *qh) {
             k_set_class_check_q<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys,
                                                            (uint32_t)e->class_par.size(), qh, e->rows_bad);
@@ -6242,7 +6493,6 @@ tbe_status tbe_set_class_device(tbe_engine *e, const uint64_t *d_ids, const uint
 
 tbe_status tbe_set_class(tbe_engine *e, const uint64_t *ids, const uint8_t *cls, uint64_t n) {
     if (!e) return TBE_EINVAL;
-    if (e->cfg.kind == TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, kNoClasses);
     if (n == 0) return TBE_OK;
     if (!ids || !cls) return fail(e, TBE_EINVAL, "null buffer");
     for (uint64_t i = 0; i < n; ++i) {
@@ -6259,7 +6509,7 @@ tbe_status tbe_set_class(tbe_engine *e, const uint64_t *ids, const uint8_t *cls,
     hipError_t hrc = hipMemcpy(d_ids, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice);
     if (hrc == hipSuccess) hrc = hipMemcpy(d_cls, cls, n, hipMemcpyHostToDevice);
     tbe_status rc = TBE_OK;
-    if (hrc == hipSuccess && e->qcls_par) {
+    if (hrc == hipSuccess && (e->qcls_par || e->acls_par)) {
         // queueing classes: the non-empty-queue rule is only known on the device.  The check
         // alone runs first, so a void call returns TBE_EINVAL and leaves the sticky flag of
         // earlier device batches as it is; the device form below checks once more (a second
@@ -6269,10 +6519,16 @@ tbe_status tbe_set_class(tbe_engine *e, const uint64_t *ids, const uint8_t *cls,
         if (hrc == hipSuccess) hrc = hipMemsetAsync(e->rows_bad, 0, sizeof(uint32_t), e->stream);
         if (hrc == hipSuccess) {
             const unsigned blocks = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192);
-            with_qhdr(e, [&](auto *qh) {
-                k_set_class_check_q<<<blocks, kBlock, 0, e->stream>>>(d_ids, d_cls, n, e->cfg.n_keys,
-                                                                      (uint32_t)e->class_par.size(), qh, e->rows_bad);
-            });
+            if (e->acls_par)
+                k_set_class_check_a<<<blocks, kBlock, 0, e->stream>>>(d_ids, d_cls, n, e->cfg.n_keys,
+                                                                      (uint32_t)e->class_par.size(), e->alocal,
+                                                                      e->rows_bad);
+            else
+                with_qhdr(e, [&](auto *qh) {
+                    k_set_class_check_q<<<blocks, kBlock, 0, e->stream>>>(d_ids, d_cls, n, e->cfg.n_keys,
+                                                                          (uint32_t)e->class_par.size(), qh,
+                                                                          e->rows_bad);
+                });
             hrc = hipGetLastError();
         }
         if (hrc == hipSuccess) hrc = hipMemcpyAsync(&bad, e->rows_bad, sizeof bad, hipMemcpyDeviceToHost, e->stream);
@@ -6292,7 +6548,6 @@ tbe_status tbe_set_class(tbe_engine *e, const uint64_t *ids, const uint8_t *cls,
 
 tbe_status tbe_get_class_device(tbe_engine *e, const uint64_t *d_ids, uint64_t n, uint8_t *d_cls, void *stream) {
     if (!e) return TBE_EINVAL;
-    if (e->cfg.kind == TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, kNoClasses);
     if (n == 0) return TBE_OK;
     if (!d_ids || !d_cls) return fail(e, TBE_EINVAL, "null buffer");
     HIP_TRY(e, hipSetDevice(e->device));
@@ -6313,7 +6568,6 @@ tbe_status tbe_get_class_device(tbe_engine *e, const uint64_t *d_ids, uint64_t n
 
 tbe_status tbe_get_class(tbe_engine *e, const uint64_t *ids, uint64_t n, uint8_t *cls) {
     if (!e) return TBE_EINVAL;
-    if (e->cfg.kind == TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, kNoClasses);
     if (n == 0) return TBE_OK;
     if (!ids || !cls) return fail(e, TBE_EINVAL, "null buffer");
     for (uint64_t i = 0; i < n; ++i)
@@ -6413,7 +6667,7 @@ static tbe_status status_batch_device(tbe_engine *e, const uint64_t *d_keys, con
     if (id_base < 0 || (uint64_t)id_base + n > (1ull << 47))
         return fail(e, TBE_EINVAL, "request ids must lie in [0, 2^47)");
     HIP_TRY(e, hipSetDevice(e->device));
-    const int32_t order = e->cfg.kind == TBE_KIND_APPROXIMATE ? e->ap.order : (int32_t)e->q_newest;
+    const int32_t order = e->cfg.kind == TBE_KIND_APPROXIMATE ? (int32_t)e->a_newest : (int32_t)e->q_newest;
     const bool may_evict = e->wait_mode == 1 && order == 1;
     if (may_evict) {
         const uint64_t need_ev = e->queued_total + n;
@@ -6569,7 +6823,7 @@ static tbe_status status_chunked(tbe_engine *e, const uint64_t *keys, const int3
                                   e->cout));
     }
     HIP_TRY(e, hipMemcpyAsync(nev, e->counters, sizeof(uint32_t), hipMemcpyDeviceToHost, e->cout));
-    const int32_t order = e->cfg.kind == TBE_KIND_APPROXIMATE ? e->ap.order : (int32_t)e->q_newest;
+    const int32_t order = e->cfg.kind == TBE_KIND_APPROXIMATE ? (int32_t)e->a_newest : (int32_t)e->q_newest;
     if (e->stats() && e->wait_mode == 1 && order == 1) {
         // the evictions of all chunks, once: their causes index the whole staged batch
         k_stats_log<<<64, kStatsBlock, 0, e->stream>>>(e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu),
@@ -6750,9 +7004,11 @@ tbe_status tbe_refresh(tbe_engine *e, int64_t ts_us, uint64_t *n_granted) {
 
 tbe_status tbe_refresh_bound(tbe_engine *e, uint64_t *bound) {
     if (!e || !bound) return TBE_EINVAL;
-    if (e->cfg.kind != TBE_KIND_QUEUEING) return fail(e, TBE_EINVAL, "not a queueing engine");
+    if (e->cfg.kind == TBE_KIND_TOKEN_BUCKET) return fail(e, TBE_EINVAL, "engine has no queues");
     // every drained entry holds >= 1 permit (zero-permit requests are never queued) and a
-    // tick grants at most TokenLimit tokens per key (q_per_key: of the class that can grant most)
+    // tick grants at most TokenLimit tokens per key (q_per_key: of the class that can grant most).
+    // Approximate kind: the ring length in place of max(1, QueueLimit), and the zero-permit
+    // registrations a sync completes beside the TokenLimit permits it can grant (A:474).
     *bound = std::min<uint64_t>(e->queued_total, e->cfg.n_keys * e->q_per_key);
     return TBE_OK;
 }
@@ -6825,21 +7081,70 @@ tbe_status tbe_wait_batch_tick_device(tbe_engine *e, const uint64_t *d_keys, con
     return TBE_OK;
 }
 
-tbe_status tbe_approx_collect(tbe_engine *e, int32_t *d_counts, void *stream) {
-    if (!e || !d_counts) return TBE_EINVAL;
+// The class mask of the *_classes calls: NULL or a bit at or above the number of classes is
+// TBE_EINVAL, decided before the device is touched.
+static const uint64_t kAllClasses[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+static tbe_status approx_mask_args(tbe_engine *e, const uint64_t *mask) {
     if (e->cfg.kind != TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, "not an approximate engine");
+    if (!mask) return fail(e, TBE_EINVAL, "mask is NULL");
+    const uint32_t nc = (uint32_t)e->aclass_opts.size();
+    for (uint32_t c = nc; c < kMaxClasses; ++c)
+        if ((mask[c >> 6] >> (c & 63)) & 1u) return fail(e, TBE_EINVAL, "mask names class %u of %u", c, nc);
+    return TBE_OK;
+}
+
+static tbe_status approx_collect(tbe_engine *e, int32_t *d_counts, void *stream, const uint64_t *mask) {
     HIP_TRY(e, hipSetDevice(e->device));
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
     const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
-    k_approx_collect<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->alocal, d_counts);
+    if (e->acls_par)
+        k_approx_collect<true><<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->alocal, d_counts,
+                                                                    e->acls_mask(mask));
+    else if (mask[0] & 1u)
+        k_approx_collect<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->alocal, d_counts);
+    else   // a plain engine without class 0: every key gives 0 and keeps its count
+        HIP_TRY(e, hipMemsetAsync(d_counts, 0, e->cfg.n_keys * sizeof(int32_t), st));
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipStreamSynchronize(st));
     return TBE_OK;
 }
 
+tbe_status tbe_approx_collect_classes(tbe_engine *e, int32_t *d_counts, const uint64_t *mask, void *stream) {
+    if (!e || !d_counts) return TBE_EINVAL;
+    if (tbe_status rc = approx_mask_args(e, mask); rc != TBE_OK) return rc;
+    return approx_collect(e, d_counts, stream, mask);
+}
+
+tbe_status tbe_approx_collect(tbe_engine *e, int32_t *d_counts, void *stream) {
+    if (!e || !d_counts) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, "not an approximate engine");
+    return approx_collect(e, d_counts, stream, kAllClasses);
+}
+
 static tbe_status approx_sync(tbe_engine *e, const int32_t *d_all_counts, uint32_t n_clients,
                               uint32_t my_client, int64_t ts_us, int64_t stagger_us, uint64_t *n_granted,
-                              hipStream_t producer = nullptr);
+                              hipStream_t producer = nullptr, const uint64_t *mask = kAllClasses);
+tbe_status tbe_approx_sync_classes(tbe_engine *e, const int32_t *d_all_counts, uint32_t n_clients,
+                                   uint32_t my_client, int64_t ts_us, int64_t stagger_us, const uint64_t *mask,
+                                   uint64_t *n_granted) {
+    if (!e || !d_all_counts || !n_granted) return TBE_EINVAL;
+    if (tbe_status rc = approx_mask_args(e, mask); rc != TBE_OK) return rc;
+    return approx_sync(e, d_all_counts, n_clients, my_client, ts_us, stagger_us, n_granted, nullptr, mask);
+}
+tbe_status tbe_approx_sync_classes_stream(tbe_engine *e, const int32_t *d_all_counts, uint32_t n_clients,
+                                          uint32_t my_client, int64_t ts_us, int64_t stagger_us,
+                                          const uint64_t *mask, void *stream, uint64_t *n_granted) {
+    if (!e || !d_all_counts || !n_granted) return TBE_EINVAL;
+    if (tbe_status rc = approx_mask_args(e, mask); rc != TBE_OK) return rc;
+    return approx_sync(e, d_all_counts, n_clients, my_client, ts_us, stagger_us, n_granted, (hipStream_t)stream,
+                       mask);
+}
+tbe_status tbe_approx_refresh_classes(tbe_engine *e, int64_t ts_us, const uint64_t *mask, uint64_t *n_granted) {
+    if (!e || !n_granted) return TBE_EINVAL;
+    if (tbe_status rc = approx_mask_args(e, mask); rc != TBE_OK) return rc;
+    if (ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+    return approx_sync(e, nullptr, 1, 0, ts_us, 0, n_granted, nullptr, mask);
+}
 tbe_status tbe_approx_sync(tbe_engine *e, const int32_t *d_all_counts, uint32_t n_clients,
                            uint32_t my_client, int64_t ts_us, int64_t stagger_us, uint64_t *n_granted) {
     if (!e || !d_all_counts || !n_granted) return TBE_EINVAL;
@@ -6856,13 +7161,14 @@ tbe_status tbe_approx_sync_stream(tbe_engine *e, const int32_t *d_all_counts, ui
 // collective that exchanged them); the sync kernel is ordered after it by an event.
 static tbe_status approx_sync(tbe_engine *e, const int32_t *d_all_counts, uint32_t n_clients,
                               uint32_t my_client, int64_t ts_us, int64_t stagger_us, uint64_t *n_granted,
-                              hipStream_t producer) {
+                              hipStream_t producer, const uint64_t *mask) {
     if (!e || !n_granted) return TBE_EINVAL;
     if (e->cfg.kind != TBE_KIND_APPROXIMATE) return fail(e, TBE_EINVAL, "not an approximate engine");
     if (n_clients == 0 || my_client >= n_clients || ts_us < 0 || stagger_us < 0)
         return fail(e, TBE_EINVAL, "bad sync arguments");
     *n_granted = 0;
     e->drained.clear();
+    if (!e->acls_par && !(mask[0] & 1u)) return TBE_OK;   // a plain engine without class 0: nothing to sync
     HIP_TRY(e, hipSetDevice(e->device));
     if (producer && producer != e->stream) {
         HIP_TRY(e, hipEventRecord(e->ev_in, producer));
@@ -6886,13 +7192,19 @@ static tbe_status approx_sync(tbe_engine *e, const int32_t *d_all_counts, uint32
     hipStream_t st = e->stream;
     HIP_TRY(e, hipMemsetAsync(e->counters + 1, 0, sizeof(uint32_t), st));
     const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
-    k_approx_sync<<<(unsigned)blocks, kBlock, 0, st>>>(
-        e->cfg.n_keys, e->alocal, e->aclient, e->gv, e->gp, e->gt, e->ring, e->ap, d_all_counts,
-        n_clients, my_client, ts_us, stagger_us, e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
-        (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), n_clients != 1 ? 1u : 0u);
+    if (e->acls_par)   // (views written at every sync: a classed engine is never aclient_lazy)
+        k_approx_sync<true><<<(unsigned)blocks, kBlock, 0, st>>>(
+            e->cfg.n_keys, e->alocal, e->aclient, e->gv, e->gp, e->gt, e->ring, e->ap, d_all_counts,
+            n_clients, my_client, ts_us, stagger_us, e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
+            (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), 1u, e->acls_mask(mask));
+    else
+        k_approx_sync<<<(unsigned)blocks, kBlock, 0, st>>>(
+            e->cfg.n_keys, e->alocal, e->aclient, e->gv, e->gp, e->gt, e->ring, e->ap, d_all_counts,
+            n_clients, my_client, ts_us, stagger_us, e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
+            (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), n_clients != 1 ? 1u : 0u);
     stats_drained(e, e->log_keyseq, e->counters + 1, (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), st);
     HIP_TRY(e, hipGetLastError());
-    e->aclient_lazy = n_clients == 1;
+    e->aclient_lazy = n_clients == 1 && !e->acls_par;   // a classed engine keeps written views
     uint32_t cnt = 0;
     HIP_TRY(e, hipMemcpyAsync(&cnt, e->counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(e, hipStreamSynchronize(st));
@@ -7032,8 +7344,12 @@ tbe_status tbe_approx_idle_device(tbe_engine *e, int64_t ts_us, uint64_t first, 
     hipStream_t caller = (hipStream_t)stream;
     if (tbe_status rc = join_in(e, caller); rc != TBE_OK) return rc;
     const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
-    k_approx_idle<<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient_lazy ? nullptr : e->aclient, e->gv, e->gt,
-                                                    first, count, ts_us, e->ap.decay_rate, d_idle);
+    if (e->acls_par)
+        k_approx_idle<true><<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient, e->gv, e->gt, first, count, ts_us,
+                                                              e->ap.decay_rate, d_idle, e->acls_view());
+    else
+        k_approx_idle<<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient_lazy ? nullptr : e->aclient, e->gv, e->gt,
+                                                        first, count, ts_us, e->ap.decay_rate, d_idle);
     HIP_TRY(e, hipGetLastError());
     return join_out(e, caller);
 }
@@ -7051,8 +7367,12 @@ tbe_status tbe_approx_reset_device(tbe_engine *e, uint64_t first, uint64_t count
     // write every view the last one-client sync left to be derived, then reset
     if (tbe_status rc = materialise_aclient(e, e->stream); rc != TBE_OK) return rc;
     const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
-    k_approx_reset<<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient, e->gv, e->gp, e->gt, first, count, d_flags,
-                                                     e->ap.token_limit);
+    if (e->acls_par)
+        k_approx_reset<true><<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient, e->gv, e->gp, e->gt, first, count,
+                                                               d_flags, e->ap.token_limit, e->acls_view());
+    else
+        k_approx_reset<<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient, e->gv, e->gp, e->gt, first, count,
+                                                         d_flags, e->ap.token_limit);
     if (e->stats()) k_stats_zero<<<blocks, kBlock, 0, e->stream>>>(d_flags, first, count, e->stats_view());
     HIP_TRY(e, hipGetLastError());
     e->queued_exact = false;   // a flagged key's queue, if it had one, is gone: queued_total is a bound
@@ -7252,10 +7572,10 @@ tbe_status tbe_queue_of(tbe_engine *e, uint64_t key, int64_t *request_id, int32_
         cnt = a.hc >> 16;
     }
     uint32_t len = rcap;   // a classed queueing engine: the key wraps at its class's ring length
-    if (e->qcls_par) {
+    if (e->qcls_par || e->acls_par) {
         uint8_t kc = 0;
         HIP_TRY(e, hipMemcpy(&kc, e->cls + key, 1, hipMemcpyDeviceToHost));
-        len = e->qclass_par[kc].o.cap;
+        len = e->qcls_par ? e->qclass_par[kc].o.cap : e->aclass_par[kc].o.cap;
     }
     std::vector<uint64_t> ent(rcap);
     HIP_TRY(e, hipMemcpy(ent.data(), e->ring + key * (uint64_t)rcap, rcap * sizeof(uint64_t),
@@ -7278,12 +7598,14 @@ tbe_status tbe_queue_of(tbe_engine *e, uint64_t key, int64_t *request_id, int32_
 // consumes tokens and A:489 adds its count back a second time; a
 // bounded ring cannot hold entries that no longer count against QueueLimit.
 extern "C++" {   // (inside the C ABI's extern "C" block: a template needs C++ linkage)
-template <typename HW>
+// AV: empty, or the AClsView of an approximate engine with extra classes (that engine's own
+// instantiation; every other engine launches the form without it).
+template <typename HW, typename... AV>
 __global__ __launch_bounds__(256) void k_cancel(
     const uint64_t *__restrict__ ckeys, const int64_t *__restrict__ cids,
     const uint32_t *__restrict__ run_start, uint32_t n_runs, int32_t approx,
     HW *__restrict__ qhdr, ALocal *__restrict__ alocal, uint64_t *__restrict__ ring,
-    uint32_t cap, uint8_t *__restrict__ hit, QClsView QC) {   // (QC.cls == NULL: no queueing classes)
+    uint32_t cap, uint8_t *__restrict__ hit, QClsView QC, AV... AC) {   // (QC.cls == NULL: no queueing classes)
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_runs) return;
     const uint32_t c0 = run_start[r], c1 = run_start[r + 1];
@@ -7304,7 +7626,11 @@ __global__ __launch_bounds__(256) void k_cancel(
     }
     uint64_t *__restrict__ kr = ring + key * (uint64_t)cap;
     // a classed queueing engine: the key's entries wrap at its class's ring length
-    const uint32_t len = QC.cls ? QC.par[QC.cls[key]].o.cap : cap;
+    uint32_t len = QC.cls ? QC.par[QC.cls[key]].o.cap : cap;
+    if constexpr (sizeof...(AV) != 0) {
+        const AClsView &A = (AC, ...);
+        len = A.par[A.cls[key]].o.cap;
+    }
     bool changed = false;
     for (uint32_t c = c0; c < c1; ++c) {
         const int64_t id = cids[c];
@@ -7373,10 +7699,16 @@ tbe_status tbe_queue_cancel(tbe_engine *e, const uint64_t *keys, const int64_t *
     const bool approx = e->cfg.kind == TBE_KIND_APPROXIMATE;
     const uint32_t rcap = approx ? e->ap.cap : e->qp.cap;
     with_qhdr(e, [&](auto *qh) {
-        k_cancel<<<(n_runs + 255) / 256, 256, 0, e->stream>>>(
-            (const uint64_t *)s.p, (const int64_t *)(s.p + off_ids), (const uint32_t *)(s.p + off_runs),
-            n_runs, approx ? 1 : 0, qh, e->alocal, e->ring, rcap, (uint8_t *)(s.p + off_hit),
-            e->qcls_par ? e->qcls_view() : QClsView{nullptr, nullptr});
+        if (e->acls_par)
+            k_cancel<<<(n_runs + 255) / 256, 256, 0, e->stream>>>(
+                (const uint64_t *)s.p, (const int64_t *)(s.p + off_ids), (const uint32_t *)(s.p + off_runs),
+                n_runs, 1, qh, e->alocal, e->ring, rcap, (uint8_t *)(s.p + off_hit), QClsView{nullptr, nullptr},
+                e->acls_view());
+        else
+            k_cancel<<<(n_runs + 255) / 256, 256, 0, e->stream>>>(
+                (const uint64_t *)s.p, (const int64_t *)(s.p + off_ids), (const uint32_t *)(s.p + off_runs),
+                n_runs, approx ? 1 : 0, qh, e->alocal, e->ring, rcap, (uint8_t *)(s.p + off_hit),
+                e->qcls_par ? e->qcls_view() : QClsView{nullptr, nullptr});
     });
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipStreamSynchronize(e->stream));

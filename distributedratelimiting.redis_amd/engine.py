@@ -60,9 +60,10 @@ class TokenBucketEngine:
                  queue_limit: int = 0, queue_order: int = 0, pack: bool = True, hot: bool = True,
                  pipeline: bool = True, narrow: bool = True, zero_wait_slots: int = 0,
                  fold_records: bool = True, digit_stream: bool = True, rerank: bool = False,
-                 classes=None, stats: bool = False):
+                 classes=None, stats: bool = False, approx_classes=None):
         """classes: extra limit classes 1.. as (token_limit, tokens_per_period, period_ticks)
         (tbe_create_classes; class 0 is this engine's own three options).
+        approx_classes: the approximate kind's extra classes (``ApproximateEngine``).
         stats: keep lease statistics (TBE_FLAG_STATS; ``statistics``, ``stats_totals``)."""
         self._lib = _capi.load()
         # stage_timing: True (every stage), "fold" (the fold alone) or False
@@ -91,8 +92,16 @@ class TokenBucketEngine:
                                         max_batch=max_batch, zero_wait_slots=zero_wait_slots)
         h = c_void_p()
         if classes and self.KIND == _capi.TBE_KIND_APPROXIMATE:
-            raise ValueError("limit classes: token-bucket and queueing kinds only")
-        if classes and self.KIND == _capi.TBE_KIND_QUEUEING:
+            raise ValueError("limit classes: token-bucket and queueing kinds only "
+                             "(the approximate kind takes approx_classes=)")
+        if approx_classes and self.KIND != _capi.TBE_KIND_APPROXIMATE:
+            raise ValueError("approx_classes: approximate kind only")
+        if approx_classes:
+            # five options per class: (token_limit, tokens_per_period, period_ticks, queue_limit, order)
+            extra = (_capi.TbeQueueClass * len(approx_classes))(
+                *[_capi.TbeQueueClass(*(int(x) for x in c)) for c in approx_classes])
+            st = self._lib.tbe_create_approx_classes(byref(self.config), extra, len(approx_classes), byref(h))
+        elif classes and self.KIND == _capi.TBE_KIND_QUEUEING:
             # five options per class: (token_limit, tokens_per_period, period_ticks, queue_limit, order)
             extra = (_capi.TbeQueueClass * len(classes))(*[_capi.TbeQueueClass(*(int(x) for x in c)) for c in classes])
             st = self._lib.tbe_create_queue_classes(byref(self.config), extra, len(classes), byref(h))
@@ -105,7 +114,7 @@ class TokenBucketEngine:
             raise TbeError(st, "tbe_create failed: " + self._lib.tbe_last_error(None).decode())
         self._h = h
         self.n_keys = n_keys
-        self.classed = bool(classes)
+        self.classed = bool(classes) or bool(approx_classes)
 
     # ------------------------------------------------------------------ lifetime
     def close(self) -> None:
@@ -389,7 +398,10 @@ class QueueingTokenBucketEngine(TokenBucketEngine):
         self.queue_limit = queue_limit
         # queue_of's buffer size: the longest ring of any class (the engine validated them)
         self._ring_len = max([max(1, queue_limit)] +
-                             [max(1, q[3]) for q in (self.queue_classes() if self.classed else [])])
+                             [max(1, q[3]) for q in (self._five_option_classes() if self.classed else [])])
+
+    def _five_option_classes(self):
+        return self.queue_classes()
 
     def queue_classes(self):
         """Every class's (token_limit, tokens_per_period, period_ticks, queue_limit, order),
@@ -534,11 +546,29 @@ class ApproximateEngine(QueueingTokenBucketEngine):
     KIND = _capi.TBE_KIND_APPROXIMATE
 
     def __init__(self, n_keys: int, token_limit: int, tokens_per_period: int, period_ticks: int,
-                 queue_limit: int, queue_order: int = 0, zero_wait_slots: int = 4, **kw):
-        """zero_wait_slots: queue entries per key for zero-permit waits (tbe.h)."""
+                 queue_limit: int, queue_order: int = 0, zero_wait_slots: int = 4, approx_classes=None, **kw):
+        """zero_wait_slots: queue entries per key for zero-permit waits (tbe.h).
+        approx_classes: extra limit classes 1.. as (token_limit, tokens_per_period,
+        period_ticks, queue_limit, order) (tbe_create_approx_classes; class 0 is this
+        engine's own five options, zero_wait_slots is shared).  Keys move between classes
+        with ``set_class``; ``collect``, ``sync`` and ``refresh`` take ``classes=`` to sync
+        each class at its own ReplenishmentPeriod (A:443)."""
         super().__init__(n_keys, token_limit, tokens_per_period, period_ticks, queue_limit,
-                         queue_order, zero_wait_slots=zero_wait_slots, **kw)
+                         queue_order, zero_wait_slots=zero_wait_slots, approx_classes=approx_classes, **kw)
         self.zero_wait_slots = zero_wait_slots
+
+    def approx_classes(self):
+        """Every class's (token_limit, tokens_per_period, period_ticks, queue_limit, order),
+        class 0 first (tbe_approx_classes)."""
+        n = c_uint32()
+        self._check(self._lib.tbe_approx_classes(self.handle, None, 0, byref(n)))
+        out = (_capi.TbeQueueClass * n.value)()
+        self._check(self._lib.tbe_approx_classes(self.handle, out, n.value, byref(n)))
+        return [(c.token_limit, c.tokens_per_period, c.replenishment_period_ticks, c.queue_limit, c.queue_order)
+                for c in out]
+
+    def _five_option_classes(self):   # (the base class sizes queue_of's buffer from the longest ring)
+        return self.approx_classes()
 
     def acquire_batch(self, keys, permits, wait: bool = True, id_base: int = 0, status=None, available=None,
                       retry_after=False):
@@ -587,17 +617,35 @@ class ApproximateEngine(QueueingTokenBucketEngine):
             self.handle, d_keys.data_ptr(), d_permits.data_ptr(), n, 1 if wait else 0, id_base,
             d_status.data_ptr(), d_available.data_ptr(), stream))
 
-    def collect(self, d_counts) -> None:
-        """Local scores of every key into the int32 device tensor `d_counts` [n_keys]."""
+    def collect(self, d_counts, classes=None) -> None:
+        """Local scores of every key into the int32 device tensor `d_counts` [n_keys].
+        classes: an iterable of class numbers; keys of other classes give 0 and keep their
+        count (tbe_approx_collect_classes)."""
+        if classes is not None:
+            self._check(self._lib.tbe_approx_collect_classes(self.handle, d_counts.data_ptr(),
+                                                             _capi.class_mask(classes), None))
+            return
         self._check(self._lib.tbe_approx_collect(self.handle, d_counts.data_ptr(), None))
 
     def sync(self, d_all_counts, n_clients: int, my_client: int, ts_us: int, stagger_us: int,
-             stream: Optional[int] = None):
+             stream: Optional[int] = None, classes=None):
         """Replay the epoch's sync calls; returns the drain log (keys, request ids, available).
         stream=None: d_all_counts must be complete at the call (tbe_approx_sync); a stream
         handle: the replay is ordered after the work enqueued on that stream so far
-        (tbe_approx_sync_stream), e.g. the collective or copy that produced the counts."""
+        (tbe_approx_sync_stream), e.g. the collective or copy that produced the counts.
+        classes: an iterable of class numbers; keys of other classes are left untouched
+        (tbe_approx_sync_classes(_stream))."""
         n = ctypes.c_uint64()
+        if classes is not None:
+            mask = _capi.class_mask(classes)
+            if stream is None:
+                self._check(self._lib.tbe_approx_sync_classes(self.handle, d_all_counts.data_ptr(), n_clients,
+                                                              my_client, ts_us, stagger_us, mask, byref(n)))
+            else:
+                self._check(self._lib.tbe_approx_sync_classes_stream(self.handle, d_all_counts.data_ptr(), n_clients,
+                                                                     my_client, ts_us, stagger_us, mask, stream,
+                                                                     byref(n)))
+            return self._drain_log(n.value)
         if stream is None:
             self._check(self._lib.tbe_approx_sync(self.handle, d_all_counts.data_ptr(), n_clients, my_client,
                                                   ts_us, stagger_us, byref(n)))
@@ -606,9 +654,13 @@ class ApproximateEngine(QueueingTokenBucketEngine):
                                                          my_client, ts_us, stagger_us, stream, byref(n)))
         return self._drain_log(n.value)
 
-    def refresh(self, ts_us: int):
-        """RefreshAsync as the only client of the global tier (A:412-508)."""
+    def refresh(self, ts_us: int, classes=None):
+        """RefreshAsync as the only client of the global tier (A:412-508); classes: an
+        iterable of class numbers to refresh alone (tbe_approx_refresh_classes)."""
         n = ctypes.c_uint64()
+        if classes is not None:
+            self._check(self._lib.tbe_approx_refresh_classes(self.handle, ts_us, _capi.class_mask(classes), byref(n)))
+            return self._drain_log(n.value)
         self._check(self._lib.tbe_approx_refresh(self.handle, ts_us, byref(n)))
         return self._drain_log(n.value)
 

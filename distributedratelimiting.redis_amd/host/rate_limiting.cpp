@@ -147,8 +147,9 @@ namespace detail {
 class LimiterCore {
 public:
     LimiterCore(tbe_kind kind, const RedisQueueingTokenBucketRateLimiterOptions &o, bool partitioned,
-                const char *type_name)
-        : kind_(kind), opt_(o), partitioned_(partitioned), type_name_(type_name) {
+                const char *type_name, const std::vector<ApproximateTokenBucketClass> *aclasses = nullptr,
+                std::function<void(const RefreshTrace &)> on_refresh = {})
+        : kind_(kind), opt_(o), partitioned_(partitioned), type_name_(type_name), on_refresh_(std::move(on_refresh)) {
         // Constructor checks in reference order (TB:24-42; A:44-72).
         if (o.TokenLimit <= 0 || o.TokensPerPeriod <= 0)
             throw ArgumentException("Both TokenLimit and TokensPerPeriod must be set to values greater than 0.",
@@ -178,6 +179,31 @@ public:
             class_limit_.push_back(k.TokenLimit);
         }
         if (extra.size() > 255) throw ArgumentException("Classes: at most 255 extra classes.", "options");
+        // approximate limit classes: five options each, class 0 the options' own
+        std::vector<tbe_queue_class> aextra;
+        class_period_ticks_.push_back(o.ReplenishmentPeriod.ticks);
+        if (aclasses && !aclasses->empty()) {
+            if (!(kind == TBE_KIND_APPROXIMATE && partitioned))
+                throw ArgumentException("ApproximateClasses: only PartitionedRedisApproximateTokenBucketRateLimiter "
+                                        "takes approximate limit classes.", "options");
+            for (const ApproximateTokenBucketClass &k : *aclasses) {
+                if (k.TokenLimit <= 0 || k.TokensPerPeriod <= 0)
+                    throw ArgumentException("ApproximateClasses: both TokenLimit and TokensPerPeriod must be "
+                                            "greater than 0.", "options");
+                if (k.QueueLimit < 0)
+                    throw ArgumentException("ApproximateClasses: QueueLimit must be greater than or equal to 0.",
+                                            "options");
+                if (k.ReplenishmentPeriod.ticks < 0)
+                    throw ArgumentException("ApproximateClasses: ReplenishmentPeriod must be greater than or equal "
+                                            "to TimeSpan.Zero.", "options");
+                aextra.push_back(tbe_queue_class{k.TokenLimit, k.TokensPerPeriod, k.ReplenishmentPeriod.ticks,
+                                                 k.QueueLimit, (int32_t)k.QueueProcessingOrder});
+                class_limit_.push_back(k.TokenLimit);
+                class_period_ticks_.push_back(k.ReplenishmentPeriod.ticks);
+            }
+            if (aextra.size() > 255)
+                throw ArgumentException("ApproximateClasses: at most 255 extra classes.", "options");
+        }
         clock_ = o.TimeSource ? o.TimeSource : Clock(SystemClockMicros);
         tbe_config c{};
         c.struct_size = sizeof c;
@@ -192,11 +218,13 @@ public:
         c.max_batch = o.MaxBatch;
         c.zero_wait_slots = kind == TBE_KIND_APPROXIMATE ? o.ZeroWaitSlots : 0;
         if (o.TrackStatistics) c.flags |= TBE_FLAG_STATS;
-        const tbe_status st = tbe_create_classes(&c, extra.data(), (uint32_t)extra.size(), &eng_);
+        const tbe_status st = aextra.empty()
+                                  ? tbe_create_classes(&c, extra.data(), (uint32_t)extra.size(), &eng_)
+                                  : tbe_create_approx_classes(&c, aextra.data(), (uint32_t)aextra.size(), &eng_);
         if (st == TBE_EINVAL) throw ArgumentException(std::string("invalid limiter options: ") + tbe_last_error(nullptr), "options");
         if (st != TBE_OK) throw RateLimiterEngineException(st, std::string("tbe_create failed: ") + tbe_last_error(nullptr));
         // TB:234 per class: EXPIRE ceil(min(max(capacity / fill_rate, 1), 31536000)) seconds
-        for (size_t i = 0; i < class_limit_.size(); ++i) {
+        for (size_t i = 0; i < class_limit_.size() && aextra.empty(); ++i) {
             const double rate = i == 0 ? o.FillRatePerSecond()
                                        : tbe_fill_rate(extra[i - 1].tokens_per_period,
                                                        extra[i - 1].replenishment_period_ticks);
@@ -207,8 +235,30 @@ public:
         }
         inbox_->core = this;
         submitter_ = std::thread([this] { Loop(); });
-        if (kind != TBE_KIND_TOKEN_BUCKET && o.AutoReplenishment && o.ReplenishmentPeriod.ticks > 0)
-            timer_ = std::thread([this] { TimerLoop(); });
+        // One timer per distinct ReplenishmentPeriod (the reference's Timer per limiter, A:77): a
+        // limiter without approximate classes has the one timer it always had, which refreshes
+        // everything; with classes each timer refreshes the classes of its period alone.
+        if (kind != TBE_KIND_TOKEN_BUCKET) {
+            for (size_t cls = 0; cls < class_period_ticks_.size(); ++cls) {
+                PeriodTimer *t = nullptr;
+                for (auto &u : timers_)
+                    if (u->ticks == class_period_ticks_[cls]) t = u.get();
+                if (!t) {
+                    timers_.push_back(std::make_unique<PeriodTimer>());
+                    t = timers_.back().get();
+                    t->ticks = class_period_ticks_[cls];
+                    t->masked = !aextra.empty();
+                }
+                t->mask[cls >> 6] |= 1ull << (cls & 63);
+                t->classes.push_back((int)cls);
+            }
+            if (o.AutoReplenishment)
+                for (auto &u : timers_)
+                    if (u->ticks > 0) {
+                        PeriodTimer *t = u.get();
+                        t->thread = std::thread([this, t] { TimerLoop(t); });
+                    }
+        }
     }
 
     ~LimiterCore() { Dispose(); }
@@ -252,6 +302,26 @@ public:
         return c;
     }
     int ClassLimit(int c) const { return class_limit_[(size_t)c]; }
+    // TokenLimit of a resourceID's class: of the class its key is in, or of ClassOf for a name
+    // that holds no key (no key is assigned).
+    int LimitOfResource(const std::string &resource) {
+        if (class_limit_.size() == 1) return class_limit_[0];
+        {
+            std::lock_guard<std::mutex> g(dir_mu_);
+            auto it = dir_.find(opt_.InstanceName + resource);
+            if (it != dir_.end()) return class_limit_[it->second < key_cls_.size() ? key_cls_[it->second] : 0];
+        }
+        return ClassLimit(ClassOfResource(resource));
+    }
+    std::vector<std::pair<TimeSpan, std::vector<int>>> Timers() const {
+        std::vector<std::pair<TimeSpan, std::vector<int>>> out;
+        for (auto &u : timers_) out.emplace_back(TimeSpan{u->ticks}, u->classes);
+        return out;
+    }
+    void TickTimer(size_t i) {  // submitter thread
+        if (i >= timers_.size()) throw ArgumentOutOfRangeException("no such replenishment timer", "index");
+        RefreshNow(timers_[i]->masked ? timers_[i]->mask : nullptr);
+    }
 
     bool TryKeyOf(const std::string &resource, uint64_t &key) {
         const std::string bucket = opt_.InstanceName + resource;
@@ -296,6 +366,13 @@ public:
                 const uint8_t c8 = (uint8_t)cls;
                 q_.emplace_back(Cmd{[this, key, c8] {
                     // (an engine error here also fails the batch that follows)
+                    // approximate kind: after the reset of the freshly taken key
+                    if (kind_ == TBE_KIND_APPROXIMATE) {
+                        try {
+                            ResetFreshKeys();
+                        } catch (...) {
+                        }
+                    }
                     (void)tbe_set_class(eng_, &key, &c8, 1);
                 }});
             }
@@ -501,14 +578,22 @@ public:
     }
 
     // One replenish tick (Q:237-271) / RefreshAsync (A:412-508), on the submitter thread.
-    void RefreshNow() {
+    // mask != nullptr (approximate limit classes): the classes of one timer's period alone.
+    void RefreshNow(const uint64_t *mask = nullptr) {
         if (disposed_.load()) return;  // A:414-417
         const int64_t now = clock_();
         uint64_t n = 0;
         if (kind_ == TBE_KIND_QUEUEING)
             Check(tbe_refresh(eng_, now, &n));
+        else if (mask)
+            Check(tbe_approx_refresh_classes(eng_, now, mask, &n));
         else
             Check(tbe_approx_refresh(eng_, now, &n));
+        if (on_refresh_ && kind_ == TBE_KIND_APPROXIMATE) {
+            RefreshTrace tr{now, {~0ull, ~0ull, ~0ull, ~0ull}};
+            if (mask) std::copy(mask, mask + 4, tr.ClassMask);
+            on_refresh_(tr);
+        }
         if (n) {
             std::vector<uint64_t> keys(n);
             std::vector<int64_t> ids(n);
@@ -548,7 +633,8 @@ public:
             timer_stop_ = true;
         }
         timer_cv_.notify_all();
-        if (timer_.joinable()) timer_.join();
+        for (auto &u : timers_)
+            if (u->thread.joinable()) u->thread.join();
         {
             std::lock_guard<std::mutex> g(mu_);
             q_.emplace_back(Cmd{[this] {
@@ -777,21 +863,30 @@ private:
         }
     }
 
-    void TimerLoop() {  // the reference's Timer(Refresh, ..., period, period) (A:77)
-        const auto period = std::chrono::nanoseconds(opt_.ReplenishmentPeriod.ticks * 100);
+    struct PeriodTimer {
+        int64_t ticks = 0;
+        uint64_t mask[4] = {0, 0, 0, 0};
+        bool masked = false;               // false: the unmasked refresh (no approximate classes)
+        std::vector<int> classes;
+        std::atomic<bool> pending{false};
+        std::thread thread;
+    };
+
+    void TimerLoop(PeriodTimer *t) {  // the reference's Timer(Refresh, ..., period, period) (A:77)
+        const auto period = std::chrono::nanoseconds(t->ticks * 100);
         std::unique_lock<std::mutex> lk(timer_mu_);
         for (;;) {
             if (timer_cv_.wait_for(lk, period, [&] { return timer_stop_; })) return;
             // Start a refresh only if the previous one has completed (A:402-409).
-            if (refresh_pending_.exchange(true)) continue;
+            if (t->pending.exchange(true)) continue;
             std::lock_guard<std::mutex> g(mu_);
             if (stop_) return;
-            q_.emplace_back(Cmd{[this] {
+            q_.emplace_back(Cmd{[this, t] {
                 try {
-                    RefreshNow();
+                    RefreshNow(t->masked ? t->mask : nullptr);
                 } catch (...) {  // the reference logs and carries on (A:445-449)
                 }
-                refresh_pending_.store(false);
+                t->pending.store(false);
             }});
             cv_.notify_one();
         }
@@ -816,8 +911,9 @@ private:
     std::mutex timer_mu_;
     std::condition_variable timer_cv_;
     bool timer_stop_ = false;
-    std::atomic<bool> refresh_pending_{false};
-    std::thread timer_;
+    std::vector<std::unique_ptr<PeriodTimer>> timers_;   // one per distinct ReplenishmentPeriod
+    std::function<void(const RefreshTrace &)> on_refresh_;
+    std::vector<int64_t> class_period_ticks_;            // ReplenishmentPeriod of every class, class 0 first
 
     std::mutex dir_mu_;
     std::unordered_map<std::string, uint64_t> dir_;
@@ -957,7 +1053,8 @@ void RedisQueueingTokenBucketRateLimiter::DisposeCore() { core_->Dispose(); }
 // ------------------------------------------------------------------ approximate
 RedisApproximateTokenBucketRateLimiter::RedisApproximateTokenBucketRateLimiter(
     const RedisApproximateTokenBucketRateLimiterOptions &o)
-    : core_(std::make_unique<LimiterCore>(TBE_KIND_APPROXIMATE, o, false, "RedisApproximateTokenBucketRateLimiter")) {}
+    : core_(std::make_unique<LimiterCore>(TBE_KIND_APPROXIMATE, o, false, "RedisApproximateTokenBucketRateLimiter",
+                                          &o.ApproximateClasses, o.OnRefresh)) {}
 RedisApproximateTokenBucketRateLimiter::~RedisApproximateTokenBucketRateLimiter() = default;
 std::optional<TimeSpan> RedisApproximateTokenBucketRateLimiter::IdleDuration() const { return core_->IdleDuration(); }
 int RedisApproximateTokenBucketRateLimiter::GetAvailablePermits() {
@@ -1006,14 +1103,16 @@ void RedisApproximateTokenBucketRateLimiter::DisposeCore() { core_->Dispose(); }
 PartitionedRedisApproximateTokenBucketRateLimiter::PartitionedRedisApproximateTokenBucketRateLimiter(
     const RedisApproximateTokenBucketRateLimiterOptions &o)
     : core_(std::make_unique<LimiterCore>(TBE_KIND_APPROXIMATE, o, true,
-                                          "PartitionedRedisApproximateTokenBucketRateLimiter")) {}
+                                          "PartitionedRedisApproximateTokenBucketRateLimiter",
+                                          &o.ApproximateClasses, o.OnRefresh)) {}
 PartitionedRedisApproximateTokenBucketRateLimiter::~PartitionedRedisApproximateTokenBucketRateLimiter() = default;
 int PartitionedRedisApproximateTokenBucketRateLimiter::GetAvailablePermits(const std::string &id) {
     core_->ThrowIfDisposed();
     // on the submitter thread, where reclaims run: the name cannot lose its key in between
     return core_->Run([this, &id] {
         uint64_t k;
-        return core_->KnownKey(id, k) ? core_->QueryApprox(k).available : core_->options().TokenLimit;
+        return core_->KnownKey(id, k) ? core_->QueryApprox(k).available
+                                      : core_->ClassLimit(core_->ClassOfResource(id));
     });
 }
 std::optional<RateLimiterStatistics> PartitionedRedisApproximateTokenBucketRateLimiter::GetStatistics(
@@ -1022,7 +1121,8 @@ std::optional<RateLimiterStatistics> PartitionedRedisApproximateTokenBucketRateL
     core_->ThrowIfDisposed();
     return core_->Run([this, &id] {
         uint64_t k;
-        if (!core_->KnownKey(id, k)) return RateLimiterStatistics{core_->options().TokenLimit, 0, 0, 0};
+        if (!core_->KnownKey(id, k))
+            return RateLimiterStatistics{core_->ClassLimit(core_->ClassOfResource(id)), 0, 0, 0};
         return core_->QueryStatistics(k, core_->QueryApprox(k).available);
     });
 }
@@ -1032,18 +1132,26 @@ bool PartitionedRedisApproximateTokenBucketRateLimiter::TryReplenish() {
     core_->Run([this] { core_->RefreshNow(); });
     return true;
 }
+std::vector<std::pair<TimeSpan, std::vector<int>>>
+PartitionedRedisApproximateTokenBucketRateLimiter::ReplenishmentTimers() const {
+    return core_->Timers();
+}
+void PartitionedRedisApproximateTokenBucketRateLimiter::TickTimer(size_t index) {
+    core_->ThrowIfDisposed();
+    core_->Run([this, index] { core_->TickTimer(index); });
+}
 uint64_t PartitionedRedisApproximateTokenBucketRateLimiter::ReclaimIdle() {
     core_->ThrowIfDisposed();
     return core_->Run([this] { return core_->Reclaim(); });
 }
 RateLimitLease PartitionedRedisApproximateTokenBucketRateLimiter::AttemptAcquireCore(const std::string &id, int p) {
-    check_limit(p, core_->options().TokenLimit);
+    check_limit(p, core_->LimitOfResource(id));
     core_->ThrowIfDisposed();
     return core_->SubmitResource(id, p, kApproxAttempt).get();
 }
 std::future<RateLimitLease> PartitionedRedisApproximateTokenBucketRateLimiter::AcquireAsyncCore(
     const std::string &id, int p, const CancellationToken &ct) {
-    check_limit(p, core_->options().TokenLimit);
+    check_limit(p, core_->LimitOfResource(id));
     core_->ThrowIfDisposed();  // A:124
     return core_->SubmitResource(id, p, kApproxWait, ct);
 }

@@ -215,8 +215,36 @@ struct RedisQueueingTokenBucketRateLimiterOptions : RedisTokenBucketRateLimiterO
     int ZeroWaitSlots = 4;
 };
 
+// One limit class of a partitioned approximate limiter: the five options the reference
+// interpolates into a limiter's sync script and keeps in its object (A:224, A:241-270, A:37,
+// A:141-158), so that differently configured limiters share one store.
+// ZeroWaitSlots stays one option of the limiter.
+struct ApproximateTokenBucketClass {
+    int TokenLimit = 0;
+    int TokensPerPeriod = 0;
+    TimeSpan ReplenishmentPeriod = TimeSpan::FromSeconds(1);
+    int QueueLimit = 0;
+    ::tbe::rate_limiting::QueueProcessingOrder QueueProcessingOrder =
+        ::tbe::rate_limiting::QueueProcessingOrder::OldestFirst;
+};
+
+// One refresh as the engine was asked for it (diagnostics, tests): its time and the classes it
+// covered (bit c of ClassMask[c >> 6]: class c; all ones: every class, the unmasked call).
+struct RefreshTrace {
+    int64_t ts_us;
+    uint64_t ClassMask[4];
+};
+
 // RedisApproximateTokenBucketRateLimiterOptions (ApproximateTokenBucket/...Options.cs).
-struct RedisApproximateTokenBucketRateLimiterOptions : RedisQueueingTokenBucketRateLimiterOptions {};
+struct RedisApproximateTokenBucketRateLimiterOptions : RedisQueueingTokenBucketRateLimiterOptions {
+    // PartitionedRedisApproximateTokenBucketRateLimiter only (the non-partitioned limiter throws
+    // ArgumentException when it is non-empty): the extra limit classes 1, 2, ...; class 0 is the
+    // five options above.  ClassOf (inherited) is the partitioner, with the rules it has on the
+    // partitioned token-bucket limiter.  (The inherited three-field Classes stays the token
+    // bucket's and is refused here.)
+    std::vector<ApproximateTokenBucketClass> ApproximateClasses;
+    std::function<void(const RefreshTrace &)> OnRefresh;  // diagnostics (tests)
+};
 
 // ------------------------------------------------------------------ base classes
 class RateLimiter {  // System.Threading.RateLimiting.RateLimiter
@@ -363,11 +391,19 @@ public:
     explicit PartitionedRedisApproximateTokenBucketRateLimiter(
         const RedisApproximateTokenBucketRateLimiterOptions &options);
     ~PartitionedRedisApproximateTokenBucketRateLimiter() override;
-    // A:81 for a name that holds a key; TokenLimit for one that does not (what its limiter
-    // would report once constructed), without assigning a key.
+    // A:81 for a name that holds a key; for one that does not, the TokenLimit of ClassOf(name)
+    // (what its limiter would report once constructed), without assigning a key.
     int GetAvailablePermits(const std::string &resourceID) override;
     std::optional<RateLimiterStatistics> GetStatistics(const std::string &resourceID) override;
-    bool TryReplenish();  // one RefreshAsync of every name now; false when AutoReplenishment is on
+    // one RefreshAsync of every name of every class now; false when AutoReplenishment is on
+    bool TryReplenish();
+    // AutoReplenishment runs one timer per distinct ReplenishmentPeriod among the classes; each
+    // refreshes only the names of the classes of its period (tbe_approx_refresh_classes), so
+    // that the instance estimate of A:443 divides a class's period by its own sync interval.
+    // ReplenishmentTimers lists them (period, classes), in the order of each period's first class.
+    std::vector<std::pair<TimeSpan, std::vector<int>>> ReplenishmentTimers() const;
+    // What timer `index` does at its tick, now (for a host that drives time itself, and tests).
+    void TickTimer(size_t index);
     uint64_t ReclaimIdle();  // frees the keys of idle names; returns the number freed
 protected:
     RateLimitLease AttemptAcquireCore(const std::string &resourceID, int permitCount) override;   // A:84-113

@@ -200,6 +200,41 @@ tbe_status tbe_create_queue_classes(const tbe_config *config, const tbe_queue_cl
 tbe_status tbe_queue_classes(const tbe_engine *engine, tbe_queue_class *out, uint32_t capacity,
                              uint32_t *n_classes);
 
+/* ---- Approximate limit classes: one approximate engine, up to 256
+ * differently configured ApproximateTokenBucket limiters over one global tier.  A class is
+ * the five options of tbe_queue_class; zero_wait_slots stays the config's, for every class.
+ * The reference interpolates a limiter's options into its sync script and its queue code
+ * (A:224, A:241-270, A:37, A:141-158), so any number of limiters share one Redis.  Per class
+ * the engine derives what tbe_create derives for the approximate kind: decay_rate =
+ * tbe_fill_rate (A:224, A:258), the period in seconds of the instance estimate (A:443) and
+ * the ring length max(1, QueueLimit) + zero_wait_slots (<= 65535).  Every request is decided
+ * as on a plain engine with the options of its key's class: REJECTED when permits >
+ * TokenLimit (A:87-90, A:119-122), the lease test with the class's order (A:191-209),
+ * admission and NewestFirst eviction with its QueueLimit (A:141-158); RetryAfter (A:390-395)
+ * takes the class's TokenLimit and fill rate; a sync decays, caps, estimates and drains each
+ * key with its class's values (A:258, A:37, A:443, A:467-501).  The 86400 s EXPIRE (A:268)
+ * does not depend on the class.
+ * TBE_EINVAL, before the device is touched: kind != TBE_KIND_APPROXIMATE, n_extra > 255,
+ * extra == NULL with n_extra > 0, a class that fails a check tbe_create makes on the
+ * config's options (the ring-length bound included).  n_extra == 0 is tbe_create.
+ * Layout: as with TBE_FLAG_NO_PACK (wide records; tbe_layout bit 0 clear); two-byte replies
+ * (bit 4) only when the largest TokenLimit of any class is <= 16382.  The ring of key k is
+ * ring[k*C .. k*C+C), C the largest ring length of any class; a key uses the first slots of
+ * its own class's length and wraps there.  A classed engine writes the client view
+ * {est, global} of every synced key at every sync (16 more bytes per key than the derived
+ * view of a plain engine's one-client sync).
+ * tbe_approx_idle(_device) decays with the key's class rate, tbe_approx_reset(_device) gives
+ * cap = TokenLimit of the key's class and leaves the class byte; tbe_approx_query,
+ * tbe_queue_cancel, tbe_queue_of, tbe_evicted, TBE_FLAG_STATS counting and the tier's
+ * exports and imports work as on a plain engine. */
+tbe_status tbe_create_approx_classes(const tbe_config *config, const tbe_queue_class *extra,
+                                     uint32_t n_extra, tbe_engine **out_engine);
+
+/* The classes of an approximate engine with all five options, class 0 first (as tbe_classes,
+ * which reports the first three); another kind of engine: TBE_EINVAL. */
+tbe_status tbe_approx_classes(const tbe_engine *engine, tbe_queue_class *out, uint32_t capacity,
+                              uint32_t *n_classes);
+
 /* cls[d_ids[i]] = d_cls[i].  The row {v, t_us} stays: the key's next evaluation clamps with
  * the new TokenLimit and refills at the new rate, as when another limiter's script runs on
  * the same Redis hash; the lapse test uses the new class from here on (the reference keeps
@@ -208,10 +243,16 @@ tbe_status tbe_queue_classes(const tbe_engine *engine, tbe_queue_class *out, uin
  * every batch after it, `stream` as in tbe_expired_device; unique ids; every pair is
  * validated before any is written, and an id >= n_keys or a class >= the number of classes
  * voids the whole call, reported by tbe_synchronize.  Without extra classes only class 0 is
- * valid.  Token-bucket and queueing kinds (approximate kind: TBE_EINVAL).
+ * valid.
  * Queueing engine with extra classes: an id whose queue is not empty voids the whole call in
  * the same way (a shorter ring or another order under live entries has no counterpart in the
- * reference); the queue of a written id stays empty. */
+ * reference); the queue of a written id stays empty.
+ * Approximate engine with extra classes: an id with anything queued (zero-permit
+ * registrations included) voids the whole call likewise.  A written id gets the client side
+ * of a limiter freshly constructed with the new class's options over the existing Redis key
+ * (A:26-28): cap = TokenLimit, local count 0, empty queue, est 1, global 0.  The tier row
+ * {v, p, t} stays; a local count not yet synced is dropped, as the reference drops it with
+ * the limiter object. */
 tbe_status tbe_set_class_device(tbe_engine *engine, const uint64_t *d_ids, const uint8_t *d_cls, uint64_t n,
                                 void *stream);
 /* The same from host buffers; synchronous, an invalid pair (or, as above, a non-empty
@@ -392,7 +433,10 @@ tbe_status tbe_wait_batch_device(tbe_engine *engine, const uint64_t *d_keys, con
 /* Upper bound on the grants one tbe_refresh_device can log: min(entries possibly queued,
  * n_keys * min(max(1, QueueLimit), TokenLimit)) -- a queued entry holds >= 1 permit and
  * a tick grants at most TokenLimit tokens per key.  With queueing classes the per-key factor
- * is the largest min(max(1, QueueLimit), TokenLimit) of any class. */
+ * is the largest min(max(1, QueueLimit), TokenLimit) of any class.
+ * Approximate kind (the grants one sync can log): per key min(ring length, TokenLimit +
+ * zero_wait_slots), the largest of any class -- zero-permit registrations complete beside
+ * the TokenLimit permits a sync can grant (A:474). */
 tbe_status tbe_refresh_bound(tbe_engine *engine, uint64_t *bound);
 
 /* Device-pointer tbe_refresh (Q:237-271): enqueues one replenish tick at ts_us.  Grants
@@ -532,6 +576,27 @@ tbe_status tbe_approx_sync_stream(tbe_engine *engine, const int32_t *d_all_count
  * call's LocalCount; no host round trip between the two).  Completed queued requests via
  * tbe_refresh_log. */
 tbe_status tbe_approx_refresh(tbe_engine *engine, int64_t ts_us, uint64_t *n_granted);
+
+/* The three calls above for a set of classes: mask is host memory, 256 bits, bit c (of word
+ * c >> 6) = class c.  For a key whose class bit is clear nothing is read-modify-written: its
+ * local count, cap, queue, client view and tier row {v, p, t} keep their bits, nothing of it
+ * is drained or logged, and tbe_approx_collect_classes writes d_counts[k] = 0 and leaves its
+ * local count.  For a key whose bit is set the call is the unmasked one.  The estimate of
+ * A:443 is ReplenishmentPeriod over the measured interval between syncs (field p, A:262), so
+ * classes of different periods are only estimated correctly when each is synced at its own
+ * period: that is what the mask is for.  The unmasked calls mean every class.  On an engine
+ * without extra classes bit 0 set is the unmasked call; bit 0 clear does and logs nothing.
+ * A bit at or above the number of classes, or mask == NULL: TBE_EINVAL before the device is
+ * touched. */
+tbe_status tbe_approx_collect_classes(tbe_engine *engine, int32_t *d_counts, const uint64_t *mask, void *stream);
+tbe_status tbe_approx_sync_classes(tbe_engine *engine, const int32_t *d_all_counts, uint32_t n_clients,
+                                   uint32_t my_client, int64_t ts_us, int64_t stagger_us, const uint64_t *mask,
+                                   uint64_t *n_granted);
+tbe_status tbe_approx_sync_classes_stream(tbe_engine *engine, const int32_t *d_all_counts, uint32_t n_clients,
+                                          uint32_t my_client, int64_t ts_us, int64_t stagger_us,
+                                          const uint64_t *mask, void *stream, uint64_t *n_granted);
+tbe_status tbe_approx_refresh_classes(tbe_engine *engine, int64_t ts_us, const uint64_t *mask,
+                                      uint64_t *n_granted);
 
 /* Local-tier state of one key: _localThrottleScore, _globalThrottleScore,
  * _instanceCountEstimate, AvailableTokens (GetAvailablePermits, A:81), queued requests. */
