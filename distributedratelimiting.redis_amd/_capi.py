@@ -49,7 +49,8 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_stats_batch", "tbe_stats_totals", "tbe_stats_export", "tbe_stats_import",
             "tbe_create_queue_classes", "tbe_queue_classes", "tbe_create_approx_classes", "tbe_approx_classes",
             "tbe_approx_collect_classes", "tbe_approx_sync_classes", "tbe_approx_sync_classes_stream",
-            "tbe_approx_refresh_classes")
+            "tbe_approx_refresh_classes",
+            "tbe_refresh_classes", "tbe_refresh_classes_device", "tbe_wait_batch_tick_classes_device")
 # k_stats_batch's shape (csrc/tbe_stats.hpp): requests per workgroup trip and slots of its
 # LDS table; the tests size their cases by them
 STATS_TILE, STATS_SLOTS = 4096, 2048
@@ -96,7 +97,7 @@ class TbeQueueClass(Structure):
 
 
 def class_mask(classes):
-    """The 256-bit mask of the tbe_approx_*_classes calls (bit c = class c) from an iterable of
+    """The 256-bit mask of the *_classes calls of both queueing kinds (bit c = class c) from an iterable of
     class numbers."""
     m = (c_uint64 * 4)()
     for c in classes:
@@ -240,6 +241,15 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_wait_batch_tick_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_int64,
                                                c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                                c_void_p, c_uint64, c_void_p, c_void_p]
+    lib.tbe_refresh_classes.restype = c_int32
+    lib.tbe_refresh_classes.argtypes = [c_void_p, c_int64, POINTER(c_uint64), POINTER(c_uint64)]
+    lib.tbe_refresh_classes_device.restype = c_int32
+    lib.tbe_refresh_classes_device.argtypes = [c_void_p, c_int64, POINTER(c_uint64), c_void_p, c_void_p, c_void_p,
+                                               c_uint64, c_void_p, c_void_p]
+    lib.tbe_wait_batch_tick_classes_device.restype = c_int32
+    lib.tbe_wait_batch_tick_classes_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_int64,
+                                                       c_int32, c_void_p, c_void_p, c_int64, POINTER(c_uint64),
+                                                       c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]
     lib.tbe_approx_acquire_batch_device.restype = c_int32
     lib.tbe_approx_acquire_batch_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_int32,
                                                     c_int64, c_void_p, c_void_p, c_void_p]

@@ -2904,6 +2904,17 @@ struct QClsView {
     const QClsPar *par;    // kMaxClasses entries
 };
 struct NoQCls {};          // what a CLS = false kernel takes in the view's place
+// The classes a masked replenish tick drains (tbe_refresh_classes and its kin; bit c of
+// w[c >> 6]: class c).  k_drain and k_fold_q take it as a template pack after the view, so the
+// forms every unmasked call launches are the ones without it.
+struct QClsBits {
+    uint64_t w[4];
+    __device__ __forceinline__ bool has(uint32_t c) const {   // (selects: no indexed copy of the argument)
+        const uint64_t x = c < 64 ? w[0] : c < 128 ? w[1] : c < 192 ? w[2] : w[3];
+        return (x >> (c & 63)) & 1u;
+    }
+};
+static inline QClsBits qcls_bits(const uint64_t *m) { return QClsBits{{m[0], m[1], m[2], m[3]}}; }
 __device__ __forceinline__ uint64_t qh_pack(uint32_t head, uint32_t cnt, int64_t qsum) {
     return (uint64_t)(head & 0xFFFFu) | ((uint64_t)(cnt & 0xFFFFu) << 16) | ((uint64_t)qsum << 32);
 }
@@ -3138,7 +3149,10 @@ constexpr uint32_t kQTailRun = 32;       // longest run a walking thread sorts a
 // TokenLimit, QueueLimit, order, ring length} of its row's class: an LDS copy of the first
 // kClsLds class records, global loads for the others.  Q.wait, Q.ai_base and Q.id_base stay
 // the batch's, and Q.cap the ring stride.
-template <bool PACKED, typename HW, bool CLS = false>
+// MK: empty, or the QClsBits of a masked fused tick (CLS only): the batch's requests are decided
+// for every class, and the tick's counting pass leaves out the rows whose class bit is clear, so
+// they never enter `need`, the log or the writing pass.
+template <bool PACKED, typename HW, bool CLS = false, typename... MK>
 __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
     const uint32_t *__restrict__ skeys, const int32_t *__restrict__ sperm,
     const int64_t *__restrict__ sts, const uint32_t *__restrict__ sidx,
@@ -3147,8 +3161,10 @@ __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
     HW *__restrict__ qhdr, uint64_t *__restrict__ ring, TbParams P, QParams Q,
     uint32_t *__restrict__ res, uint32_t *__restrict__ ev_cause, int64_t *__restrict__ ev_id,
     uint32_t *__restrict__ ev_count, uint32_t ev_cap, const uint32_t *__restrict__ err, uint32_t narrow,
-    QTick T, FoldFmt G, const uint64_t *__restrict__ rec0, std::conditional_t<CLS, QClsView, NoQCls> QC = {}) {
+    QTick T, FoldFmt G, const uint64_t *__restrict__ rec0, std::conditional_t<CLS, QClsView, NoQCls> QC = {},
+    MK... M) {
     static_assert(!CLS || !PACKED, "classes: wide records only");
+    static_assert(sizeof...(MK) == 0 || (CLS && sizeof...(MK) == 1), "a mask: classed engines, one QClsBits");
     __shared__ __attribute__((aligned(16))) Slot slot[1 << kMaxRBits];   // LDS-DMA destinations
     __shared__ __attribute__((aligned(16))) HW qh[1 << kMaxRBits];
     uint8_t *lcls = nullptr;    // CLS: the bucket's class bytes
@@ -3519,7 +3535,9 @@ __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
 #pragma unroll
         for (uint32_t u = 0; u < kRowsPer; ++u) {
             const uint32_t j = tid + u * kQBlock;
-            if (j < nrows) {
+            bool on = j < nrows;
+            if constexpr (sizeof...(MK) != 0) on = on && (M, ...).has(lcls[j]);   // (read here only: the tick's block)
+            if (on) {
                 Slot st = slot[j];
                 uint64_t h = qh_widen(qh[j]);
                 bool sm = false;
@@ -3581,12 +3599,17 @@ __global__ __launch_bounds__(kQBlock, TBE_Q_WAVES) void k_fold_q(
 // as (key, drain position, request id, remaining); the host orders them by key.
 // CLS: each key is drained with its class's parameters (cls[key] and the class table in
 // global memory: one lookup per queued key).
-template <typename HW, bool CLS = false>
+// MK: empty, or the QClsBits of a masked tick (CLS only): a queued key whose class bit is clear
+// is skipped before its row is loaded -- it adds 0 to the block scan and nothing of it is
+// written, its lapsed row included -- and the trip count stays block-uniform.
+template <typename HW, bool CLS = false, typename... MK>
 __global__ __launch_bounds__(kBlock) void k_drain(
     uint64_t n_keys, Slot *__restrict__ table, HW *__restrict__ qhdr,
     const uint64_t *__restrict__ ring, TbParams P, QParams Q, int64_t ts_us,
     uint64_t *__restrict__ log_keyseq, int64_t *__restrict__ log_id, int32_t *__restrict__ log_rem,
-    uint32_t *__restrict__ log_count, uint32_t log_cap, std::conditional_t<CLS, QClsView, NoQCls> QC = {}) {
+    uint32_t *__restrict__ log_count, uint32_t log_cap, std::conditional_t<CLS, QClsView, NoQCls> QC = {},
+    MK... M) {
+    static_assert(sizeof...(MK) == 0 || (CLS && sizeof...(MK) == 1), "a mask: classed engines, one QClsBits");
     __shared__ uint32_t wsum[kWaves];
     __shared__ uint32_t log_base;
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
@@ -3598,7 +3621,8 @@ __global__ __launch_bounds__(kBlock) void k_drain(
         const uint64_t key = k0 + threadIdx.x;
         const bool valid = key < n_keys;
         uint64_t h = valid ? qh_widen(qhdr[key]) : 0ull;
-        const bool queued = ((h >> 16) & 0xFFFFu) != 0;
+        bool queued = ((h >> 16) & 0xFFFFu) != 0;
+        if constexpr (sizeof...(MK) != 0) queued = queued && (M, ...).has(QC.cls[key]);
         Slot st = (valid && queued) ? table[key] : Slot{0.0, 0};
         const uint64_t *__restrict__ kr = ring + key * (uint64_t)Q.cap;
         bool sm = false;
@@ -4750,6 +4774,7 @@ struct tbe_engine {
     int32_t *acounts = nullptr;   // tbe_approx_refresh's own count buffer (single client)
     int wait_mode = 1;
     QTick qtick{-1, nullptr, nullptr, nullptr, nullptr, 0};   // tbe_wait_batch_tick_device
+    const uint64_t *qtick_mask = nullptr;   // tbe_wait_batch_tick_classes_device on a classed engine: the tick's classes
     std::vector<std::pair<uint64_t, int64_t>> evicted;              // (cause, id), sorted
     std::vector<std::tuple<uint64_t, int64_t, int32_t>> drained;     // (key, id, rem)
 
@@ -5315,6 +5340,12 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
                     e->cfg.n_keys, e->table, qh, e->ring, e->params, q, w.res[0], e->ev_cause, e->ev_id,
                     e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(),
                     e->qtick, G, rec0);
+            else if (e->qcls_par && e->qtick_mask)
+                k_fold_q<false, HW, true, QClsBits><<<e->nbuckets, kQBlock, 0, sf>>>(
+                    sorted.keys, sorted.permits, sorted.ts, sorted.idx, nullptr, nullptr, e->pf, w.bstart,
+                    e->r_bits, e->cfg.n_keys, e->table, qh, e->ring, e->params, q, w.res[0], e->ev_cause,
+                    e->ev_id, e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err,
+                    e->wait_rw(), e->qtick, G, rec0, e->qcls_view(), qcls_bits(e->qtick_mask));
             else if (e->qcls_par)
                 k_fold_q<false, HW, true><<<e->nbuckets, kQBlock, 0, sf>>>(
                     sorted.keys, sorted.permits, sorted.ts, sorted.idx, nullptr, nullptr, e->pf, w.bstart,
@@ -6942,10 +6973,41 @@ tbe_status tbe_evicted(tbe_engine *e, uint64_t *cause_index, int64_t *request_id
     return TBE_OK;
 }
 
-tbe_status tbe_refresh(tbe_engine *e, int64_t ts_us, uint64_t *n_granted) {
-    if (!e || !n_granted) return TBE_EINVAL;
+// The class mask of the queueing kind's *_classes calls: NULL or a bit at or above the number
+// of classes is TBE_EINVAL, decided before the device is touched.
+static tbe_status queue_mask_args(tbe_engine *e, const uint64_t *mask) {
     if (e->cfg.kind != TBE_KIND_QUEUEING) return fail(e, TBE_EINVAL, "not a queueing engine");
-    if (ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+    if (!mask) return fail(e, TBE_EINVAL, "mask is NULL");
+    const uint32_t nc = (uint32_t)e->qclass_opts.size();
+    for (uint32_t c = nc; c < kMaxClasses; ++c)
+        if ((mask[c >> 6] >> (c & 63)) & 1u) return fail(e, TBE_EINVAL, "mask names class %u of %u", c, nc);
+    return TBE_OK;
+}
+static bool mask_empty(const uint64_t *mask) { return !(mask[0] | mask[1] | mask[2] | mask[3]); }
+
+// One k_drain over every key into the given log.  mask == nullptr: the unmasked tick.  With a
+// mask, a classed engine launches the masked form; an engine without extra classes has class 0
+// alone, whose bit the callers have decided (they do not come here with it clear).
+static void launch_drain(tbe_engine *e, int64_t ts_us, uint64_t *keyseq, int64_t *id, int32_t *rem,
+                         uint32_t *count, uint32_t cap, const uint64_t *mask, hipStream_t st) {
+    const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
+    with_qhdr(e, [&](auto *qh) {
+        using HW = std::remove_pointer_t<decltype(qh)>;
+        if (e->qcls_par && mask)
+            k_drain<HW, true, QClsBits><<<(unsigned)blocks, kBlock, 0, st>>>(
+                e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us, keyseq, id, rem, count, cap,
+                e->qcls_view(), qcls_bits(mask));
+        else if (e->qcls_par)
+            k_drain<HW, true><<<(unsigned)blocks, kBlock, 0, st>>>(
+                e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us, keyseq, id, rem, count, cap,
+                e->qcls_view());
+        else
+            k_drain<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us,
+                                                        keyseq, id, rem, count, cap);
+    });
+}
+
+static tbe_status queue_refresh(tbe_engine *e, int64_t ts_us, uint64_t *n_granted, const uint64_t *mask) {
     *n_granted = 0;
     e->drained.clear();
     HIP_TRY(e, hipSetDevice(e->device));
@@ -6954,6 +7016,7 @@ tbe_status tbe_refresh(tbe_engine *e, int64_t ts_us, uint64_t *n_granted) {
         if (qrc != TBE_OK) return qrc;
     }
     if (e->queued_total == 0) return TBE_OK;
+    if (mask && mask_empty(mask)) return TBE_OK;   // no class ticks: nothing drains (an unclassed engine: bit 0 clear)
     if (e->queued_total > e->log_cap) {
         dfree(e->log_keyseq);
         dfree(e->log_id);
@@ -6966,18 +7029,8 @@ tbe_status tbe_refresh(tbe_engine *e, int64_t ts_us, uint64_t *n_granted) {
     }
     hipStream_t st = e->stream;
     HIP_TRY(e, hipMemsetAsync(e->counters + 1, 0, sizeof(uint32_t), st));
-    const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
-    with_qhdr(e, [&](auto *qh) {
-        using HW = std::remove_pointer_t<decltype(qh)>;
-        if (e->qcls_par)
-            k_drain<HW, true><<<(unsigned)blocks, kBlock, 0, st>>>(
-                e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us, e->log_keyseq, e->log_id, e->log_rem,
-                e->counters + 1, (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), e->qcls_view());
-        else
-            k_drain<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us,
-                                                        e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
-                                                        (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu));
-    });
+    launch_drain(e, ts_us, e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
+                 (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), mask, st);
     stats_drained(e, e->log_keyseq, e->counters + 1, (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), st);
     HIP_TRY(e, hipGetLastError());
     uint32_t cnt = 0;
@@ -7002,6 +7055,20 @@ tbe_status tbe_refresh(tbe_engine *e, int64_t ts_us, uint64_t *n_granted) {
     return TBE_OK;
 }
 
+tbe_status tbe_refresh(tbe_engine *e, int64_t ts_us, uint64_t *n_granted) {
+    if (!e || !n_granted) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_QUEUEING) return fail(e, TBE_EINVAL, "not a queueing engine");
+    if (ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+    return queue_refresh(e, ts_us, n_granted, nullptr);
+}
+
+tbe_status tbe_refresh_classes(tbe_engine *e, int64_t ts_us, const uint64_t *mask, uint64_t *n_granted) {
+    if (!e || !n_granted) return TBE_EINVAL;
+    if (tbe_status rc = queue_mask_args(e, mask); rc != TBE_OK) return rc;
+    if (ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+    return queue_refresh(e, ts_us, n_granted, mask);
+}
+
 tbe_status tbe_refresh_bound(tbe_engine *e, uint64_t *bound) {
     if (!e || !bound) return TBE_EINVAL;
     if (e->cfg.kind == TBE_KIND_TOKEN_BUCKET) return fail(e, TBE_EINVAL, "engine has no queues");
@@ -7013,11 +7080,9 @@ tbe_status tbe_refresh_bound(tbe_engine *e, uint64_t *bound) {
     return TBE_OK;
 }
 
-tbe_status tbe_refresh_device(tbe_engine *e, int64_t ts_us, uint64_t *d_keyseq, int64_t *d_request_id,
-                              int32_t *d_remaining, uint64_t capacity, uint32_t *d_count, void *stream) {
-    if (!e || !d_count) return TBE_EINVAL;
-    if (e->cfg.kind != TBE_KIND_QUEUEING) return fail(e, TBE_EINVAL, "not a queueing engine");
-    if (ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+static tbe_status queue_refresh_device(tbe_engine *e, int64_t ts_us, uint64_t *d_keyseq, int64_t *d_request_id,
+                                       int32_t *d_remaining, uint64_t capacity, uint32_t *d_count, void *stream,
+                                       const uint64_t *mask) {
     uint64_t bound = 0;
     tbe_status rc = tbe_refresh_bound(e, &bound);
     if (rc != TBE_OK) return rc;
@@ -7030,34 +7095,39 @@ tbe_status tbe_refresh_device(tbe_engine *e, int64_t ts_us, uint64_t *d_keyseq, 
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
     HIP_TRY(e, hipMemsetAsync(d_count, 0, sizeof(uint32_t), st));
     if (bound == 0) return TBE_OK;   // nothing queued
-    const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
-    with_qhdr(e, [&](auto *qh) {
-        using HW = std::remove_pointer_t<decltype(qh)>;
-        if (e->qcls_par)
-            k_drain<HW, true><<<(unsigned)blocks, kBlock, 0, st>>>(
-                e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us, d_keyseq, d_request_id, d_remaining,
-                d_count, (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu), e->qcls_view());
-        else
-            k_drain<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us,
-                                                        d_keyseq, d_request_id, d_remaining, d_count,
-                                                        (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu));
-    });
+    if (mask && mask_empty(mask)) return TBE_OK;   // no class ticks: *d_count = 0 (queued_total and queued_exact stay)
+    launch_drain(e, ts_us, d_keyseq, d_request_id, d_remaining, d_count,
+                 (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu), mask, st);
     stats_drained(e, d_keyseq, d_count, (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu), st);
     HIP_TRY(e, hipGetLastError());
     e->queued_exact = false;   // queued_total stays an upper bound
     return TBE_OK;
 }
 
-tbe_status tbe_wait_batch_tick_device(tbe_engine *e, const uint64_t *d_keys, const int32_t *d_permits,
-                                      const int64_t *d_ts_us, uint64_t n, int64_t id_base, int32_t wait,
-                                      uint8_t *d_status, int32_t *d_remaining, int64_t tick_ts_us,
-                                      uint64_t *d_keyseq, int64_t *d_request_id, int32_t *d_log_remaining,
-                                      uint64_t capacity, uint32_t *d_count, void *stream) {
+tbe_status tbe_refresh_device(tbe_engine *e, int64_t ts_us, uint64_t *d_keyseq, int64_t *d_request_id,
+                              int32_t *d_remaining, uint64_t capacity, uint32_t *d_count, void *stream) {
     if (!e || !d_count) return TBE_EINVAL;
     if (e->cfg.kind != TBE_KIND_QUEUEING) return fail(e, TBE_EINVAL, "not a queueing engine");
-    if (tick_ts_us < 0) return fail(e, TBE_EINVAL, "tick_ts_us < 0");
-    if (n == 0) return tbe_refresh_device(e, tick_ts_us, d_keyseq, d_request_id, d_log_remaining, capacity,
-                                          d_count, stream);
+    if (ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+    return queue_refresh_device(e, ts_us, d_keyseq, d_request_id, d_remaining, capacity, d_count, stream, nullptr);
+}
+
+tbe_status tbe_refresh_classes_device(tbe_engine *e, int64_t ts_us, const uint64_t *mask, uint64_t *d_keyseq,
+                                      int64_t *d_request_id, int32_t *d_remaining, uint64_t capacity,
+                                      uint32_t *d_count, void *stream) {
+    if (!e || !d_count) return TBE_EINVAL;
+    if (tbe_status rc = queue_mask_args(e, mask); rc != TBE_OK) return rc;
+    if (ts_us < 0) return fail(e, TBE_EINVAL, "ts_us < 0");
+    return queue_refresh_device(e, ts_us, d_keyseq, d_request_id, d_remaining, capacity, d_count, stream, mask);
+}
+
+static tbe_status queue_wait_batch_tick(tbe_engine *e, const uint64_t *d_keys, const int32_t *d_permits,
+                                        const int64_t *d_ts_us, uint64_t n, int64_t id_base, int32_t wait,
+                                        uint8_t *d_status, int32_t *d_remaining, int64_t tick_ts_us,
+                                        uint64_t *d_keyseq, int64_t *d_request_id, int32_t *d_log_remaining,
+                                        uint64_t capacity, uint32_t *d_count, void *stream, const uint64_t *mask) {
+    if (n == 0) return queue_refresh_device(e, tick_ts_us, d_keyseq, d_request_id, d_log_remaining, capacity,
+                                            d_count, stream, mask);
     if (!d_ts_us) return fail(e, TBE_EINVAL, "null buffer");
     // the drain log bound after this batch's possible enqueues (tbe_refresh_bound)
     const uint64_t per_key = e->q_per_key;
@@ -7071,14 +7141,43 @@ tbe_status tbe_wait_batch_tick_device(tbe_engine *e, const uint64_t *d_keys, con
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
     HIP_TRY(e, hipMemsetAsync(d_count, 0, sizeof(uint32_t), st));
     e->wait_mode = wait ? 1 : 0;
-    e->qtick = QTick{tick_ts_us, d_keyseq, d_request_id, d_log_remaining, d_count,
-                     (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu)};
+    // a mask without a class: the batch alone (*d_count stays 0), tbe_wait_batch_device's launch
+    if (!(mask && mask_empty(mask)))
+        e->qtick = QTick{tick_ts_us, d_keyseq, d_request_id, d_log_remaining, d_count,
+                         (uint32_t)std::min<uint64_t>(capacity, 0xFFFFFFFFu)};
+    e->qtick_mask = e->qcls_par ? mask : nullptr;   // (an unclassed engine: bit 0 is set here, the unmasked tick)
     const tbe_status rc = status_batch_device(e, d_keys, d_permits, d_ts_us, n, id_base, d_status, d_remaining, stream);
     e->qtick = QTick{-1, nullptr, nullptr, nullptr, nullptr, 0};
+    e->qtick_mask = nullptr;
     if (rc != TBE_OK) return rc;
     e->drained.clear();
     e->queued_exact = false;   // queued_total stays an upper bound
     return TBE_OK;
+}
+
+tbe_status tbe_wait_batch_tick_device(tbe_engine *e, const uint64_t *d_keys, const int32_t *d_permits,
+                                      const int64_t *d_ts_us, uint64_t n, int64_t id_base, int32_t wait,
+                                      uint8_t *d_status, int32_t *d_remaining, int64_t tick_ts_us,
+                                      uint64_t *d_keyseq, int64_t *d_request_id, int32_t *d_log_remaining,
+                                      uint64_t capacity, uint32_t *d_count, void *stream) {
+    if (!e || !d_count) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_QUEUEING) return fail(e, TBE_EINVAL, "not a queueing engine");
+    if (tick_ts_us < 0) return fail(e, TBE_EINVAL, "tick_ts_us < 0");
+    return queue_wait_batch_tick(e, d_keys, d_permits, d_ts_us, n, id_base, wait, d_status, d_remaining, tick_ts_us,
+                                 d_keyseq, d_request_id, d_log_remaining, capacity, d_count, stream, nullptr);
+}
+
+tbe_status tbe_wait_batch_tick_classes_device(tbe_engine *e, const uint64_t *d_keys, const int32_t *d_permits,
+                                              const int64_t *d_ts_us, uint64_t n, int64_t id_base, int32_t wait,
+                                              uint8_t *d_status, int32_t *d_remaining, int64_t tick_ts_us,
+                                              const uint64_t *mask, uint64_t *d_keyseq, int64_t *d_request_id,
+                                              int32_t *d_log_remaining, uint64_t capacity, uint32_t *d_count,
+                                              void *stream) {
+    if (!e || !d_count) return TBE_EINVAL;
+    if (tbe_status rc = queue_mask_args(e, mask); rc != TBE_OK) return rc;
+    if (tick_ts_us < 0) return fail(e, TBE_EINVAL, "tick_ts_us < 0");
+    return queue_wait_batch_tick(e, d_keys, d_permits, d_ts_us, n, id_base, wait, d_status, d_remaining, tick_ts_us,
+                                 d_keyseq, d_request_id, d_log_remaining, capacity, d_count, stream, mask);
 }
 
 // The class mask of the *_classes calls: NULL or a bit at or above the number of classes is

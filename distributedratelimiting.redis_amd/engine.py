@@ -478,29 +478,49 @@ class QueueingTokenBucketEngine(TokenBucketEngine):
         return b.value
 
     def refresh_device(self, ts_us: int, d_keyseq, d_ids, d_rem, d_count,
-                       stream: Optional[int] = None) -> None:
+                       stream: Optional[int] = None, classes=None) -> None:
         """Enqueue one replenish tick; the drain log lands in the device tensors
-        (capacity = d_keyseq.numel(), which must be >= refresh_bound())."""
+        (capacity = d_keyseq.numel(), which must be >= refresh_bound()).  ``classes``: an
+        iterable of class numbers; the tick drains those classes' keys alone and leaves every
+        other key untouched (tbe_refresh_classes_device)."""
+        if classes is not None:
+            self._check(self._lib.tbe_refresh_classes_device(
+                self.handle, ts_us, _capi.class_mask(classes), d_keyseq.data_ptr(), d_ids.data_ptr(),
+                d_rem.data_ptr(), d_keyseq.numel(), d_count.data_ptr(), stream))
+            return
         self._check(self._lib.tbe_refresh_device(self.handle, ts_us, d_keyseq.data_ptr(), d_ids.data_ptr(),
                                                  d_rem.data_ptr(), d_keyseq.numel(), d_count.data_ptr(),
                                                  stream))
 
     def wait_batch_tick_device(self, d_keys, d_permits, d_ts, d_status, d_remaining, id_base: int,
                                tick_ts_us: int, d_keyseq, d_ids, d_rem, d_count, wait: bool = True,
-                               stream: Optional[int] = None) -> None:
+                               stream: Optional[int] = None, classes=None) -> None:
         """``wait_batch_device`` then ``refresh_device(tick_ts_us)`` as one fused call
         (tbe_wait_batch_tick_device); the log capacity must cover ``refresh_bound()`` after
-        the batch."""
+        the batch.  ``classes``: the batch is decided for every class and the fused tick drains
+        the named classes alone (tbe_wait_batch_tick_classes_device)."""
         n = d_keys.numel()
+        if classes is not None:
+            self._check(self._lib.tbe_wait_batch_tick_classes_device(
+                self.handle, d_keys.data_ptr(), d_permits.data_ptr(), d_ts.data_ptr(), n, id_base,
+                1 if wait else 0, d_status.data_ptr(), d_remaining.data_ptr(), tick_ts_us,
+                _capi.class_mask(classes), d_keyseq.data_ptr(), d_ids.data_ptr(), d_rem.data_ptr(),
+                d_keyseq.numel(), d_count.data_ptr(), stream))
+            return
         self._check(self._lib.tbe_wait_batch_tick_device(
             self.handle, d_keys.data_ptr(), d_permits.data_ptr(), d_ts.data_ptr(), n, id_base,
             1 if wait else 0, d_status.data_ptr(), d_remaining.data_ptr(), tick_ts_us, d_keyseq.data_ptr(),
             d_ids.data_ptr(), d_rem.data_ptr(), d_keyseq.numel(), d_count.data_ptr(), stream))
 
-    def refresh(self, ts_us: int):
-        """One replenish tick; returns (keys u64, request ids i64, remaining i32) in (key, drain) order."""
+    def refresh(self, ts_us: int, classes=None):
+        """One replenish tick; returns (keys u64, request ids i64, remaining i32) in (key, drain) order.
+        ``classes``: an iterable of class numbers whose keys the tick drains (tbe_refresh_classes:
+        each limiter's own timer in the reference); every other key is left untouched."""
         n = ctypes.c_uint64()
-        self._check(self._lib.tbe_refresh(self.handle, ts_us, byref(n)))
+        if classes is None:
+            self._check(self._lib.tbe_refresh(self.handle, ts_us, byref(n)))
+        else:
+            self._check(self._lib.tbe_refresh_classes(self.handle, ts_us, _capi.class_mask(classes), byref(n)))
         m = n.value
         keys = np.empty(m, dtype=np.uint64)
         ids = np.empty(m, dtype=np.int64)

@@ -147,9 +147,8 @@ namespace detail {
 class LimiterCore {
 public:
     LimiterCore(tbe_kind kind, const RedisQueueingTokenBucketRateLimiterOptions &o, bool partitioned,
-                const char *type_name, const std::vector<ApproximateTokenBucketClass> *aclasses = nullptr,
-                std::function<void(const RefreshTrace &)> on_refresh = {})
-        : kind_(kind), opt_(o), partitioned_(partitioned), type_name_(type_name), on_refresh_(std::move(on_refresh)) {
+                const char *type_name, const std::vector<ApproximateTokenBucketClass> *aclasses = nullptr)
+        : kind_(kind), opt_(o), partitioned_(partitioned), type_name_(type_name), on_refresh_(o.OnRefresh) {
         // Constructor checks in reference order (TB:24-42; A:44-72).
         if (o.TokenLimit <= 0 || o.TokensPerPeriod <= 0)
             throw ArgumentException("Both TokenLimit and TokensPerPeriod must be set to values greater than 0.",
@@ -204,6 +203,30 @@ public:
             if (aextra.size() > 255)
                 throw ArgumentException("ApproximateClasses: at most 255 extra classes.", "options");
         }
+        // queueing limit classes: five options each, class 0 the options' own
+        std::vector<tbe_queue_class> qextra;
+        if (!o.QueueingClasses.empty()) {
+            if (!(kind == TBE_KIND_QUEUEING && partitioned))
+                throw ArgumentException("QueueingClasses: only PartitionedRedisQueueingTokenBucketRateLimiter "
+                                        "takes queueing limit classes.", "options");
+            for (const QueueingTokenBucketClass &k : o.QueueingClasses) {
+                if (k.TokenLimit <= 0 || k.TokensPerPeriod <= 0)
+                    throw ArgumentException("QueueingClasses: both TokenLimit and TokensPerPeriod must be "
+                                            "greater than 0.", "options");
+                if (k.QueueLimit < 0)
+                    throw ArgumentException("QueueingClasses: QueueLimit must be greater than or equal to 0.",
+                                            "options");
+                if (k.ReplenishmentPeriod.ticks < 0)
+                    throw ArgumentException("QueueingClasses: ReplenishmentPeriod must be greater than or equal "
+                                            "to TimeSpan.Zero.", "options");
+                qextra.push_back(tbe_queue_class{k.TokenLimit, k.TokensPerPeriod, k.ReplenishmentPeriod.ticks,
+                                                 k.QueueLimit, (int32_t)k.QueueProcessingOrder});
+                class_limit_.push_back(k.TokenLimit);
+                class_period_ticks_.push_back(k.ReplenishmentPeriod.ticks);
+            }
+            if (qextra.size() > 255)
+                throw ArgumentException("QueueingClasses: at most 255 extra classes.", "options");
+        }
         clock_ = o.TimeSource ? o.TimeSource : Clock(SystemClockMicros);
         tbe_config c{};
         c.struct_size = sizeof c;
@@ -218,13 +241,14 @@ public:
         c.max_batch = o.MaxBatch;
         c.zero_wait_slots = kind == TBE_KIND_APPROXIMATE ? o.ZeroWaitSlots : 0;
         if (o.TrackStatistics) c.flags |= TBE_FLAG_STATS;
-        const tbe_status st = aextra.empty()
-                                  ? tbe_create_classes(&c, extra.data(), (uint32_t)extra.size(), &eng_)
-                                  : tbe_create_approx_classes(&c, aextra.data(), (uint32_t)aextra.size(), &eng_);
+        const tbe_status st =
+            !aextra.empty()   ? tbe_create_approx_classes(&c, aextra.data(), (uint32_t)aextra.size(), &eng_)
+            : !qextra.empty() ? tbe_create_queue_classes(&c, qextra.data(), (uint32_t)qextra.size(), &eng_)
+                              : tbe_create_classes(&c, extra.data(), (uint32_t)extra.size(), &eng_);
         if (st == TBE_EINVAL) throw ArgumentException(std::string("invalid limiter options: ") + tbe_last_error(nullptr), "options");
         if (st != TBE_OK) throw RateLimiterEngineException(st, std::string("tbe_create failed: ") + tbe_last_error(nullptr));
         // TB:234 per class: EXPIRE ceil(min(max(capacity / fill_rate, 1), 31536000)) seconds
-        for (size_t i = 0; i < class_limit_.size() && aextra.empty(); ++i) {
+        for (size_t i = 0; i < class_limit_.size() && aextra.empty() && qextra.empty(); ++i) {
             const double rate = i == 0 ? o.FillRatePerSecond()
                                        : tbe_fill_rate(extra[i - 1].tokens_per_period,
                                                        extra[i - 1].replenishment_period_ticks);
@@ -235,9 +259,10 @@ public:
         }
         inbox_->core = this;
         submitter_ = std::thread([this] { Loop(); });
-        // One timer per distinct ReplenishmentPeriod (the reference's Timer per limiter, A:77): a
-        // limiter without approximate classes has the one timer it always had, which refreshes
-        // everything; with classes each timer refreshes the classes of its period alone.
+        // One timer per distinct ReplenishmentPeriod (the reference's Timer per limiter, A:77 and
+        // Q's _renewTimer): a limiter without approximate or queueing classes has the one timer it
+        // always had, which refreshes everything; with classes each timer refreshes the classes of
+        // its period alone.
         if (kind != TBE_KIND_TOKEN_BUCKET) {
             for (size_t cls = 0; cls < class_period_ticks_.size(); ++cls) {
                 PeriodTimer *t = nullptr;
@@ -247,7 +272,7 @@ public:
                     timers_.push_back(std::make_unique<PeriodTimer>());
                     t = timers_.back().get();
                     t->ticks = class_period_ticks_[cls];
-                    t->masked = !aextra.empty();
+                    t->masked = !aextra.empty() || !qextra.empty();
                 }
                 t->mask[cls >> 6] |= 1ull << (cls & 63);
                 t->classes.push_back((int)cls);
@@ -411,6 +436,7 @@ public:
         const uint64_t n = names_.size();
         if (n == 0) return 0;
         if (kind_ == TBE_KIND_APPROXIMATE) return ReclaimIdle(n, busy);
+        if (kind_ == TBE_KIND_QUEUEING) return ReclaimQueueing(n, busy);
         // TB:234: EXPIRE ceil(min(max(capacity / fill_rate, 1), 31536000)) seconds; the
         // engine's expiry test is tbe_query's (millisecond resolution).  With limit classes a
         // key lapses by the TTL of its own class (class_ttl_ms_).
@@ -486,6 +512,52 @@ public:
                 ++freed;
             }
             if (any) Check(tbe_approx_reset(eng_, k0, m, flags.data()));
+        }
+        reclaimed_ += freed;
+        return freed;
+    }
+
+    // The queueing branch of Reclaim (reclaim_mu_ and dir_mu_ held, submitter thread): the engine
+    // says which keys Redis would have dropped by now (tbe_expired_device: absent or lapsed by the
+    // TTL of the key's class, and never a key with queued requests, so a queued wait keeps its
+    // name).  The flags land in page-locked host memory, which the device writes directly.
+    uint64_t ReclaimQueueing(uint64_t n, const std::unordered_set<uint64_t> &busy) {
+        const int64_t now = clock_();
+        std::vector<uint8_t> is_free(n, 0);
+        for (uint64_t k : free_ids_) is_free[k] = 1;
+        uint64_t freed = 0;
+        constexpr uint64_t kChunk = 1u << 20;
+        void *buf = nullptr;
+        Check(tbe_alloc_host(std::min(n, kChunk), &buf));
+        std::unique_ptr<void, void (*)(void *)> hold(buf, [](void *p) { (void)tbe_free_host(p); });
+        uint8_t *flags = static_cast<uint8_t *>(buf);
+        for (uint64_t k0 = 0; k0 < n; k0 += kChunk) {
+            const uint64_t m = std::min(kChunk, n - k0);
+            Check(tbe_expired_device(eng_, now, k0, m, flags, 0, nullptr));
+            Check(tbe_synchronize(eng_));
+            std::vector<uint64_t> ids;
+            for (uint64_t j = 0; j < m; ++j) {
+                const uint64_t k = k0 + j;
+                if (!flags[j] || is_free[k] || busy.count(k)) continue;
+                dir_.erase(names_[k]);
+                names_[k].clear();
+                last_reply_.erase(k);
+                free_ids_.push_back(k);
+                ids.push_back(k);
+                ++freed;
+            }
+            if (ids.empty()) continue;
+            // a freed key's row goes back absent, so a new name starts from a full bucket whatever
+            // the clock does later; its lease counters go to the next name at zero
+            const std::vector<double> v(ids.size(), 0.0);
+            const std::vector<int64_t> t(ids.size(), INT64_MIN);
+            Check(tbe_import_rows(eng_, ids.data(), v.data(), t.data(), ids.size()));
+            if (opt_.TrackStatistics) {
+                std::vector<uint64_t> ok(m), failed(m);
+                Check(tbe_stats_export(eng_, k0, m, ok.data(), failed.data()));
+                for (uint64_t k : ids) ok[k - k0] = failed[k - k0] = 0;
+                Check(tbe_stats_import(eng_, k0, m, ok.data(), failed.data()));
+            }
         }
         reclaimed_ += freed;
         return freed;
@@ -578,18 +650,21 @@ public:
     }
 
     // One replenish tick (Q:237-271) / RefreshAsync (A:412-508), on the submitter thread.
-    // mask != nullptr (approximate limit classes): the classes of one timer's period alone.
+    // mask != nullptr (a limiter with approximate or queueing classes): the classes of one
+    // timer's period alone.
     void RefreshNow(const uint64_t *mask = nullptr) {
         if (disposed_.load()) return;  // A:414-417
         const int64_t now = clock_();
         uint64_t n = 0;
-        if (kind_ == TBE_KIND_QUEUEING)
+        if (kind_ == TBE_KIND_QUEUEING && mask)
+            Check(tbe_refresh_classes(eng_, now, mask, &n));
+        else if (kind_ == TBE_KIND_QUEUEING)
             Check(tbe_refresh(eng_, now, &n));
         else if (mask)
             Check(tbe_approx_refresh_classes(eng_, now, mask, &n));
         else
             Check(tbe_approx_refresh(eng_, now, &n));
-        if (on_refresh_ && kind_ == TBE_KIND_APPROXIMATE) {
+        if (on_refresh_) {
             RefreshTrace tr{now, {~0ull, ~0ull, ~0ull, ~0ull}};
             if (mask) std::copy(mask, mask + 4, tr.ClassMask);
             on_refresh_(tr);
@@ -866,7 +941,7 @@ private:
     struct PeriodTimer {
         int64_t ticks = 0;
         uint64_t mask[4] = {0, 0, 0, 0};
-        bool masked = false;               // false: the unmasked refresh (no approximate classes)
+        bool masked = false;               // false: the unmasked refresh (a limiter without extra classes)
         std::vector<int> classes;
         std::atomic<bool> pending{false};
         std::thread thread;
@@ -1050,11 +1125,65 @@ std::future<RateLimitLease> RedisQueueingTokenBucketRateLimiter::AcquireAsyncCor
 }
 void RedisQueueingTokenBucketRateLimiter::DisposeCore() { core_->Dispose(); }
 
+// ------------------------------------------------------------------ partitioned queueing
+PartitionedRedisQueueingTokenBucketRateLimiter::PartitionedRedisQueueingTokenBucketRateLimiter(
+    const RedisQueueingTokenBucketRateLimiterOptions &o)
+    : core_(std::make_unique<LimiterCore>(TBE_KIND_QUEUEING, o, true,
+                                          "PartitionedRedisQueueingTokenBucketRateLimiter")) {}
+PartitionedRedisQueueingTokenBucketRateLimiter::~PartitionedRedisQueueingTokenBucketRateLimiter() = default;
+int PartitionedRedisQueueingTokenBucketRateLimiter::GetAvailablePermits(const std::string &id) {
+    core_->ThrowIfDisposed();
+    uint64_t k;
+    return core_->KnownKey(id, k) ? core_->LastReply(k) : core_->ClassLimit(core_->ClassOfResource(id));
+}
+std::optional<RateLimiterStatistics> PartitionedRedisQueueingTokenBucketRateLimiter::GetStatistics(
+    const std::string &id) {
+    if (!core_->TracksStatistics()) return std::nullopt;
+    core_->ThrowIfDisposed();
+    // on the submitter thread, where reclaims run: the name cannot lose its key in between
+    return core_->Run([this, &id] {
+        uint64_t k;
+        if (!core_->KnownKey(id, k))
+            return RateLimiterStatistics{core_->ClassLimit(core_->ClassOfResource(id)), 0, 0, 0};
+        return core_->QueryStatistics(k, core_->LastReply(k));
+    });
+}
+bool PartitionedRedisQueueingTokenBucketRateLimiter::TryReplenish() {
+    if (core_->options().AutoReplenishment) return false;
+    core_->ThrowIfDisposed();
+    core_->Run([this] { core_->RefreshNow(); });
+    return true;
+}
+std::vector<std::pair<TimeSpan, std::vector<int>>>
+PartitionedRedisQueueingTokenBucketRateLimiter::ReplenishmentTimers() const {
+    return core_->Timers();
+}
+void PartitionedRedisQueueingTokenBucketRateLimiter::TickTimer(size_t index) {
+    core_->ThrowIfDisposed();
+    core_->Run([this, index] { core_->TickTimer(index); });
+}
+uint64_t PartitionedRedisQueueingTokenBucketRateLimiter::ReclaimExpired() {
+    core_->ThrowIfDisposed();
+    return core_->Run([this] { return core_->Reclaim(); });
+}
+RateLimitLease PartitionedRedisQueueingTokenBucketRateLimiter::AttemptAcquireCore(const std::string &id, int p) {
+    check_limit(p, core_->LimitOfResource(id));
+    core_->ThrowIfDisposed();
+    return core_->SubmitResource(id, p, kQueueAttempt).get();
+}
+std::future<RateLimitLease> PartitionedRedisQueueingTokenBucketRateLimiter::AcquireAsyncCore(
+    const std::string &id, int p, const CancellationToken &ct) {
+    check_limit(p, core_->LimitOfResource(id));
+    core_->ThrowIfDisposed();
+    return core_->SubmitResource(id, p, kQueueWait, ct);
+}
+void PartitionedRedisQueueingTokenBucketRateLimiter::DisposeCore() { core_->Dispose(); }
+
 // ------------------------------------------------------------------ approximate
 RedisApproximateTokenBucketRateLimiter::RedisApproximateTokenBucketRateLimiter(
     const RedisApproximateTokenBucketRateLimiterOptions &o)
     : core_(std::make_unique<LimiterCore>(TBE_KIND_APPROXIMATE, o, false, "RedisApproximateTokenBucketRateLimiter",
-                                          &o.ApproximateClasses, o.OnRefresh)) {}
+                                          &o.ApproximateClasses)) {}
 RedisApproximateTokenBucketRateLimiter::~RedisApproximateTokenBucketRateLimiter() = default;
 std::optional<TimeSpan> RedisApproximateTokenBucketRateLimiter::IdleDuration() const { return core_->IdleDuration(); }
 int RedisApproximateTokenBucketRateLimiter::GetAvailablePermits() {
@@ -1104,7 +1233,7 @@ PartitionedRedisApproximateTokenBucketRateLimiter::PartitionedRedisApproximateTo
     const RedisApproximateTokenBucketRateLimiterOptions &o)
     : core_(std::make_unique<LimiterCore>(TBE_KIND_APPROXIMATE, o, true,
                                           "PartitionedRedisApproximateTokenBucketRateLimiter",
-                                          &o.ApproximateClasses, o.OnRefresh)) {}
+                                          &o.ApproximateClasses)) {}
 PartitionedRedisApproximateTokenBucketRateLimiter::~PartitionedRedisApproximateTokenBucketRateLimiter() = default;
 int PartitionedRedisApproximateTokenBucketRateLimiter::GetAvailablePermits(const std::string &id) {
     core_->ThrowIfDisposed();

@@ -15,6 +15,7 @@
 //   RedisQueueingTokenBucketRateLimiter    TokenBucketWithQueue/RedisTokenBucketRateLimiter.cs:9-400
 //   RedisApproximateTokenBucketRateLimiter ApproximateTokenBucket/RedisApproximateTokenBucketRateLimiter.cs:9-599
 //   PartitionedRedisApproximateTokenBucketRateLimiter   the reference README's second TODO (no file upstream)
+//   PartitionedRedisQueueingTokenBucketRateLimiter      Q:9-400 behind the partitioner of PTB:42 (no file upstream)
 //   *Options                               */Redis*Options.cs (TBO:9-85, QO, AO)
 //   ServiceCollection::AddRedis*           ServiceCollectionExtensions.cs:10-26
 // Method names follow the GA System.Threading.RateLimiting API (AttemptAcquire /
@@ -202,11 +203,37 @@ struct RedisTokenBucketRateLimiterOptions {
     double FillRatePerSecond() const;                             // TBO:82-85
 };
 
+// One limit class of a partitioned queueing limiter: the five options the reference
+// interpolates into a limiter's script and keeps in its object (Q:405-461, TB:184-185), so that
+// differently configured limiters share one store.
+struct QueueingTokenBucketClass {
+    int TokenLimit = 0;
+    int TokensPerPeriod = 0;
+    TimeSpan ReplenishmentPeriod = TimeSpan::FromSeconds(1);
+    int QueueLimit = 0;
+    ::tbe::rate_limiting::QueueProcessingOrder QueueProcessingOrder =
+        ::tbe::rate_limiting::QueueProcessingOrder::OldestFirst;
+};
+
+// One refresh as the engine was asked for it (diagnostics, tests): its time and the classes it
+// covered (bit c of ClassMask[c >> 6]: class c; all ones: every class, the unmasked call).
+struct RefreshTrace {
+    int64_t ts_us;
+    uint64_t ClassMask[4];
+};
+
 // RedisQueueingTokenBucketRateLimiterOptions (TokenBucketWithQueue/...Options.cs).
 struct RedisQueueingTokenBucketRateLimiterOptions : RedisTokenBucketRateLimiterOptions {
     int QueueLimit = 0;
     ::tbe::rate_limiting::QueueProcessingOrder QueueProcessingOrder =
         ::tbe::rate_limiting::QueueProcessingOrder::OldestFirst;
+    // PartitionedRedisQueueingTokenBucketRateLimiter only (every other limiter throws
+    // ArgumentException when it is non-empty): the extra limit classes 1, 2, ...; class 0 is the
+    // five options of this struct.  ClassOf (inherited) is the partitioner, with the rules it has
+    // on the partitioned token-bucket limiter.  (The inherited three-field Classes stays the
+    // token bucket's and is refused by every queueing limiter.)
+    std::vector<QueueingTokenBucketClass> QueueingClasses;
+    std::function<void(const RefreshTrace &)> OnRefresh;  // diagnostics (tests): every replenish tick / refresh
     // Timer-driven replenishment every ReplenishmentPeriod (the reference's timer);
     // false: call TryReplenish() yourself (as System.Threading.RateLimiting allows).
     bool AutoReplenishment = true;
@@ -228,13 +255,6 @@ struct ApproximateTokenBucketClass {
         ::tbe::rate_limiting::QueueProcessingOrder::OldestFirst;
 };
 
-// One refresh as the engine was asked for it (diagnostics, tests): its time and the classes it
-// covered (bit c of ClassMask[c >> 6]: class c; all ones: every class, the unmasked call).
-struct RefreshTrace {
-    int64_t ts_us;
-    uint64_t ClassMask[4];
-};
-
 // RedisApproximateTokenBucketRateLimiterOptions (ApproximateTokenBucket/...Options.cs).
 struct RedisApproximateTokenBucketRateLimiterOptions : RedisQueueingTokenBucketRateLimiterOptions {
     // PartitionedRedisApproximateTokenBucketRateLimiter only (the non-partitioned limiter throws
@@ -243,7 +263,6 @@ struct RedisApproximateTokenBucketRateLimiterOptions : RedisQueueingTokenBucketR
     // partitioned token-bucket limiter.  (The inherited three-field Classes stays the token
     // bucket's and is refused here.)
     std::vector<ApproximateTokenBucketClass> ApproximateClasses;
-    std::function<void(const RefreshTrace &)> OnRefresh;  // diagnostics (tests)
 };
 
 // ------------------------------------------------------------------ base classes
@@ -352,6 +371,42 @@ public:
 protected:
     RateLimitLease AttemptAcquireCore(int permitCount) override;
     std::future<RateLimitLease> AcquireAsyncCore(int permitCount, const CancellationToken &ct) override;          // Q:67-134
+    void DisposeCore() override;
+private:
+    std::unique_ptr<detail::LimiterCore> core_;
+};
+
+// One queueing limiter per resourceID (BucketId = InstanceName + resourceID, as PTB:42), all
+// of them in one engine with queueing limit classes (tbe_create_queue_classes): each name has
+// its own bucket row and queue, and is decided with the five options of its class
+// (Options.QueueingClasses, Options.ClassOf).  AttemptAcquire is Q:136-165, AcquireAsync
+// Q:67-134; a queued lease completes at the replenish tick of its class.
+class PartitionedRedisQueueingTokenBucketRateLimiter final : public PartitionedRateLimiter<std::string> {
+public:
+    explicit PartitionedRedisQueueingTokenBucketRateLimiter(const RedisQueueingTokenBucketRateLimiterOptions &options);
+    ~PartitionedRedisQueueingTokenBucketRateLimiter() override;
+    // The last script reply for a name that holds a key; for one that does not, the TokenLimit of
+    // ClassOf(name), without assigning a key.
+    int GetAvailablePermits(const std::string &resourceID) override;
+    std::optional<RateLimiterStatistics> GetStatistics(const std::string &resourceID) override;
+    // one replenish tick (Q:237-271) of every name of every class now; false when
+    // AutoReplenishment is on
+    bool TryReplenish();
+    // AutoReplenishment runs one timer per distinct ReplenishmentPeriod among the classes, as the
+    // reference runs one timer per limiter object: each drains only the names of the classes of
+    // its period (tbe_refresh_classes).  ReplenishmentTimers lists them (period, classes), in the
+    // order of each period's first class.
+    std::vector<std::pair<TimeSpan, std::vector<int>>> ReplenishmentTimers() const;
+    // What timer `index` does at its tick, now (for a host that drives time itself, and tests).
+    void TickTimer(size_t index);
+    // Frees the keys of buckets Redis would have expired (TB:232-235, by each name's class) for
+    // new resource ids; a name with a queued wait keeps its key.  Runs by itself when all
+    // PartitionLimit keys are taken.  Returns the number freed.
+    uint64_t ReclaimExpired();
+protected:
+    RateLimitLease AttemptAcquireCore(const std::string &resourceID, int permitCount) override;   // Q:136-165
+    std::future<RateLimitLease> AcquireAsyncCore(const std::string &resourceID, int permitCount,
+                                                 const CancellationToken &ct) override;           // Q:67-134
     void DisposeCore() override;
 private:
     std::unique_ptr<detail::LimiterCore> core_;

@@ -166,7 +166,9 @@ tbe_status tbe_classes(const tbe_engine *engine, tbe_class *out, uint32_t capaci
  * share one Redis.  Every request, and every drained entry of a tick, is decided exactly as
  * on a plain engine with the options of its key's class: the REJECTED test (Q:70-73), the
  * script call, the Q:153 test, admission and NewestFirst eviction (Q:92-109), and the head
- * or tail the drain peeks (Q:237-271).  A tick drains every key of every class. */
+ * or tail the drain peeks (Q:237-271).  tbe_refresh(_device) and the tick of
+ * tbe_wait_batch_tick_device drain every key of every class; the *_classes forms below tick
+ * the classes of a mask alone, as each limiter's own timer does in the reference. */
 typedef struct tbe_queue_class {
     int32_t token_limit;                  /* TokenLimit (TBO:43), > 0 and < 2^30 - 1 */
     int32_t tokens_per_period;            /* TokensPerPeriod (TBO:30), > 0 */
@@ -461,6 +463,42 @@ tbe_status tbe_wait_batch_tick_device(tbe_engine *engine, const uint64_t *d_keys
                                       uint64_t *d_keyseq, int64_t *d_request_id, int32_t *d_log_remaining,
                                       uint64_t capacity, uint32_t *d_count, void *stream);
 
+/* ---- Per-class replenish ticks.  In the reference the replenish timer belongs
+ * to one limiter (its own ReplenishmentPeriod) and drains that limiter's queue alone
+ * (Q:237-271); these three calls are tbe_refresh, tbe_refresh_device and
+ * tbe_wait_batch_tick_device with a class mask, so the classes of one engine tick at their own
+ * periods.  mask: host memory, 256 bits, bit c of word c >> 6 = class c (the form
+ * tbe_approx_refresh_classes takes); it is read before the call returns.
+ *   A key whose class bit is set: the unmasked call for that key -- same grants, same log
+ *     entries, same row and header bits.
+ *   A key whose class bit is clear: left alone completely.  Its row {v, t}, its queue header
+ *     and its ring keep their bits, nothing of it is logged, and a row that would have lapsed
+ *     by its class's TTL at ts_us is not rewritten: that passive expiry belongs to the tick of
+ *     the key's own limiter.
+ *   An engine without extra classes: bit 0 set is the unmasked call; bit 0 clear drains
+ *     nothing and writes *d_count = 0 (the fused call is then tbe_wait_batch_device).
+ *   An all-clear mask is valid and drains nothing.
+ * In tbe_wait_batch_tick_classes_device the batch's requests are decided for every class; only
+ * the fused tick is masked.
+ * TBE_EINVAL before the device is touched: mask == NULL, a bit at or above the number of
+ * classes, an engine that is not of the queueing kind (and what the unmasked call refuses).
+ * tbe_refresh_bound is unchanged and remains an upper bound for a masked tick; the capacity
+ * checks use it.  The engine's count of queued entries and TBE_FLAG_STATS counting are handled
+ * as in the unmasked calls.  tbe_refresh_classes's log is read with tbe_refresh_log. */
+tbe_status tbe_refresh_classes(tbe_engine *engine, int64_t ts_us, const uint64_t *mask, uint64_t *n_granted);
+
+tbe_status tbe_refresh_classes_device(tbe_engine *engine, int64_t ts_us, const uint64_t *mask,
+                                      uint64_t *d_keyseq, int64_t *d_request_id, int32_t *d_remaining,
+                                      uint64_t capacity, uint32_t *d_count, void *stream);
+
+tbe_status tbe_wait_batch_tick_classes_device(tbe_engine *engine, const uint64_t *d_keys,
+                                              const int32_t *d_permits, const int64_t *d_ts_us, uint64_t n,
+                                              int64_t id_base, int32_t wait, uint8_t *d_status,
+                                              int32_t *d_remaining, int64_t tick_ts_us, const uint64_t *mask,
+                                              uint64_t *d_keyseq, int64_t *d_request_id,
+                                              int32_t *d_log_remaining, uint64_t capacity, uint32_t *d_count,
+                                              void *stream);
+
 /* Queue of one key, oldest first (Deque enumeration order, DQ:116-125).  A diagnostic call:
  * synchronous, and on an engine with queueing classes it also reads the key's class byte
  * (one more blocking one-byte copy) to know where the key's ring wraps. */
@@ -690,8 +728,8 @@ tbe_status tbe_approx_import_rows(tbe_engine *engine, const uint64_t *ids, const
  *     when it completes); TBE_WAIT_REJECTED nothing (an exception in the reference, not a
  *     lease); each NewestFirst eviction (Q:94-109, A:143-158) -> failed on the evicted
  *     entry's key.
- *   tbe_refresh(_device), the tick of tbe_wait_batch_tick_device, tbe_approx_sync(_stream),
- *     tbe_approx_refresh: each drained grant -> ok on its key.
+ *   tbe_refresh(_device), the tick of tbe_wait_batch_tick_device, their *_classes forms,
+ *     tbe_approx_sync(_stream), tbe_approx_refresh: each drained grant -> ok on its key.
  *   tbe_queue_cancel and a batch skipped as invalid count nothing.
  * The counters are per id: tbe_expired_device(clear != 0) and tbe_approx_reset(_device) zero
  * them for the keys they flag; tbe_set_class*, imports and exports of rows leave them alone.
