@@ -897,6 +897,33 @@ __device__ __forceinline__ int64_t rel_base(const int64_t *__restrict__ ts, cons
     return pack_base(ts, F);
 #endif
 }
+// k_fold_wide's prologue as independent memory operations issued back to back: the slice
+// DMA as soon as the bucket is known; *err, the bucket's bounds, the batch's first timestamp
+// and the prefetch target's bounds in one scalar round trip; every record of a chunk loaded
+// (out-of-range slots at a clamped index) before any is decoded, escaped times afterwards.
+// 0 (the default): the form before -- each of those waited for before the next was issued.
+// The early form compiles as intended (four DMA and three record loads back to back, one
+// wait) but config B's fold was 4-27 us shorter per batch in four paired traces against
+// 4-19 us between two runs of one build, and its wave cycles per wave did not move
+// (profiles/r12_load_order_ab.txt): the fold is not bound by this chain.  Off until a
+// measurement says otherwise.
+#ifndef TBE_FOLD_EARLY_LOADS
+#define TBE_FOLD_EARLY_LOADS 0
+#endif
+#if TBE_FOLD_EARLY_LOADS
+// The three bases from a batch's first timestamp already in a register (k_fold_wide loads
+// ts[0] together with its other scalars).
+__device__ __forceinline__ int64_t pack_base_of(int64_t ts0, const PackFmt &F) { return ts0 - ((int64_t)1 << (F.wb - 1)); }
+__device__ __forceinline__ int64_t rel_base_of(int64_t ts0, const PackFmt &F) {
+#if TBE_REL_BASE
+    (void)F;
+    const int64_t b = ts0 - ((int64_t)1 << 31);
+    return b > 0 ? b : 0;
+#else
+    return pack_base_of(ts0, F);
+#endif
+}
+#endif
 __device__ __forceinline__ uint64_t pack_rec(uint64_t key, int32_t p, int64_t ts, uint64_t idx,
                                              int64_t tbase, const PackFmt &F) {
     const uint64_t pc = (uint64_t)(p < 0 ? 0 : (p > F.pc_max ? F.pc_max : p));
@@ -1012,6 +1039,45 @@ __device__ __forceinline__ void fold_input_fam(uint64_t rec, uint32_t q, const F
             ts = (int64_t)((uint64_t)tbase1 + (rec >> (G.rb + G.pb + 1 + G.pw)));
         }
     }
+}
+// fold_input_fam in two phases (TBE_FOLD_EARLY_LOADS): fold_decode_fam reads no memory -- it
+// decodes every field of a record, the time as if it were not escaped, and returns the
+// record's escape bit; fold_escaped_fam then fetches an escaped record's time.  A kernel can
+// so load all its records, decode them, and visit the escaped ones (rare) afterwards, where
+// fold_input_fam's load inside the branch made every record's load wait for the one before.
+#if TBE_FOLD_EARLY_LOADS
+__device__ __forceinline__ int64_t fold_base_of(int64_t ts0, const FoldFmt &G) { return ts0 - ((int64_t)1 << (G.tw - 1)); }
+#endif
+template <int FAM>
+__device__ __forceinline__ bool fold_decode_fam(uint64_t rec, uint32_t q, const FoldFmt &G, int64_t tbase1,
+                                                int64_t tbase0, const PackFmt &F, uint32_t rmask, uint32_t &row,
+                                                int32_t &p, int64_t &ts, uint32_t &pos) {
+    if (FAM >= 1 || (FAM < 0 && G.on)) {
+        row = (uint32_t)(rec & ((1ull << G.rb) - 1));
+        p = (int32_t)((rec >> G.rb) & ((1ull << G.pb) - 1));
+        pos = (uint32_t)((rec >> (G.rb + G.pb + 1)) & ((1ull << G.pw) - 1));
+        ts = (int64_t)((uint64_t)tbase1 + (rec >> (G.rb + G.pb + 1 + G.pw)));
+        return (rec >> (G.rb + G.pb)) & 1;
+    }
+    row = (uint32_t)(rec & F.kmask) & rmask;
+    p = (int32_t)((rec >> F.kb) & ((1ull << F.pb) - 1));
+    pos = q;
+    ts = (int64_t)((uint64_t)tbase0 + (rec >> (F.kb + F.pb + 1)));
+    return (rec >> (F.kb + F.pb)) & 1;
+}
+// (`ts` is the time fold_decode_fam gave: a plain record's payload is ts - tbase0, so the
+// record itself need not stay in registers.)
+template <int FAM>
+__device__ __forceinline__ int64_t fold_escaped_fam(int64_t ts, uint32_t pos, const FoldFmt &G,
+                                                    const uint64_t *__restrict__ rec0,
+                                                    const int64_t *__restrict__ ts_orig, int64_t tbase0,
+                                                    const PackFmt &F) {
+    if (FAM == 0 || (FAM < 0 && !G.on)) return ts_orig[(uint64_t)ts - (uint64_t)tbase0];
+    if (FAM == 1 || (FAM < 0 && G.n0)) return (int64_t)rec0[pos];   // narrow pass-0 records' side array
+    uint32_t k;
+    int32_t p0;
+    unpack_rec(rec0[pos], ts_orig, tbase0, F, k, p0, ts);
+    return ts;
 }
 
 // Stable partition pass over packed records (see k_scatter; one 8-byte LDS staging
@@ -1339,6 +1405,13 @@ constexpr uint32_t kWideSolo = TBE_WIDE_SOLO ? 64u : 0u;   // pending requests t
 #ifndef TBE_FOLD_PREFETCH_MIN
 #define TBE_FOLD_PREFETCH_MIN 1024           // ... by workgroups whose bucket has this many requests
 #endif
+// k_fold_wide's barrier before the write-back waits for LDS only (the write-back reads the
+// rows and the dirty bitmap from LDS and depends on no global access of this workgroup);
+// 0: __syncthreads(), which also waits for every reply store's acknowledgement and for the
+// prefetch touches.  Measured slower by 0.011 ms per config-B step (three runs each): off.
+#ifndef TBE_FOLD_LDS_BARRIER
+#define TBE_FOLD_LDS_BARRIER 0
+#endif
 #ifndef TBE_WIDE_MIN_SHIFT
 #define TBE_WIDE_MIN_SHIFT 11
 #endif
@@ -1464,16 +1537,51 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
             lds_dma16(rows + (j < nrows ? j : nrows - 1), &row[u * kWideBlock + (tid & ~63)]);
         }
     };
+#if TBE_FOLD_EARLY_LOADS
+    // One scalar round trip: every load below depends on the kernel arguments alone.  The
+    // prefetch target's bounds are read at an in-bounds index (this bucket's) when there is
+    // no target.  The slice DMA, whose addresses need none of them, goes out before they are
+    // waited for, so every exit from here on first waits for it: LDS is not released with
+    // DMA writes in flight.  (An erroring batch has read a slice and writes nothing.)
+#if TBE_FOLD_PREFETCH
+    const uint32_t pf_blk = blockIdx.x + TBE_FOLD_PREFETCH;
+    const uint32_t pf_b = fold_bucket_at(G, pf_blk);
+    const bool pf_ok = pf_blk < gridDim.x && (!G.on || pf_b < G.nb);
+    const uint32_t pf_at = pf_ok ? pf_b : b;
+    const uint32_t pf_s = bstart[pf_at], pf_e = bstart[pf_at + 1];
+#endif
+    const uint32_t err_set = *err;
+    const uint32_t s = bstart[b], e = bstart[b + 1];
+    const int64_t ts0 = PACKED ? ts_orig[0] : 0;
+    slice_dma();
+    // The one wait for those scalar loads, behind the DMA's issue.  Its operands pin every
+    // loaded value here: left alone, the compiler sinks each load to the block of its first
+    // use, behind the branches below, and the round trips line up one after another again.
+#if TBE_FOLD_PREFETCH
+    asm volatile("s_waitcnt lgkmcnt(0)" ::"s"(err_set), "s"(s), "s"(e), "s"(ts0), "s"(pf_s), "s"(pf_e));
+#else
+    asm volatile("s_waitcnt lgkmcnt(0)" ::"s"(err_set), "s"(s), "s"(e), "s"(ts0));
+#endif
+    // Buckets with >= wide_min requests only (k_fold_sparse takes the others): the whole slice
+    // is pulled in (LDS-DMA) and only its dirty lines are written back.
+    if (err_set || s == e || e - s < wide_min) {
+        lds_dma_wait();
+        return;
+    }
+    const int64_t tbase = (PACKED && FAM != 1) ? pack_base_of(ts0, F) : 0;   // (narrow pass-0 records: unused)
+    const int64_t tbase1 = (PACKED && (FAM < 0 ? G.on != 0 : FAM >= 1)) ? fold_base_of(ts0, G) : 0;
+    const TimeBase TB = time_base(PACKED ? rel_base_of(ts0, F) : 0, P.ttl_ms);   // fast request times (req_time_rel)
+#else
     if (*err) return;
     const uint32_t s = bstart[b], e = bstart[b + 1];
     if (s == e) return;
     // Buckets with >= wide_min requests only (k_fold_sparse takes the others): the whole slice
     // is pulled in (LDS-DMA) and only its dirty lines are written back.
     if (e - s < wide_min) return;
-    const bool dense = true;
     const int64_t tbase = (PACKED && FAM != 1) ? pack_base(ts_orig, F) : 0;   // (narrow pass-0 records: unused)
     const int64_t tbase1 = (FAM < 0 ? G.on != 0 : FAM >= 1) ? fold_base(ts_orig, G) : 0;
     const TimeBase TB = time_base(PACKED ? rel_base(ts_orig, F) : 0, P.ttl_ms);   // fast request times (req_time_rel)
+#endif
     const bool count_hot = hot_next != nullptr && (e - s) >= kHotMin;
 
     uint32_t kl[kWidePer];
@@ -1483,6 +1591,45 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
     uint32_t pend = 0;
     auto load_chunk = [&](uint32_t c) {
         pend = 0;
+#if TBE_FOLD_EARLY_LOADS
+        // every load of the chunk first: a slot past the bucket's end reads the bucket's last
+        // request (e > s here) and is discarded
+        uint64_t raw[kWidePer];
+#pragma unroll
+        for (int r = 0; r < kWidePer; ++r) {
+            const uint32_t q = c + r * kWideBlock + tid;
+            const uint32_t qc = q < e ? q : e - 1;
+            if (PACKED) {
+                raw[r] = LD_F(srec + qc);
+            } else {
+                kl[r] = skeys[qc];
+                pm[r] = sperm[qc];
+                tsv[r] = sts[qc];
+            }
+        }
+        uint32_t esc = 0;   // PACKED: slots whose time is escaped (rare)
+#pragma unroll
+        for (int r = 0; r < kWidePer; ++r) {
+            const uint32_t q = c + r * kWideBlock + tid;
+            const bool in = q < e;
+            if (PACKED) {
+                if (fold_decode_fam<FAM>(raw[r], q, G, tbase1, tbase, F, rmask, kl[r], pm[r], tsv[r], pos[r]) && in)
+                    esc |= 1u << r;
+            } else {
+                kl[r] &= rmask;
+            }
+            kl[r] = in ? kl[r] : 0u;
+            pm[r] = in ? pm[r] : 0;
+            tsv[r] = in ? tsv[r] : 0;
+            if (!PACKED || !in) pos[r] = q;
+            pend |= in ? 1u << r : 0u;
+        }
+        if (PACKED && esc) {
+#pragma unroll
+            for (int r = 0; r < kWidePer; ++r)
+                if (esc & (1u << r)) tsv[r] = fold_escaped_fam<FAM>(tsv[r], pos[r], G, rec0, ts_orig, tbase, F);
+        }
+#else
 #pragma unroll
         for (int r = 0; r < kWidePer; ++r) {
             const uint32_t q = c + r * kWideBlock + tid;
@@ -1502,13 +1649,18 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
                 pend |= 1u << r;
             }
         }
+#endif
     };
 
 #if TBE_FOLD_PREFETCH
     uint32_t pf_sink = 0;
 #endif
-    load_chunk(s);   // in flight together with the dense slice
-    if (dense) slice_dma();
+#if TBE_FOLD_EARLY_LOADS
+    load_chunk(s);   // issued behind the slice DMA and in flight together with it
+#else
+    load_chunk(s);   // (each slot's load is waited for before the next, and all before the DMA)
+    slice_dma();
+#endif
     if constexpr (CLS) {
         // R class bytes, four per lane, coalesced (cls is padded to whole buckets); visible
         // after the first chunk's barrier, like the slice
@@ -1551,6 +1703,19 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
         // barrier before this workgroup's write-back.  384 blocks = half of the 768
         // workgroups in flight: config B fold 0.93 -> 0.85 ms; 768 -> 0.90, 1536 -> 0.93
         // (profiles/r04d_ablate_perm0_prefetch.log)
+#if TBE_FOLD_EARLY_LOADS
+        // (The target's bounds came with this bucket's, in the prologue.  One address and one
+        // predicate per lane for both kinds of touch: they do not depend on the chunk, the
+        // compiler keeps them in registers across the rounds, and two addresses spilled.)
+        if (c == s && e - s >= TBE_FOLD_PREFETCH_MIN && pf_ok && pf_e - pf_s >= wide_min && pf_e > pf_s) {
+            const bool trow = tid < (int)(kMaxRows / 8);
+            const uint64_t fr0 = (uint64_t)pf_b << r_bits;
+            const uint32_t dq = (uint32_t)(tid - kMaxRows / 8) * 16u;
+            const void *tp = trow ? (const void *)(table + fr0 + (uint32_t)tid * 8u) : PACKED ? (const void *)(srec + pf_s + dq) : nullptr;
+            if (trow ? (uint64_t)tid * 8u < n_keys - fr0 : PACKED && dq < pf_e - pf_s)
+                pf_sink = *reinterpret_cast<const uint32_t *>(tp);
+        }
+#else
         if (c == s && e - s >= TBE_FOLD_PREFETCH_MIN) {
             const uint32_t fblk = blockIdx.x + TBE_FOLD_PREFETCH;
             const uint32_t fb = fold_bucket_at(G, fblk);
@@ -1567,6 +1732,7 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
                 }
             }
         }
+#endif
 #endif
         if (count_hot) {
 #pragma unroll
@@ -1806,7 +1972,14 @@ __global__ __launch_bounds__(kWideBlock, TBE_WIDE_WAVES) void k_fold_wide(
             if (q < e && (keep & (1u << r))) put_reply(res, pos[r], rep[r], narrow);
         }
     }
+#if TBE_FOLD_LDS_BARRIER
+    // rows and dirty bits settled: LDS writes released, the barrier, LDS reads acquired
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+#else
     __syncthreads();
+#endif
     // dirty lines stream out (non-temporal: 12% faster fold, profiles/r01_v10_ablate.log)
     for (uint32_t j = tid; j < nrows; j += kWideBlock)
         if (row_line_dirty(dirty, j)) ST_S(rows + j, row[j]);
@@ -2201,7 +2374,13 @@ __global__ __launch_bounds__(kPartBlock) void k_unrank(uint64_t n, const uint8_t
 #ifndef TBE_UNPART_RUNS
 #define TBE_UNPART_RUNS 1                    // 0: 4-byte permutation and k_unscatter, as before (A/B)
 #endif
-constexpr int kRunTasks1 = 3 * kPartBlock;   // one-byte replies: dword tasks per tile, rounded up to the block
+// k_unpart_runs with its independent memory operations issued back to back: step 1's loads
+// together, step 3's loads before its LDS writes, and for full tiles step 4 as a straight-line
+// body whose stores do not wait for one another.  0: the form before (A/B).
+#ifndef TBE_UNPART_STRAIGHT
+#define TBE_UNPART_STRAIGHT 1
+#endif
+constexpr int kRunTasks1 = 3 * kPartBlock;  // one-byte replies: dword tasks per tile, rounded up to the block
 static_assert(kTile / 4 + 3 * kDigits / 2 <= kRunTasks1, "every run: its dwords, plus at most 1.5 for its ragged ends");
 template <int W>
 __global__ __launch_bounds__(kPartBlock, 8) void k_unpart_runs(
@@ -2228,13 +2407,51 @@ __global__ __launch_bounds__(kPartBlock, 8) void k_unpart_runs(
     if (sticky && blockIdx.x == 0 && tid == 0 && *err) *sticky = 1u;
     const uint32_t tile = xcd_swizzle(blockIdx.x, gridDim.x);
     const uint64_t base = (uint64_t)tile * kTile;
+#if TBE_UNPART_STRAIGHT
+    // 32-bit (run_batch admits n < 2^32, and base <= n): a scalar minimum.  As a 64-bit minimum
+    // next to the full-tile branch of step 4, hipcc (ROCm 7.2) compiled this to an s_cselect on a
+    // condition code that nothing had set -- its branch peephole had removed the s_and that did --
+    // and a partial tile then stored all 4096 elements, past n (tests: unaligned outputs, and
+    // the guard elements of test_gpu_fold_load_order.py).
+    const int nvalid = (int)min((uint32_t)kTile, (uint32_t)(n - base));
+#else
     const int nvalid = (int)min<uint64_t>(kTile, n - base);
+#endif
     // the tile's indices, 8 per lane (the permutation buffer holds whole tiles: entries past
     // nvalid are read and never used); in flight during the offset loads and the scan, and
     // waited for where they go to LDS, before the runs are loaded
     const u32x4 iv = LD_U(reinterpret_cast<const u32x4 *>(idx + base) + tid);
     // 1. offsets and counts
     uint32_t cnt = 0;
+#if TBE_UNPART_STRAIGHT
+    // the four loads of a digit's thread issued together (tile_offsets' three among them),
+    // where a branch on the tile's place in its block and tile_offsets' scan each waited for
+    // the loads before them
+    uint32_t g = 0;
+    {
+        uint32_t tot = 0, tp = 0, bp = 0, nx = 0;
+        const uint32_t blk = tile / tiles_per_blk;
+        const bool inner = tile + 1 < ntiles && (tile + 1) % tiles_per_blk != 0;
+        if (tid < kDigits) {
+            // the running count after this tile: the next tile's, or at a block's last tile
+            // the next block's prefix (the digit's total at the last block)
+            const uint32_t *nxp = inner              ? tileprefix + (uint64_t)(tile + 1) * kDigits + tid
+                                  : blk + 1 < nblk ? blockprefix + (uint64_t)(blk + 1) * kDigits + tid
+                                                   : digit_total + tid;
+            tot = digit_total[tid];
+            tp = tileprefix[(uint64_t)tile * kDigits + tid];
+            bp = blockprefix[(uint64_t)blk * kDigits + tid];
+            nx = *nxp;
+        }
+        uint32_t all_d;
+        const uint32_t dbase = block_excl_scan<kPartBlock>(tot, wsum, &all_d);
+        if (tid < kDigits) {
+            cnt = inner ? nx - tp : nx - bp - tp;
+            g = dbase + bp + tp;
+            goff[tid] = g;
+        }
+    }
+#else
     if (tid < kDigits) {
         const uint32_t blk = tile / tiles_per_blk;
         const uint32_t tp = tileprefix[(uint64_t)tile * kDigits + tid];
@@ -2248,6 +2465,7 @@ __global__ __launch_bounds__(kPartBlock, 8) void k_unpart_runs(
     }
     tile_offsets<kPartBlock>(tile, tiles_per_blk, tileprefix, blockprefix, digit_total, goff, wsum);
     const uint32_t g = tid < kDigits ? goff[tid] : 0u;   // (this thread's own store)
+#endif
     // tasks of this digit's run: its replies, or the aligned dwords they lie in
     const uint32_t ntask = W == 1 ? (cnt ? ((g & 3u) + cnt + 3u) >> 2 : 0u) : cnt;
     // one scan for both: counts sum to at most kTile (low half), tasks to at most kTasks
@@ -2296,6 +2514,40 @@ __global__ __launch_bounds__(kPartBlock, 8) void k_unpart_runs(
     }
     __syncthreads();
     // 3. the runs, in staged order
+#if TBE_UNPART_STRAIGHT
+    // every task's load first: a thread past the last task repeats the last task's load (an
+    // in-bounds address, the value unused), so that no load sits in a branch and is waited for
+    // before the next one issues
+    {
+        uint32_t v[kPer], td[kPer], tt[kPer];
+        const uint32_t klast = ntasks ? ntasks - 1u : 0u;
+#pragma unroll
+        for (int it = 0; it < kPer; ++it) {
+            const uint32_t k = min((uint32_t)(it * kPartBlock + tid), klast);
+            td[it] = tdig[k];
+            tt[it] = k - tst[td[it]];
+            const uint32_t gd = goff[td[it]];
+            v[it] = res_in[W == 1 ? (gd >> 2) + tt[it] : gd + tt[it]];
+        }
+#pragma unroll
+        for (int it = 0; it < kPer; ++it) {
+            const uint32_t k = (uint32_t)(it * kPartBlock + tid);
+            if (k >= ntasks) continue;
+            if constexpr (W == 1) {
+                const uint32_t gd = goff[td[it]];
+                const uint32_t a = (gd & ~3u) + 4u * tt[it];
+                const uint32_t c = rcnt[td[it]], s = lst[td[it]];
+#pragma unroll
+                for (uint32_t bb = 0; bb < 4; ++bb) {
+                    const uint32_t p = a + bb - gd;   // (wraps below the run's start)
+                    if (p < c) reply[s + p] = (uint8_t)(v[it] >> (8 * bb));
+                }
+            } else {
+                reply[k] = v[it];                     // (tasks are staged replies: k = lst[d] + t)
+            }
+        }
+    }
+#else
 #pragma unroll
     for (int it = 0; it < kPer; ++it) {
         const uint32_t k = (uint32_t)(it * kPartBlock + tid);
@@ -2316,8 +2568,34 @@ __global__ __launch_bounds__(kPartBlock, 8) void k_unpart_runs(
             reply[k] = res_in[gd + t];            // (tasks are staged replies: k = lst[d] + t)
         }
     }
+#endif
     __syncthreads();
     // 4. arrival order
+#if TBE_UNPART_STRAIGHT
+    // A full tile: indices, then replies, then the sixteen stores, straight-line.  In the
+    // masked loop below every element's branch holds its LDS reads and its stores, and the
+    // compiler waits for the stores before (vmcnt counts a store until it is acknowledged)
+    // ahead of the next element's reads: eight serialized write round trips per wave.
+    if (nvalid == kTile) {
+        uint32_t r[kPartItems];
+#pragma unroll
+        for (int it = 0; it < kPartItems; ++it) r[it] = lidx[it * kPartBlock + tid] & (kTile - 1);
+#pragma unroll
+        for (int it = 0; it < kPartItems; ++it) r[it] = reply[r[it]];
+#pragma unroll
+        for (int it = 0; it < kPartItems; ++it) {
+            const uint64_t i = base + (uint64_t)(it * kPartBlock + tid);
+            if (W == 1) {
+                ST_U(granted + i, (uint8_t)(r[it] >> 7));
+                ST_U(remaining + i, (int32_t)(r[it] & 0x7Fu));
+            } else {
+                ST_U(granted + i, (uint8_t)(r[it] >> 31));
+                ST_U(remaining + i, (int32_t)(r[it] & 0x7FFFFFFFu));
+            }
+        }
+        return;
+    }
+#endif
 #pragma unroll
     for (int it = 0; it < kPartItems; ++it) {
         const int e = it * kPartBlock + tid;

@@ -286,6 +286,15 @@ VARIANT_SETS = {
         "runs0_u": (["TBE_UNPART_RUNS=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
         "load16_u": (["TBE_HIST_LOAD16=1"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
     },
+    "load_order": {   # independent memory operations back to back: the un-partition (on), the fold's prologue and LDS-only barrier (off) (run with --plain)
+        "base_u": ([], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "before_u": (["TBE_UNPART_STRAIGHT=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "early_u": (["TBE_FOLD_EARLY_LOADS=1"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "earlyonly_u": (["TBE_FOLD_EARLY_LOADS=1", "TBE_UNPART_STRAIGHT=0"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "earlylds_u": (["TBE_FOLD_EARLY_LOADS=1", "TBE_FOLD_LDS_BARRIER=1"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "earlypf192_u": (["TBE_FOLD_EARLY_LOADS=1", "TBE_FOLD_PREFETCH=192"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+        "earlypf768_u": (["TBE_FOLD_EARLY_LOADS=1", "TBE_FOLD_PREFETCH=768"], ["--workload", "uniform", "--steps", "20", "--warmup", "5"]),
+    },
     "unpart_z": {
         "base_z": ([], ["--workload", "zipf", "--steps", "20", "--warmup", "5"]),
         "runs0_z": (["TBE_UNPART_RUNS=0"], ["--workload", "zipf", "--steps", "20", "--warmup", "5"]),
