@@ -5314,6 +5314,444 @@ FoldFmt batch_fold_fmt(const tbe_engine *e, uint64_t n) {
     return G;
 }
 
+// ---- launch helpers.  Every kernel with more than one instantiation has one launch_* function
+// that holds its argument list; the stage functions below only say which template arguments go
+// with which condition.  Arguments that a kernel defaults are passed with the default's value.
+template <int V>
+using I_ = std::integral_constant<int, V>;
+
+// Calls f(I_<W>) for the first listed reply width W that equals rw, for the last one otherwise.
+template <int W, int... Ws, typename F>
+void with_width(int rw, F &&f) {
+    if constexpr (sizeof...(Ws) == 0) f(I_<W>{});
+    else if (rw == W) f(I_<W>{});
+    else with_width<Ws...>(rw, f);
+}
+
+// A log capacity as the 32-bit count the kernels take.
+inline uint32_t cap32(uint64_t cap) { return (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFu); }
+inline uint32_t ev_cap32(const tbe_engine *e) { return cap32(e->ev_cap); }
+
+// What the launches of one batch depend on: run_batch computes it once, the stages read it.
+struct Batch {
+    tbe_engine *e;
+    Workspace &w;
+    const uint64_t *keys;
+    const int32_t *permits;
+    const int64_t *ts;
+    uint64_t n;
+    uint8_t *granted;
+    int32_t *remaining;
+    int64_t *retry;              // approximate kind: RetryAfter per request, or NULL
+    int64_t id_base;
+    uint32_t ai_base;
+    hipStream_t sp, sf;          // partition passes and bucket starts; fold, hot runs, un-partition
+    bool pipe;                   // sp and sf differ (token bucket)
+    uint32_t ntiles, nblk, tpb;  // tiles_for(n)
+    bool approx, wait;           // the kind; wait: status-packed replies (queueing and approximate)
+    bool unrank;                 // final un-partition by k_unrank: pass 0 stores no permutation
+    // the final un-partition through staged digit runs (k_unpart_runs), pass 0 writing 2-byte
+    // tile-local indices: the token-bucket kind with packed records and a stored permutation
+    bool runs;
+    int rw;                      // reply width in bytes: 1 (narrow), 2 (medium) or 4
+    FoldFmt G;                   // this batch's fold records (batch_fold_fmt)
+    PackFmt pf;                  // e->pf with this batch's n0
+    const uint64_t *rec0;        // token bucket, queueing: where the folds find pass-0 records or times
+    unsigned fold_grid;
+    // token bucket: a sparse batch's dense buckets are listed for k_fold_wide, the rest go to
+    // one wave each (k_fold_sparse)
+    uint32_t tb_wmin;
+    bool sparse_tb;
+    HotSet *hot, *hot_next;      // this batch's hot set and the one it nominates into, or NULL
+    ClsView cls;
+    QClsView qcls;
+    AClsView acls;
+    const PassBufs &sorted() const { return w.pass[e->passes - 1]; }
+};
+
+template <typename KeyT, bool HOT = false>
+void launch_hist(const Batch &b, int p, const KeyT *src) {
+    tbe_engine *e = b.e;
+    Workspace &w = b.w;
+    // the last pass also counts requests per bucket (k_bscan turns them into bstart)
+    k_hist<KeyT, HOT><<<b.nblk, kHBlock, 0, b.sp>>>(
+        src, b.n, e->r_bits + kDigitBits * p, b.tpb, b.ntiles, w.pass[p].tileprefix, w.blocksum, e->cfg.n_keys,
+        w.err, p == 0 ? 1 : 0, e->packed ? e->pf.kmask : ~0ull, HOT ? b.hot : nullptr, e->nbuckets, e->r_bits,
+        p == e->passes - 1 ? w.bcount : nullptr, kDigitBits * p, e->nb_total,
+        (p == 0 && b.unrank) ? w.dig0 : nullptr);
+}
+
+// One pass over wide records {key, permits, ts, idx}; pass 0 (KeyIn: the caller's 8-byte keys)
+// validates.
+template <typename KeyIn, bool IDX, bool TS = true>
+void launch_scatter(const Batch &b, int p, const KeyIn *kin) {
+    constexpr bool first = std::is_same_v<KeyIn, uint64_t>;
+    Workspace &w = b.w;
+    const PassBufs &out = w.pass[p];
+    const PassBufs &in = w.pass[first ? 0 : p - 1];   // (unused by pass 0)
+    k_scatter<KeyIn, IDX, TS><<<b.ntiles, kPartBlock, 0, b.sp>>>(
+        kin, first ? b.permits : in.permits, !TS ? nullptr : first ? b.ts : in.ts,
+        (IDX && !first) ? in.idx : nullptr, b.n, b.e->r_bits + kDigitBits * p, out.tileprefix, out.blockprefix,
+        out.digit_total, b.tpb, out.keys, out.permits, TS ? out.ts : nullptr, IDX ? out.idx : nullptr, out.perm,
+        w.err, first ? 1 : 0);
+}
+
+// One pass over packed records.  FIRST reads the caller's columns (and writes the digit stream
+// and the escaped times of narrow records), LAST writes this batch's fold records from the
+// caller's timestamps, a pass that is neither moves e->pf records and a permutation.
+template <bool FIRST, bool HOT = false, bool IDX = false, bool NOTS = false, bool LAST = false, int FAM = -1,
+          bool P16 = false>
+void launch_scatter_rec(const Batch &b, int p) {
+    tbe_engine *e = b.e;
+    Workspace &w = b.w;
+    const PassBufs &out = w.pass[p];
+    const PassBufs &in = w.pass[FIRST ? 0 : p - 1];   // (unused by pass 0)
+    const bool timed_last = LAST && !b.approx;        // (the approximate kind's records carry no time)
+    k_scatter_rec<FIRST, HOT, IDX, NOTS, LAST, FAM, P16><<<b.ntiles, kPartBlock, 0, b.sp>>>(
+        FIRST ? b.keys : nullptr, FIRST ? b.permits : nullptr, ((FIRST && !NOTS) || timed_last) ? b.ts : nullptr,
+        FIRST ? nullptr : in.rec, b.n, e->r_bits + kDigitBits * p, (FIRST || LAST) ? b.pf : e->pf, out.tileprefix,
+        out.blockprefix, out.digit_total, b.tpb, out.rec, (LAST || (FIRST && b.unrank)) ? nullptr : out.perm, w.err,
+        HOT ? b.hot : nullptr, HOT ? e->nbuckets : 0u, HOT ? e->r_bits : 0, (IDX && !FIRST) ? in.idx : nullptr,
+        IDX ? out.idx : nullptr, LAST ? b.G : FoldFmt{}, (FIRST && e->dig1) ? w.dig1 : nullptr,
+        LAST ? w.dig1 : nullptr, (FIRST && !NOTS) ? w.ts0 : nullptr,
+        timed_last ? pass1_codec(b.pf, b.G, true) : Pass1Codec{});
+}
+
+// Pass p's scatter: which k_scatter / k_scatter_rec instantiation the kind, the pass and the
+// batch's record formats select.
+void scatter_pass(const Batch &b, int p) {
+    tbe_engine *e = b.e;
+    const bool first = p == 0, last = b.G.on && p == e->passes - 1;   // last: writes fold records
+    if (!e->packed) {
+        const PassBufs &in = b.w.pass[first ? 0 : p - 1];
+        if (b.approx && first) launch_scatter<uint64_t, true, false>(b, p, b.keys);
+        else if (b.approx) launch_scatter<uint32_t, true, false>(b, p, in.keys);
+        else if (first && !b.wait) launch_scatter<uint64_t, false>(b, p, b.keys);
+        else if (first) launch_scatter<uint64_t, true>(b, p, b.keys);
+        else if (!b.wait) launch_scatter<uint32_t, false>(b, p, in.keys);
+        else launch_scatter<uint32_t, true>(b, p, in.keys);
+    } else if (b.approx) {   //                    FIRST  HOT    IDX    NOTS   LAST
+        if (first) launch_scatter_rec<true, false, false, true>(b, p);
+        else if (last) launch_scatter_rec<false, false, false, false, true>(b, p);
+        else launch_scatter_rec<false>(b, p);
+    } else if (b.wait) {
+        if (first) launch_scatter_rec<true, false, true>(b, p);
+        else if (last) launch_scatter_rec<false, false, true, false, true, -1>(b, p);   // (FAM 1 would need scratch)
+        else launch_scatter_rec<false, false, true>(b, p);
+    } else if (first) {      //                                   FIRST  HOT    IDX    NOTS   LAST  FAM P16
+        if (b.hot && b.runs) launch_scatter_rec<true, true, false, false, false, -1, true>(b, p);
+        else if (b.runs) launch_scatter_rec<true, false, false, false, false, -1, true>(b, p);
+        else if (b.hot) launch_scatter_rec<true, true>(b, p);
+        else launch_scatter_rec<true>(b, p);
+    } else if (last) {       // per record family (k_scatter_rec's FAM)
+        if (TBE_PASS1_CODEC && b.G.n0 && pass1_codec_ok(b.pf, b.G))
+            launch_scatter_rec<false, false, false, false, true, 1>(b, p);
+        else if (TBE_PASS1_CODEC && !b.G.n0) launch_scatter_rec<false, false, false, false, true, 0>(b, p);
+        else launch_scatter_rec<false, false, false, false, true, -1>(b, p);
+    } else {
+        launch_scatter_rec<false>(b, p);
+    }
+}
+
+// Stage: the partition passes (histogram, column scan, scatter per 8-bit digit), on sp.
+tbe_status stage_partition(const Batch &b) {
+    tbe_engine *e = b.e;
+    Workspace &w = b.w;
+    // every batch: its dominant keys join its own hot set (k_hot_sample)
+    if (b.hot && b.n >= kHotSampleMin)
+        k_hot_sample<<<1, 1024, 0, b.sp>>>(b.keys, b.n, e->cfg.n_keys, b.hot, e->hot_cap);
+    for (int p = 0; p < e->passes; ++p) {
+        PassBufs &out = w.pass[p];
+        stage_begin(e, ST_HIST, b.sp);
+        if (p == 0 && b.hot) launch_hist<uint64_t, true>(b, p, b.keys);
+        else if (p == 0) launch_hist<uint64_t>(b, p, b.keys);
+        else if (e->dig1 && p == 1)   // pass 1's digits, written by pass 0's scatter
+            k_hist_dig<<<b.nblk, kHBlock, 0, b.sp>>>(w.dig1, b.n, b.tpb, b.ntiles, out.tileprefix, w.blocksum,
+                                                     w.pass[0].digit_total, p == e->passes - 1 ? w.bcount : nullptr,
+                                                     e->nb_total);
+        else if (e->packed) launch_hist<uint64_t>(b, p, w.pass[p - 1].rec);
+        else launch_hist<uint32_t>(b, p, w.pass[p - 1].keys);
+        stage_end(e, ST_HIST, b.sp);
+        stage_begin(e, ST_COLSCAN, b.sp);
+        k_colscan<<<kDigits, kBlock, 0, b.sp>>>(w.blocksum, b.nblk, out.blockprefix, out.digit_total);
+        stage_end(e, ST_COLSCAN, b.sp);
+        stage_begin(e, ST_SCATTER, b.sp);
+        scatter_pass(b, p);
+        stage_end(e, ST_SCATTER, b.sp);
+    }
+    return TBE_OK;
+}
+
+// Stage: the bucket starts from the last pass's bucket counts, on sp.
+tbe_status stage_bounds(const Batch &b) {
+    tbe_engine *e = b.e;
+    Workspace &w = b.w;
+    stage_begin(e, ST_BOUNDS, b.sp);
+    const uint32_t bs_blocks = (e->nb_total + kBsTile - 1) / kBsTile;
+    if (TBE_BSCAN_LB && bs_blocks <= kBsMaxBlocks) {
+        // a fresh tag per launch on these flags, taken here (ADVICE r05): a batch that
+        // failed between its launch and the end of run_batch cannot hand its tag on
+        if (++w.bs_tag == 0) {   // 2^32 launches: back to the zeroed state
+            HIP_TRY(e, hipMemsetAsync(w.bsflags, 0, kBsMaxBlocks * sizeof(unsigned long long), b.sp));
+            w.bs_tag = 1;
+        }
+        k_bscan_lb<<<bs_blocks, 1024, 0, b.sp>>>(w.bcount, e->nb_total, w.bstart, w.bsflags, w.bs_tag, e->nbuckets,
+                                                 b.tb_wmin, b.sparse_tb ? w.dlist : nullptr);
+    } else if (b.sparse_tb) {
+        k_bscan<<<1, 1024, 0, b.sp>>>(w.bcount, e->nb_total, w.bstart, e->nbuckets, b.tb_wmin, w.dlist);
+    } else {
+        k_bscan<<<1, 1024, 0, b.sp>>>(w.bcount, e->nb_total, w.bstart);
+    }
+    stage_end(e, ST_BOUNDS, b.sp);
+    return TBE_OK;
+}
+
+// The folds take their requests as packed records (PACKED: srec, and the caller's timestamps
+// where the kind has them) or as the wide columns; the other form's pointers are NULL.
+template <bool PACKED, bool RETRY = false, bool CLS = false>
+void launch_fold_a(const Batch &b, const AParams &a, const uint64_t *rec0) {
+    tbe_engine *e = b.e;
+    Workspace &w = b.w;
+    const PassBufs &s = b.sorted();
+    std::conditional_t<CLS, AClsView, NoACls> cv{};
+    if constexpr (CLS) cv = b.acls;
+    k_fold_a<PACKED, RETRY, CLS><<<PACKED ? b.fold_grid : e->nbuckets, kFoldBlock, 0, b.sf>>>(
+        PACKED ? nullptr : s.keys, PACKED ? nullptr : s.permits, PACKED ? nullptr : s.idx, PACKED ? s.rec : nullptr,
+        e->pf, w.bstart, e->r_bits, e->cfg.n_keys, e->alocal, e->ring, a, w.res[0], e->ev_cause, e->ev_id,
+        e->counters, ev_cap32(e), w.err, e->wait_rw(), b.G, rec0, RETRY ? e->aclient : nullptr,
+        RETRY ? w.def[0] : nullptr, cv);
+}
+
+// mask: none, or the QClsBits of a masked fused tick (classed engines)
+template <bool PACKED, bool CLS = false, typename HW, typename... MK>
+void launch_fold_q(const Batch &b, const QParams &q, HW *qh, MK... mask) {
+    tbe_engine *e = b.e;
+    Workspace &w = b.w;
+    const PassBufs &s = b.sorted();
+    std::conditional_t<CLS, QClsView, NoQCls> qc{};
+    if constexpr (CLS) qc = b.qcls;
+    k_fold_q<PACKED, HW, CLS, MK...><<<PACKED ? b.fold_grid : e->nbuckets, kQBlock, 0, b.sf>>>(
+        PACKED ? nullptr : s.keys, PACKED ? nullptr : s.permits, PACKED ? nullptr : s.ts, s.idx,
+        PACKED ? s.rec : nullptr, PACKED ? b.ts : nullptr, e->pf, w.bstart, e->r_bits, e->cfg.n_keys, e->table, qh,
+        e->ring, e->params, q, w.res[0], e->ev_cause, e->ev_id, e->counters, ev_cap32(e), w.err, e->wait_rw(),
+        e->qtick, b.G, b.rec0, qc, mask...);
+}
+
+// dlist: a sparse batch's dense buckets (grid: their most), or NULL: every bucket
+template <bool PACKED, int FAM = -1, bool CLS = false>
+void launch_fold_wide(const Batch &b, unsigned grid, const uint32_t *dlist) {
+    tbe_engine *e = b.e;
+    Workspace &w = b.w;
+    const PassBufs &s = b.sorted();
+    k_fold_wide<PACKED, FAM, CLS><<<grid, kWideBlock, 0, b.sf>>>(
+        PACKED ? nullptr : s.keys, PACKED ? nullptr : s.permits, PACKED ? nullptr : s.ts, PACKED ? s.rec : nullptr,
+        PACKED ? b.ts : nullptr, e->pf, w.bstart, e->r_bits, e->cfg.n_keys, e->table, e->params, w.res[0], w.err,
+        PACKED ? b.hot_next : nullptr, (PACKED && e->narrow) ? 1u : 0u, b.tb_wmin, b.G, b.rec0, dlist,
+        CLS ? b.cls : ClsView{nullptr, nullptr});
+}
+
+// the packed wide fold, per record family (k_fold_wide's FAM, fold_input_fam)
+void launch_fold_wide_packed(const Batch &b, unsigned grid, const uint32_t *dlist) {
+    if (!TBE_FOLD_FAM) launch_fold_wide<true, -1>(b, grid, dlist);
+    else if (!b.G.on) launch_fold_wide<true, 0>(b, grid, dlist);
+    else if (b.G.n0) launch_fold_wide<true, 1>(b, grid, dlist);
+    else launch_fold_wide<true, 2>(b, grid, dlist);
+}
+
+// walk: the bucket ids the waves stride over
+template <bool PACKED, bool CLS = false>
+void launch_fold_sparse(const Batch &b, unsigned grid, uint32_t walk) {
+    tbe_engine *e = b.e;
+    Workspace &w = b.w;
+    const PassBufs &s = b.sorted();
+    k_fold_sparse<PACKED, CLS><<<grid, kSpBlock, 0, b.sf>>>(
+        PACKED ? nullptr : s.keys, PACKED ? nullptr : s.permits, PACKED ? nullptr : s.ts, PACKED ? s.rec : nullptr,
+        PACKED ? b.ts : nullptr, e->pf, w.bstart, e->r_bits, e->cfg.n_keys, e->table, e->params, w.res[0], w.err,
+        (PACKED && e->narrow) ? 1u : 0u, b.tb_wmin, b.G, b.rec0, walk, CLS ? b.cls : ClsView{nullptr, nullptr});
+}
+
+// Stage: the fold, the kind's decisions bucket by bucket, on sf.
+// (hot_next->n_cand was reset by the k_hot_update that consumed its last nominations.)
+tbe_status stage_fold(const Batch &b) {
+    tbe_engine *e = b.e;
+    stage_begin(e, ST_FOLD, b.sf);
+    if (b.approx) {
+        AParams a = e->ap;
+        a.id_base = b.id_base;
+        a.wait = e->wait_mode;
+        a.ai_base = b.ai_base;
+        // Approximate engines allocate no ts0: with narrow pass-0 records (G.n0) there is nothing
+        // for k_fold_a's arrival() to read through rec0.  Only a batch that can queue reads an
+        // arrival index, and batch_fold_fmt gives such a batch no narrow records.
+        if (b.G.n0 && a.wait)
+            return fail(e, TBE_EINVAL, "approximate wait batch with narrow pass-0 records");
+        const uint64_t *rec0 = (b.G.on && !b.G.n0) ? b.w.pass[e->passes - 2].rec : nullptr;
+        const bool retry = b.retry != nullptr;   //          PACKED RETRY  CLS
+        if (e->acls_par && retry) launch_fold_a<false, true, true>(b, a, rec0);   // classes: wide records
+        else if (e->acls_par) launch_fold_a<false, false, true>(b, a, rec0);
+        else if (retry && e->packed) launch_fold_a<true, true>(b, a, rec0);
+        else if (retry) launch_fold_a<false, true>(b, a, rec0);
+        else if (e->packed) launch_fold_a<true>(b, a, rec0);
+        else launch_fold_a<false>(b, a, rec0);
+    } else if (b.wait) {
+        QParams q = e->qp;
+        q.id_base = b.id_base;
+        q.wait = e->wait_mode;
+        q.ai_base = b.ai_base;
+        with_qhdr(e, [&](auto *qh) {   //                         PACKED CLS
+            if (e->packed) launch_fold_q<true>(b, q, qh);
+            else if (e->qcls_par && e->qtick_mask) launch_fold_q<false, true>(b, q, qh, qcls_bits(e->qtick_mask));
+            else if (e->qcls_par) launch_fold_q<false, true>(b, q, qh);
+            else launch_fold_q<false>(b, q, qh);
+        });
+    } else if (b.sparse_tb) {
+        // sparse batch: at most n / wmin buckets are dense (k_bscan listed them); one wave per
+        // other bucket
+        const unsigned dgrid = (unsigned)std::min<uint64_t>(e->nbuckets, b.n / b.tb_wmin + 1);
+        const uint32_t walk = e->packed ? b.fold_grid : e->nbuckets;
+        const unsigned sgrid = (unsigned)std::min<uint64_t>((walk + kSpWaves - 1) / kSpWaves, 2048);
+        if (e->packed) {
+            launch_fold_wide_packed(b, dgrid, b.w.dlist);
+            launch_fold_sparse<true>(b, sgrid, walk);
+        } else if (e->cls) {
+            launch_fold_wide<false, -1, true>(b, dgrid, b.w.dlist);
+            launch_fold_sparse<false, true>(b, sgrid, walk);
+        } else {
+            launch_fold_wide<false>(b, dgrid, b.w.dlist);
+            launch_fold_sparse<false>(b, sgrid, walk);
+        }
+    } else if (e->packed) {   // a dense batch: k_fold_wide takes every bucket
+        launch_fold_wide_packed(b, b.fold_grid, nullptr);
+    } else if (e->cls) {
+        launch_fold_wide<false, -1, true>(b, e->nbuckets, nullptr);
+    } else {
+        launch_fold_wide<false>(b, e->nbuckets, nullptr);
+    }
+    stage_end(e, ST_FOLD, b.sf);
+    return TBE_OK;
+}
+
+// Stage: runs of this batch's hot keys, after the fold (which may write back a hot key's
+// unchanged row as part of its bucket's slice), then the hot set of batch b+2.
+tbe_status stage_hot(const Batch &b) {
+    tbe_engine *e = b.e;
+    Workspace &w = b.w;
+    const PassBufs &s = b.sorted();
+    const uint32_t narrow = e->narrow ? 1u : 0u;
+    const uint32_t keep = e->hot_cap - hot_reserve_host(e->hot_cap);
+    stage_begin(e, ST_HOT, b.sf);
+    const unsigned sgrid = (unsigned)std::min<uint64_t>(1024, b.n / kSeg + e->hot_cap);
+    // (the summary kernel also scans the run lengths into the runs' first segments)
+    k_hot_summary<true><<<sgrid, kSegBlock, 0, b.sf>>>(s.rec, b.ts, e->pf, w.bstart, e->nbuckets, w.segbase, w.summ,
+                                                       w.err, b.G, b.rec0, b.hot, e->table, e->params, w.res[0],
+                                                       narrow, 1u);
+    k_hot_chain<<<e->hot_cap, kSegBlock, 0, b.sf>>>(s.rec, b.ts, e->pf, w.bstart, e->nbuckets, b.hot, b.hot_next,
+                                                    w.segbase, w.summ, w.sst, e->table, e->params, w.res[0], w.err,
+                                                    narrow, b.G, b.rec0, 1u);
+    k_hot_replies<<<sgrid, kSegBlock, 0, b.sf>>>(s.rec, b.ts, e->pf, w.bstart, e->nbuckets, w.segbase, w.sst,
+                                                 e->params, w.res[0], w.err, narrow, b.G, b.rec0);
+    if (b.pipe) {
+        // The next-but-one batch's hot set, on a stream of its own beside this batch's
+        // un-partition; batch b+2 (same workspace) waits for it before its partition.
+        HIP_TRY(e, hipEventRecord(e->ev_hot, b.sf));
+        HIP_TRY(e, hipStreamWaitEvent(e->hstream, e->ev_hot, 0));
+        k_hot_update<<<1, 1024, 0, e->hstream>>>(b.hot_next, keep, w.err);
+        HIP_TRY(e, hipEventRecord(w.hot_done, e->hstream));
+        w.hot_pending = true;
+    } else {
+        k_hot_update<<<1, 1024, 0, b.sf>>>(b.hot_next, keep, w.err);
+    }
+    stage_end(e, ST_HOT, b.sf);
+    return TBE_OK;
+}
+
+// Pass p's gather from w.res[cur] (and, RETRY, w.def[cur]): into the other buffer, or FINAL
+// (p == 0) into the caller's arrays, with the batch's sticky error (k_sticky's work).
+// CLS: RetryAfter at the rate of the key's class.
+template <bool FINAL, bool WAIT, int W, bool RETRY = false, bool CLS = false>
+void launch_unscatter(const Batch &b, int p, int cur) {
+    tbe_engine *e = b.e;
+    Workspace &w = b.w;
+    std::conditional_t<CLS, RetryCls, NoRetryCls> rc{};
+    if constexpr (CLS) rc = RetryCls{e->cls, e->acls_rate, b.keys, e->cfg.n_keys};
+    k_unscatter<FINAL, WAIT, W, RETRY, CLS><<<(unsigned)((b.n + kUnTile - 1) / kUnTile), kUnBlock, 0, b.sf>>>(
+        b.n, w.pass[p].perm, w.res[cur], FINAL ? nullptr : w.res[cur ^ 1], FINAL ? b.granted : nullptr,
+        FINAL ? b.remaining : nullptr, FINAL ? w.err : nullptr, FINAL ? e->sticky : nullptr,
+        RETRY ? w.def[cur] : nullptr, (RETRY && !FINAL) ? w.def[cur ^ 1] : nullptr,
+        (RETRY && FINAL) ? b.retry : nullptr, (RETRY && FINAL && !CLS) ? e->ap.decay_rate : 0.0, rc);
+}
+
+template <int W, bool WAIT = false, bool RETRY = false>
+void launch_unrank(const Batch &b, int cur) {
+    Workspace &w = b.w;
+    k_unrank<W, WAIT, RETRY><<<b.ntiles, kPartBlock, 0, b.sf>>>(
+        b.n, w.dig0, w.pass[0].tileprefix, w.pass[0].blockprefix, w.pass[0].digit_total, b.tpb, w.res[cur],
+        b.granted, b.remaining, RETRY ? w.def[cur] : nullptr, RETRY ? b.retry : nullptr,
+        RETRY ? b.e->ap.decay_rate : 0.0);
+}
+
+template <int W>
+void launch_unpart_runs(const Batch &b, int cur) {
+    Workspace &w = b.w;
+    k_unpart_runs<W><<<b.ntiles, kPartBlock, 0, b.sf>>>(
+        b.n, reinterpret_cast<const uint16_t *>(w.pass[0].perm), w.pass[0].tileprefix, w.pass[0].blockprefix,
+        w.pass[0].digit_total, b.tpb, b.ntiles, b.nblk, w.res[cur], b.granted, b.remaining, w.err, b.e->sticky);
+}
+
+// Stage: the replies back into arrival order, pass by pass, on sf.  Which widths each form is
+// instantiated for: the token bucket has no two-byte replies, the approximate kind (RETRY
+// included) no one-byte ones.
+tbe_status stage_unpartition(const Batch &b) {
+    tbe_engine *e = b.e;
+    const bool retry = b.retry != nullptr;
+    stage_begin(e, ST_UNSCATTER, b.sf);
+    int cur = 0;
+    // with fold records the replies are already in pass passes-2's output order
+    for (int p = e->passes - (b.G.on ? 2 : 1); p >= 1; --p) {
+        if (retry) with_width<2, 4>(b.rw, [&](auto W) { launch_unscatter<false, false, W, true>(b, p, cur); });
+        else with_width<1, 2, 4>(b.rw, [&](auto W) { launch_unscatter<false, false, W>(b, p, cur); });
+        cur ^= 1;
+    }
+    if (retry && b.unrank)
+        with_width<2, 4>(b.rw, [&](auto W) { launch_unrank<W, true, true>(b, cur); });
+    else if (retry && e->acls_par)
+        with_width<2, 4>(b.rw, [&](auto W) { launch_unscatter<true, true, W, true, true>(b, 0, cur); });
+    else if (retry)
+        with_width<2, 4>(b.rw, [&](auto W) { launch_unscatter<true, true, W, true>(b, 0, cur); });
+    else if (b.runs)
+        with_width<1, 4>(b.rw, [&](auto W) { launch_unpart_runs<W>(b, cur); });
+    else if (b.unrank && !b.wait)
+        with_width<1, 4>(b.rw, [&](auto W) { launch_unrank<W>(b, cur); });
+    else if (b.unrank)
+        with_width<1, 2, 4>(b.rw, [&](auto W) { launch_unrank<W, true>(b, cur); });
+    else if (b.wait)
+        with_width<1, 2, 4>(b.rw, [&](auto W) { launch_unscatter<true, true, W>(b, 0, cur); });
+    else
+        with_width<1, 4>(b.rw, [&](auto W) { launch_unscatter<true, false, W>(b, 0, cur); });
+    stage_end(e, ST_UNSCATTER, b.sf);
+    if (b.unrank) k_sticky<<<1, 64, 0, b.sf>>>(b.w.err, e->sticky);   // (otherwise the final unscatter did it)
+    return TBE_OK;
+}
+
+// Lease statistics: behind the batch's last reply-writing kernel and before the events that
+// release the caller's stream and this workspace (the kernels read the caller's keys, the
+// final reply bytes and w.err).  chunk: one chunk of a chunked host batch.
+void batch_stats(const Batch &b, bool chunk) {
+    tbe_engine *e = b.e;
+    Workspace &w = b.w;
+    const unsigned sgrid = (unsigned)std::min<uint64_t>((b.n + kStatsTile - 1) / kStatsTile, kStatsMaxBlocks);
+    k_stats_batch<<<sgrid, kStatsBlock, 0, b.sf>>>(b.keys, b.granted, b.n, w.err, e->stats_view());
+    // NewestFirst evictions fail the evicted lease.  A chunk leaves them to its caller: the log
+    // runs on over the chunks.
+    const int32_t order = b.approx ? (int32_t)e->a_newest : (int32_t)e->q_newest;   // (some class evicts)
+    if (b.wait && e->wait_mode == 1 && order == 1 && !chunk && e->ev_cause)
+        k_stats_log<<<64, kStatsBlock, 0, b.sf>>>(e->counters, ev_cap32(e), e->ev_cause, b.keys, b.n, b.ai_base,
+                                                  nullptr, e->cfg.n_keys, w.err, e->st_failed, e->st_tot + 1);
+    if (e->qtick.ts >= 0 && e->qtick.count)  // the fused tick's grants (tbe_wait_batch_tick_device)
+        k_stats_log<<<64, kStatsBlock, 0, b.sf>>>(e->qtick.count, e->qtick.cap, nullptr, nullptr, 0, 0,
+                                                  e->qtick.keyseq, e->cfg.n_keys, w.err, e->st_ok, e->st_tot);
+}
+
 // Enqueue the whole pipeline for one device-resident batch.  `caller` is the stream the
 // inputs were produced on and the replies are awaited on; NULL: the inputs are complete
 // at the call and the replies are ordered on the engine's stream.
@@ -5328,7 +5766,7 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
                      hipStream_t caller, int64_t id_base = 0, hipEvent_t in_ready = nullptr,
                      hipStream_t out_stream = nullptr, uint32_t ai_base = 0, int64_t *retry = nullptr) {
     const bool approx = e->cfg.kind == TBE_KIND_APPROXIMATE;
-    const bool wait = e->cfg.kind != TBE_KIND_TOKEN_BUCKET;   // status-packed replies
+    const bool wait = e->cfg.kind != TBE_KIND_TOKEN_BUCKET;
     if (n == 0) return TBE_OK;
     if (n >= (1ull << 32)) return fail(e, TBE_EINVAL, "batch of %llu requests exceeds 2^32-1",
                                        (unsigned long long)n);
@@ -5337,13 +5775,12 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
     Workspace &w = e->ws[pipe ? e->ws_cur : 0];
     tbe_status rc = ensure_workspace(e, w, n);
     if (rc != TBE_OK) return rc;
+    const FoldFmt G = batch_fold_fmt(e, n);
     if (retry) {   // (approximate kind) the deficit side arrays, as large as the replies'
         if (!w.def[0]) HIP_TRY(e, hipMalloc(&w.def[0], w.cap_n * sizeof(uint32_t)));
-        if (!w.def[1] && e->passes - (batch_fold_fmt(e, n).on ? 2 : 1) >= 1)
+        if (!w.def[1] && e->passes - (G.on ? 2 : 1) >= 1)
             HIP_TRY(e, hipMalloc(&w.def[1], w.cap_n * sizeof(uint32_t)));
     }
-    uint32_t ntiles, nblk, tpb;
-    tiles_for(n, ntiles, nblk, tpb);
     hipStream_t sf = caller ? caller : e->stream, sp = sf;
     if (pipe) {
         sf = e->stream;
@@ -5365,457 +5802,46 @@ tbe_status run_batch(tbe_engine *e, const uint64_t *keys, const int32_t *permits
         w.bs_fresh = false;
     }
 
-    const uint64_t kmask = e->packed ? e->pf.kmask : ~0ull;
-    const FoldFmt G = batch_fold_fmt(e, n);
+    Batch b{e, w, keys, permits, ts, n, granted, remaining, retry, id_base, ai_base, sp, sf, pipe};
+    tiles_for(n, b.ntiles, b.nblk, b.tpb);
+    b.approx = approx;
+    b.wait = wait;
+    b.unrank = e->unrank;
+    b.runs = TBE_UNPART_RUNS && e->packed && !approx && !wait && !b.unrank && !retry;
+    b.rw = e->narrow ? 1 : (e->medium ? 2 : 4);
+    b.G = G;
     // narrow pass-0 records only with this batch's fold records; the folds then find an
-    // escaped request's time in ts0 (FoldFmt::n0)
-    PackFmt pf = e->pf;
-    pf.n0 = G.n0;
-    const uint64_t *rec0 = G.on ? (G.n0 ? reinterpret_cast<const uint64_t *>(w.ts0) : w.pass[e->passes - 2].rec)
-                                : nullptr;
-    const bool unrank = e->unrank;
-    // the final un-partition through staged digit runs (k_unpart_runs), pass 0 writing 2-byte
-    // tile-local indices: the token-bucket kind with packed records and a stored permutation
-    const bool runs = TBE_UNPART_RUNS && e->packed && !approx && !wait && !unrank && !retry;
-    const unsigned fold_grid = G.on ? (unsigned)((1ull << G.region_bits) * G.n_hi) : e->nbuckets;
-    // token bucket: a sparse batch's dense buckets are listed for k_fold_wide, the rest go to
-    // one wave each (k_fold_sparse)
-    const uint32_t tb_wmin = (!approx && !wait) ? fold_wide_min(e, n) : 1u;
-    const bool sparse_tb = tb_wmin > 1u;
+    // escaped request's time in ts0 (FoldFmt::n0).  (The approximate fold: see stage_fold.)
+    b.pf = e->pf;
+    b.pf.n0 = G.n0;
+    b.rec0 = (G.on && !approx) ? (G.n0 ? reinterpret_cast<const uint64_t *>(w.ts0) : w.pass[e->passes - 2].rec)
+                               : nullptr;
+    b.fold_grid = G.on ? (unsigned)((1ull << G.region_bits) * G.n_hi) : e->nbuckets;
+    b.tb_wmin = (!approx && !wait) ? fold_wide_min(e, n) : 1u;
+    b.sparse_tb = b.tb_wmin > 1u;
     // hot runs: see tbe_engine::hot.  Not in a sparse batch below 2^20 requests (the
     // micro-batch regime): there a key busy enough to matter fills one dense bucket, which
     // k_fold_wide takes whole, and the hot machinery (the sampler, four launches) costs more
     // than it saves -- uniform 2^18: 0.10 ms per batch without, Zipf 2^20: 0.44 with against
     // 0.68 without (profiles/r05q_ablate_hot_sparse.log).  Which keys are hot never changes
     // a decision; the hot sets keep their contents for the next batch that runs them.
-    const bool hot_on = e->hot_cap && !(sparse_tb && n < (1ull << TBE_HOT_SPARSE_MIN_LOG2));
-    HotSet *hot = hot_on ? e->hot[e->nbatch % 3] : nullptr;
-    HotSet *hot_next = hot_on ? e->hot[(e->nbatch + 2) % 3] : nullptr;
-    // every batch: its dominant keys join its own hot set (k_hot_sample)
-    if (hot && n >= kHotSampleMin) k_hot_sample<<<1, 1024, 0, sp>>>(keys, n, e->cfg.n_keys, hot, e->hot_cap);
-    for (int p = 0; p < e->passes; ++p) {
-        const int shift = e->r_bits + kDigitBits * p;
-        PassBufs &out = w.pass[p];
-        stage_begin(e, ST_HIST, sp);
-        // the last pass also counts requests per bucket (k_bscan turns them into bstart)
-        uint32_t *bc = (p == e->passes - 1) ? w.bcount : nullptr;
-        const int lowbits = kDigitBits * p;
-        uint8_t *dig = (p == 0 && unrank) ? w.dig0 : nullptr;
-        uint8_t *dnext = (p == 0 && e->dig1) ? w.dig1 : nullptr;   // pass 1's digits (k_hist_dig)
-        if (p == 0 && hot)
-            k_hist<uint64_t, true><<<nblk, kHBlock, 0, sp>>>(keys, n, shift, tpb, ntiles, out.tileprefix,
-                                                             w.blocksum, e->cfg.n_keys, w.err, 1, kmask,
-                                                             hot, e->nbuckets, e->r_bits, bc, lowbits,
-                                                             e->nb_total, dig);
-        else if (p == 0)
-            k_hist<uint64_t><<<nblk, kHBlock, 0, sp>>>(keys, n, shift, tpb, ntiles, out.tileprefix,
-                                                       w.blocksum, e->cfg.n_keys, w.err, 1, kmask,
-                                                       nullptr, e->nbuckets, e->r_bits, bc, lowbits,
-                                                       e->nb_total, dig);
-        else if (e->dig1 && p == 1)
-            k_hist_dig<<<nblk, kHBlock, 0, sp>>>(w.dig1, n, tpb, ntiles, out.tileprefix, w.blocksum,
-                                                 w.pass[0].digit_total, bc, e->nb_total);
-        else if (e->packed)
-            k_hist<uint64_t><<<nblk, kHBlock, 0, sp>>>(w.pass[p - 1].rec, n, shift, tpb, ntiles,
-                                                       out.tileprefix, w.blocksum, e->cfg.n_keys,
-                                                       w.err, 0, kmask, nullptr, e->nbuckets,
-                                                       e->r_bits, bc, lowbits, e->nb_total);
-        else
-            k_hist<uint32_t><<<nblk, kHBlock, 0, sp>>>(w.pass[p - 1].keys, n, shift, tpb, ntiles,
-                                                       out.tileprefix, w.blocksum, e->cfg.n_keys,
-                                                       w.err, 0, kmask, nullptr, e->nbuckets,
-                                                       e->r_bits, bc, lowbits, e->nb_total);
-        stage_end(e, ST_HIST, sp);
-        stage_begin(e, ST_COLSCAN, sp);
-        k_colscan<<<kDigits, kBlock, 0, sp>>>(w.blocksum, nblk, out.blockprefix, out.digit_total);
-        stage_end(e, ST_COLSCAN, sp);
-        stage_begin(e, ST_SCATTER, sp);
-        // the last pass of a batch with timestamps, per record family (k_scatter_rec's FAM)
-#define LAUNCH_LAST_FAM(IDXK, FAMK, iin_, iout_)                                                               \
-    k_scatter_rec<false, false, IDXK, false, true, FAMK><<<ntiles, kPartBlock, 0, sp>>>(                       \
-        nullptr, nullptr, ts, w.pass[p - 1].rec, n, shift, pf, out.tileprefix, out.blockprefix,                \
-        out.digit_total, tpb, out.rec, nullptr, w.err, nullptr, 0, 0, iin_, iout_, G, nullptr, w.dig1, nullptr, \
-        pass1_codec(pf, G, true))
-#define LAUNCH_LAST(IDXK, iin_, iout_)                                                     \
-    do {                                                                                   \
-        if (TBE_PASS1_CODEC && G.n0 && pass1_codec_ok(pf, G))                              \
-            LAUNCH_LAST_FAM(IDXK, 1, iin_, iout_);                                         \
-        else if (TBE_PASS1_CODEC && !G.n0)                                                 \
-            LAUNCH_LAST_FAM(IDXK, 0, iin_, iout_);                                         \
-        else                                                                               \
-            LAUNCH_LAST_FAM(IDXK, -1, iin_, iout_);                                        \
-    } while (0)
-        if (e->packed && approx && p == 0)
-            k_scatter_rec<true, false, false, true><<<ntiles, kPartBlock, 0, sp>>>(
-                keys, permits, nullptr, nullptr, n, shift, pf, out.tileprefix, out.blockprefix,
-                out.digit_total, tpb, out.rec, unrank ? nullptr : out.perm, w.err, nullptr, 0, 0, nullptr,
-                nullptr, FoldFmt{}, dnext);
-        else if (e->packed && approx && G.on && p == e->passes - 1)
-            k_scatter_rec<false, false, false, false, true><<<ntiles, kPartBlock, 0, sp>>>(
-                nullptr, nullptr, nullptr, w.pass[p - 1].rec, n, shift, pf, out.tileprefix,
-                out.blockprefix, out.digit_total, tpb, out.rec, nullptr, w.err, nullptr, 0, 0, nullptr,
-                nullptr, G, nullptr, w.dig1);
-        else if (e->packed && approx)
-            k_scatter_rec<false><<<ntiles, kPartBlock, 0, sp>>>(
-                nullptr, nullptr, nullptr, w.pass[p - 1].rec, n, shift, e->pf, out.tileprefix,
-                out.blockprefix, out.digit_total, tpb, out.rec, out.perm, w.err);
-        else if (e->packed && wait && p == 0)
-            k_scatter_rec<true, false, true><<<ntiles, kPartBlock, 0, sp>>>(
-                keys, permits, ts, nullptr, n, shift, pf, out.tileprefix, out.blockprefix,
-                out.digit_total, tpb, out.rec, unrank ? nullptr : out.perm, w.err, nullptr, 0, 0, nullptr, out.idx,
-                FoldFmt{}, dnext, nullptr, w.ts0);
-        else if (e->packed && wait && G.on && p == e->passes - 1)
-            LAUNCH_LAST_FAM(true, -1, w.pass[p - 1].idx, out.idx);   // (queueing kind: FAM 1 would need scratch)
-        else if (e->packed && wait)
-            k_scatter_rec<false, false, true><<<ntiles, kPartBlock, 0, sp>>>(
-                nullptr, nullptr, nullptr, w.pass[p - 1].rec, n, shift, e->pf, out.tileprefix,
-                out.blockprefix, out.digit_total, tpb, out.rec, out.perm, w.err, nullptr, 0, 0,
-                w.pass[p - 1].idx, out.idx);
-        else if (e->packed && p == 0 && hot && runs)
-            k_scatter_rec<true, true, false, false, false, -1, true><<<ntiles, kPartBlock, 0, sp>>>(
-                keys, permits, ts, nullptr, n, shift, pf, out.tileprefix, out.blockprefix,
-                out.digit_total, tpb, out.rec, out.perm, w.err, hot, e->nbuckets, e->r_bits,
-                nullptr, nullptr, FoldFmt{}, dnext, nullptr, w.ts0);
-        else if (e->packed && p == 0 && runs)
-            k_scatter_rec<true, false, false, false, false, -1, true><<<ntiles, kPartBlock, 0, sp>>>(
-                keys, permits, ts, nullptr, n, shift, pf, out.tileprefix, out.blockprefix,
-                out.digit_total, tpb, out.rec, out.perm, w.err, nullptr, 0, 0, nullptr,
-                nullptr, FoldFmt{}, dnext, nullptr, w.ts0);
-        else if (e->packed && p == 0 && hot)
-            k_scatter_rec<true, true><<<ntiles, kPartBlock, 0, sp>>>(
-                keys, permits, ts, nullptr, n, shift, pf, out.tileprefix, out.blockprefix,
-                out.digit_total, tpb, out.rec, unrank ? nullptr : out.perm, w.err, hot, e->nbuckets, e->r_bits,
-                nullptr, nullptr, FoldFmt{}, dnext, nullptr, w.ts0);
-        else if (e->packed && p == 0)
-            k_scatter_rec<true><<<ntiles, kPartBlock, 0, sp>>>(
-                keys, permits, ts, nullptr, n, shift, pf, out.tileprefix, out.blockprefix,
-                out.digit_total, tpb, out.rec, unrank ? nullptr : out.perm, w.err, nullptr, 0, 0, nullptr,
-                nullptr, FoldFmt{}, dnext, nullptr, w.ts0);
-        else if (e->packed && G.on && p == e->passes - 1)
-            LAUNCH_LAST(false, nullptr, nullptr);
-        else if (e->packed)
-            k_scatter_rec<false><<<ntiles, kPartBlock, 0, sp>>>(
-                nullptr, nullptr, nullptr, w.pass[p - 1].rec, n, shift, e->pf, out.tileprefix,
-                out.blockprefix, out.digit_total, tpb, out.rec, out.perm, w.err);
-        else if (approx && p == 0)
-            k_scatter<uint64_t, true, false><<<ntiles, kPartBlock, 0, sp>>>(
-                keys, permits, nullptr, nullptr, n, shift, out.tileprefix, out.blockprefix,
-                out.digit_total, tpb, out.keys, out.permits, nullptr, out.idx, out.perm, w.err, 1);
-        else if (approx)
-            k_scatter<uint32_t, true, false><<<ntiles, kPartBlock, 0, sp>>>(
-                w.pass[p - 1].keys, w.pass[p - 1].permits, nullptr, w.pass[p - 1].idx, n, shift,
-                out.tileprefix, out.blockprefix, out.digit_total, tpb, out.keys, out.permits, nullptr,
-                out.idx, out.perm, w.err, 0);
-        else if (p == 0 && !wait)
-            k_scatter<uint64_t, false><<<ntiles, kPartBlock, 0, sp>>>(
-                keys, permits, ts, nullptr, n, shift, out.tileprefix, out.blockprefix,
-                out.digit_total, tpb, out.keys, out.permits, out.ts, nullptr, out.perm, w.err, 1);
-        else if (p == 0)
-            k_scatter<uint64_t, true><<<ntiles, kPartBlock, 0, sp>>>(
-                keys, permits, ts, nullptr, n, shift, out.tileprefix, out.blockprefix,
-                out.digit_total, tpb, out.keys, out.permits, out.ts, out.idx, out.perm, w.err, 1);
-        else if (!wait)
-            k_scatter<uint32_t, false><<<ntiles, kPartBlock, 0, sp>>>(
-                w.pass[p - 1].keys, w.pass[p - 1].permits, w.pass[p - 1].ts, nullptr, n, shift,
-                out.tileprefix, out.blockprefix, out.digit_total, tpb, out.keys, out.permits,
-                out.ts, nullptr, out.perm, w.err, 0);
-        else
-            k_scatter<uint32_t, true><<<ntiles, kPartBlock, 0, sp>>>(
-                w.pass[p - 1].keys, w.pass[p - 1].permits, w.pass[p - 1].ts, w.pass[p - 1].idx,
-                n, shift, out.tileprefix, out.blockprefix, out.digit_total, tpb, out.keys,
-                out.permits, out.ts, out.idx, out.perm, w.err, 0);
-        stage_end(e, ST_SCATTER, sp);
-    }
-    const PassBufs &sorted = w.pass[e->passes - 1];
-    stage_begin(e, ST_BOUNDS, sp);
-    const uint32_t bs_blocks = (e->nb_total + kBsTile - 1) / kBsTile;
-    if (TBE_BSCAN_LB && bs_blocks <= kBsMaxBlocks) {
-        // a fresh tag per launch on these flags, taken here (ADVICE r05): a batch that
-        // failed between its launch and the end of run_batch cannot hand its tag on
-        if (++w.bs_tag == 0) {   // 2^32 launches: back to the zeroed state
-            HIP_TRY(e, hipMemsetAsync(w.bsflags, 0, kBsMaxBlocks * sizeof(unsigned long long), sp));
-            w.bs_tag = 1;
-        }
-        k_bscan_lb<<<bs_blocks, 1024, 0, sp>>>(w.bcount, e->nb_total, w.bstart, w.bsflags, w.bs_tag,
-                                               e->nbuckets, tb_wmin, sparse_tb ? w.dlist : nullptr);
-    }
-    else if (sparse_tb)
-        k_bscan<<<1, 1024, 0, sp>>>(w.bcount, e->nb_total, w.bstart, e->nbuckets, tb_wmin, w.dlist);
-    else
-        k_bscan<<<1, 1024, 0, sp>>>(w.bcount, e->nb_total, w.bstart);
-    stage_end(e, ST_BOUNDS, sp);
+    const bool hot_on = e->hot_cap && !(b.sparse_tb && n < (1ull << TBE_HOT_SPARSE_MIN_LOG2));
+    b.hot = hot_on ? e->hot[e->nbatch % 3] : nullptr;
+    b.hot_next = hot_on ? e->hot[(e->nbatch + 2) % 3] : nullptr;
+    b.cls = e->cls_view();
+    b.qcls = e->qcls_view();
+    b.acls = e->acls_view();
+
+    if ((rc = stage_partition(b)) != TBE_OK) return rc;
+    if ((rc = stage_bounds(b)) != TBE_OK) return rc;
     if (pipe) {
         HIP_TRY(e, hipEventRecord(e->ev_part, sp));
         HIP_TRY(e, hipStreamWaitEvent(sf, e->ev_part, 0));
     }
-    // hot_next->n_cand was reset by the k_hot_update that consumed its last nominations
-    // the packed wide fold, per record family (k_fold_wide's FAM, fold_input_fam)
-#define LAUNCH_WIDE_FAM(FAMK, grid_, dlist_)                                                              \
-    k_fold_wide<true, FAMK><<<grid_, kWideBlock, 0, sf>>>(                                                \
-        nullptr, nullptr, nullptr, sorted.rec, ts, e->pf, w.bstart, e->r_bits, e->cfg.n_keys, e->table,   \
-        e->params, w.res[0], w.err, hot_next, e->narrow ? 1u : 0u, tb_wmin, G, rec0, dlist_)
-#define LAUNCH_WIDE(grid_, dlist_)                      \
-    do {                                                \
-        if (!TBE_FOLD_FAM)                              \
-            LAUNCH_WIDE_FAM(-1, grid_, dlist_);         \
-        else if (!G.on)                                 \
-            LAUNCH_WIDE_FAM(0, grid_, dlist_);          \
-        else if (G.n0)                                  \
-            LAUNCH_WIDE_FAM(1, grid_, dlist_);          \
-        else                                            \
-            LAUNCH_WIDE_FAM(2, grid_, dlist_);          \
-    } while (0)
-    stage_begin(e, ST_FOLD, sf);
-    if (approx) {
-        AParams a = e->ap;
-        a.id_base = id_base;
-        a.wait = e->wait_mode;
-        a.ai_base = ai_base;
-        if (e->acls_par && retry)   // a classed engine moves wide records (create_engine)
-            k_fold_a<false, true, true><<<e->nbuckets, kFoldBlock, 0, sf>>>(
-                sorted.keys, sorted.permits, sorted.idx, nullptr, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
-                e->alocal, e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
-                (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(), G, rec0, e->aclient,
-                w.def[0], e->acls_view());
-        else if (e->acls_par)
-            k_fold_a<false, false, true><<<e->nbuckets, kFoldBlock, 0, sf>>>(
-                sorted.keys, sorted.permits, sorted.idx, nullptr, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
-                e->alocal, e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
-                (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(), G, rec0, nullptr,
-                nullptr, e->acls_view());
-        else if (retry && e->packed)
-            k_fold_a<true, true><<<fold_grid, kFoldBlock, 0, sf>>>(
-                nullptr, nullptr, nullptr, sorted.rec, e->pf, w.bstart, e->r_bits, e->cfg.n_keys, e->alocal,
-                e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
-                (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(), G, rec0, e->aclient,
-                w.def[0]);
-        else if (retry)
-            k_fold_a<false, true><<<e->nbuckets, kFoldBlock, 0, sf>>>(
-                sorted.keys, sorted.permits, sorted.idx, nullptr, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
-                e->alocal, e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
-                (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(), G, rec0, e->aclient,
-                w.def[0]);
-        else if (e->packed)
-            k_fold_a<true><<<fold_grid, kFoldBlock, 0, sf>>>(
-                nullptr, nullptr, nullptr, sorted.rec, e->pf, w.bstart, e->r_bits, e->cfg.n_keys, e->alocal,
-                e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
-                (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(), G, rec0);
-        else
-            k_fold_a<false><<<e->nbuckets, kFoldBlock, 0, sf>>>(
-                sorted.keys, sorted.permits, sorted.idx, nullptr, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
-                e->alocal, e->ring, a, w.res[0], e->ev_cause, e->ev_id, e->counters,
-                (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(), G, rec0);
-    } else if (wait) {
-        QParams q = e->qp;
-        q.id_base = id_base;
-        q.wait = e->wait_mode;
-        q.ai_base = ai_base;
-        with_qhdr(e, [&](auto *qh) {
-            using HW = std::remove_pointer_t<decltype(qh)>;
-            if (e->packed)
-                k_fold_q<true, HW><<<fold_grid, kQBlock, 0, sf>>>(
-                    nullptr, nullptr, nullptr, sorted.idx, sorted.rec, ts, e->pf, w.bstart, e->r_bits,
-                    e->cfg.n_keys, e->table, qh, e->ring, e->params, q, w.res[0], e->ev_cause, e->ev_id,
-                    e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err, e->wait_rw(),
-                    e->qtick, G, rec0);
-            else if (e->qcls_par && e->qtick_mask)
-                k_fold_q<false, HW, true, QClsBits><<<e->nbuckets, kQBlock, 0, sf>>>(
-                    sorted.keys, sorted.permits, sorted.ts, sorted.idx, nullptr, nullptr, e->pf, w.bstart,
-                    e->r_bits, e->cfg.n_keys, e->table, qh, e->ring, e->params, q, w.res[0], e->ev_cause,
-                    e->ev_id, e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err,
-                    e->wait_rw(), e->qtick, G, rec0, e->qcls_view(), qcls_bits(e->qtick_mask));
-            else if (e->qcls_par)
-                k_fold_q<false, HW, true><<<e->nbuckets, kQBlock, 0, sf>>>(
-                    sorted.keys, sorted.permits, sorted.ts, sorted.idx, nullptr, nullptr, e->pf, w.bstart,
-                    e->r_bits, e->cfg.n_keys, e->table, qh, e->ring, e->params, q, w.res[0], e->ev_cause,
-                    e->ev_id, e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err,
-                    e->wait_rw(), e->qtick, G, rec0, e->qcls_view());
-            else
-                k_fold_q<false, HW><<<e->nbuckets, kQBlock, 0, sf>>>(
-                    sorted.keys, sorted.permits, sorted.ts, sorted.idx, nullptr, nullptr, e->pf, w.bstart,
-                    e->r_bits, e->cfg.n_keys, e->table, qh, e->ring, e->params, q, w.res[0], e->ev_cause,
-                    e->ev_id, e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu), w.err,
-                    e->wait_rw(), e->qtick, G, rec0);
-        });
-    } else if (sparse_tb) {
-        // sparse batch: at most n / wmin buckets are dense (k_bscan listed them); one wave per
-        // other bucket
-        const unsigned dgrid = (unsigned)std::min<uint64_t>(e->nbuckets, n / tb_wmin + 1);
-        const uint32_t walk = e->packed ? fold_grid : e->nbuckets;
-        const unsigned sgrid = (unsigned)std::min<uint64_t>((walk + kSpWaves - 1) / kSpWaves, 2048);
-        if (e->packed) {
-            LAUNCH_WIDE(dgrid, w.dlist);
-            k_fold_sparse<true><<<sgrid, kSpBlock, 0, sf>>>(
-                nullptr, nullptr, nullptr, sorted.rec, ts, e->pf, w.bstart, e->r_bits, e->cfg.n_keys,
-                e->table, e->params, w.res[0], w.err, e->narrow ? 1u : 0u, tb_wmin, G, rec0, walk);
-        } else if (e->cls) {
-            k_fold_wide<false, -1, true><<<dgrid, kWideBlock, 0, sf>>>(
-                sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,
-                e->cfg.n_keys, e->table, e->params, w.res[0], w.err, nullptr, 0u, tb_wmin, G, rec0, w.dlist,
-                e->cls_view());
-            k_fold_sparse<false, true><<<sgrid, kSpBlock, 0, sf>>>(
-                sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,
-                e->cfg.n_keys, e->table, e->params, w.res[0], w.err, 0u, tb_wmin, G, rec0, walk, e->cls_view());
-        } else {
-            k_fold_wide<false><<<dgrid, kWideBlock, 0, sf>>>(
-                sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,
-                e->cfg.n_keys, e->table, e->params, w.res[0], w.err, nullptr, 0u, tb_wmin, G, rec0, w.dlist);
-            k_fold_sparse<false><<<sgrid, kSpBlock, 0, sf>>>(
-                sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,
-                e->cfg.n_keys, e->table, e->params, w.res[0], w.err, 0u, tb_wmin, G, rec0, walk);
-        }
-    } else if (e->packed) {   // a dense batch: k_fold_wide takes every bucket
-        LAUNCH_WIDE(fold_grid, nullptr);
-    } else if (e->cls) {
-        k_fold_wide<false, -1, true><<<e->nbuckets, kWideBlock, 0, sf>>>(
-            sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,
-            e->cfg.n_keys, e->table, e->params, w.res[0], w.err, nullptr, 0u, tb_wmin, G, rec0, nullptr,
-            e->cls_view());
-    } else {
-        k_fold_wide<false><<<e->nbuckets, kWideBlock, 0, sf>>>(
-            sorted.keys, sorted.permits, sorted.ts, nullptr, nullptr, e->pf, w.bstart, e->r_bits,
-            e->cfg.n_keys, e->table, e->params, w.res[0], w.err, nullptr, 0u, tb_wmin, G, rec0);
-    }
-    stage_end(e, ST_FOLD, sf);
-    if (hot) {
-        // runs of this batch's hot keys, after the fold (which may write back a hot key's
-        // unchanged row as part of its bucket's slice), then the hot set of batch b+2
-        stage_begin(e, ST_HOT, sf);
-        const unsigned sgrid = (unsigned)std::min<uint64_t>(1024, n / kSeg + e->hot_cap);
-        // (the summary kernel also scans the run lengths into the runs' first segments)
-        k_hot_summary<true><<<sgrid, kSegBlock, 0, sf>>>(sorted.rec, ts, e->pf, w.bstart, e->nbuckets,
-                                                             w.segbase, w.summ, w.err, G, rec0, hot, e->table,
-                                                             e->params, w.res[0], e->narrow ? 1u : 0u, 1u);
-        k_hot_chain<<<e->hot_cap, kSegBlock, 0, sf>>>(sorted.rec, ts, e->pf, w.bstart, e->nbuckets, hot,
-                                                      hot_next, w.segbase, w.summ, w.sst, e->table,
-                                                      e->params, w.res[0], w.err, e->narrow ? 1u : 0u, G, rec0,
-                                                      1u);
-        k_hot_replies<<<sgrid, kSegBlock, 0, sf>>>(sorted.rec, ts, e->pf, w.bstart, e->nbuckets,
-                                                   w.segbase, w.sst, e->params, w.res[0], w.err, e->narrow ? 1u : 0u,
-                                                   G, rec0);
-        if (pipe) {
-            // The next-but-one batch's hot set, on a stream of its own beside this batch's
-            // un-partition; batch b+2 (same workspace) waits for it before its partition.
-            HIP_TRY(e, hipEventRecord(e->ev_hot, sf));
-            HIP_TRY(e, hipStreamWaitEvent(e->hstream, e->ev_hot, 0));
-            k_hot_update<<<1, 1024, 0, e->hstream>>>(hot_next, e->hot_cap - hot_reserve_host(e->hot_cap), w.err);
-            HIP_TRY(e, hipEventRecord(w.hot_done, e->hstream));
-            w.hot_pending = true;
-        } else {
-            k_hot_update<<<1, 1024, 0, sf>>>(hot_next, e->hot_cap - hot_reserve_host(e->hot_cap), w.err);
-        }
-        stage_end(e, ST_HOT, sf);
-    }
-    stage_begin(e, ST_UNSCATTER, sf);
-    const unsigned untiles = (unsigned)((n + kUnTile - 1) / kUnTile);
-    int cur = 0;
-    // with fold records the replies are already in pass passes-2's output order
-    for (int p = e->passes - (G.on ? 2 : 1); p >= 1; --p) {
-        if (retry && e->medium)
-            k_unscatter<false, false, 2, true><<<untiles, kUnBlock, 0, sf>>>(
-                n, w.pass[p].perm, w.res[cur], w.res[cur ^ 1], nullptr, nullptr, nullptr, nullptr, w.def[cur],
-                w.def[cur ^ 1]);
-        else if (retry)
-            k_unscatter<false, false, 4, true><<<untiles, kUnBlock, 0, sf>>>(
-                n, w.pass[p].perm, w.res[cur], w.res[cur ^ 1], nullptr, nullptr, nullptr, nullptr, w.def[cur],
-                w.def[cur ^ 1]);
-        else if (e->narrow && !approx)
-            k_unscatter<false, false, 1><<<untiles, kUnBlock, 0, sf>>>(n, w.pass[p].perm, w.res[cur],
-                                                                   w.res[cur ^ 1], nullptr, nullptr);
-        else if (e->medium)
-            k_unscatter<false, false, 2><<<untiles, kUnBlock, 0, sf>>>(n, w.pass[p].perm, w.res[cur],
-                                                                   w.res[cur ^ 1], nullptr, nullptr);
-        else
-            k_unscatter<false, false><<<untiles, kUnBlock, 0, sf>>>(n, w.pass[p].perm, w.res[cur],
-                                                                    w.res[cur ^ 1], nullptr, nullptr);
-        cur ^= 1;
-    }
-#define TBE_UNRANK(...)                                                                             \
-    __VA_ARGS__<<<ntiles, kPartBlock, 0, sf>>>(n, w.dig0, w.pass[0].tileprefix, w.pass[0].blockprefix, \
-                                               w.pass[0].digit_total, tpb, w.res[cur], granted, remaining)
-    // (the approximate kind has no one-byte replies: its RETRY forms are the 2- and 4-byte ones)
-    if (retry && unrank && e->medium)
-        k_unrank<2, true, true><<<ntiles, kPartBlock, 0, sf>>>(
-            n, w.dig0, w.pass[0].tileprefix, w.pass[0].blockprefix, w.pass[0].digit_total, tpb, w.res[cur],
-            granted, remaining, w.def[cur], retry, e->ap.decay_rate);
-    else if (retry && unrank)
-        k_unrank<4, true, true><<<ntiles, kPartBlock, 0, sf>>>(
-            n, w.dig0, w.pass[0].tileprefix, w.pass[0].blockprefix, w.pass[0].digit_total, tpb, w.res[cur],
-            granted, remaining, w.def[cur], retry, e->ap.decay_rate);
-    else if (retry && e->acls_par && e->medium)
-        k_unscatter<true, true, 2, true, true><<<untiles, kUnBlock, 0, sf>>>(
-            n, w.pass[0].perm, w.res[cur], nullptr, granted, remaining, w.err, e->sticky, w.def[cur], nullptr,
-            retry, 0.0, RetryCls{e->cls, e->acls_rate, keys, e->cfg.n_keys});
-    else if (retry && e->acls_par)
-        k_unscatter<true, true, 4, true, true><<<untiles, kUnBlock, 0, sf>>>(
-            n, w.pass[0].perm, w.res[cur], nullptr, granted, remaining, w.err, e->sticky, w.def[cur], nullptr,
-            retry, 0.0, RetryCls{e->cls, e->acls_rate, keys, e->cfg.n_keys});
-    else if (retry && e->medium)
-        k_unscatter<true, true, 2, true><<<untiles, kUnBlock, 0, sf>>>(
-            n, w.pass[0].perm, w.res[cur], nullptr, granted, remaining, w.err, e->sticky, w.def[cur], nullptr,
-            retry, e->ap.decay_rate);
-    else if (retry)
-        k_unscatter<true, true, 4, true><<<untiles, kUnBlock, 0, sf>>>(
-            n, w.pass[0].perm, w.res[cur], nullptr, granted, remaining, w.err, e->sticky, w.def[cur], nullptr,
-            retry, e->ap.decay_rate);
-    else if (runs && e->narrow)
-        k_unpart_runs<1><<<ntiles, kPartBlock, 0, sf>>>(
-            n, reinterpret_cast<const uint16_t *>(w.pass[0].perm), w.pass[0].tileprefix, w.pass[0].blockprefix,
-            w.pass[0].digit_total, tpb, ntiles, nblk, w.res[cur], granted, remaining, w.err, e->sticky);
-    else if (runs)
-        k_unpart_runs<4><<<ntiles, kPartBlock, 0, sf>>>(
-            n, reinterpret_cast<const uint16_t *>(w.pass[0].perm), w.pass[0].tileprefix, w.pass[0].blockprefix,
-            w.pass[0].digit_total, tpb, ntiles, nblk, w.res[cur], granted, remaining, w.err, e->sticky);
-    else if (unrank && !wait && e->narrow)
-        TBE_UNRANK(k_unrank<1>);
-    else if (unrank && !wait)
-        TBE_UNRANK(k_unrank<4>);
-    else if (unrank && e->narrow)
-        TBE_UNRANK(k_unrank<1, true>);
-    else if (unrank && e->medium)
-        TBE_UNRANK(k_unrank<2, true>);
-    else if (unrank)
-        TBE_UNRANK(k_unrank<4, true>);
-#undef TBE_UNRANK
-    else if (e->narrow && !wait && !approx)
-        k_unscatter<true, false, 1><<<untiles, kUnBlock, 0, sf>>>(n, w.pass[0].perm, w.res[cur],
-                                                                  nullptr, granted, remaining,
-            w.err, e->sticky);
-    else if (wait && e->narrow)
-        k_unscatter<true, true, 1><<<untiles, kUnBlock, 0, sf>>>(n, w.pass[0].perm, w.res[cur],
-                                                                 nullptr, granted, remaining,
-            w.err, e->sticky);
-    else if (wait && e->medium)
-        k_unscatter<true, true, 2><<<untiles, kUnBlock, 0, sf>>>(n, w.pass[0].perm, w.res[cur],
-                                                                 nullptr, granted, remaining,
-            w.err, e->sticky);
-    else if (wait)
-        k_unscatter<true, true><<<untiles, kUnBlock, 0, sf>>>(n, w.pass[0].perm, w.res[cur],
-                                                              nullptr, granted, remaining,
-            w.err, e->sticky);
-    else
-        k_unscatter<true, false><<<untiles, kUnBlock, 0, sf>>>(n, w.pass[0].perm, w.res[cur],
-                                                               nullptr, granted, remaining,
-            w.err, e->sticky);
-    stage_end(e, ST_UNSCATTER, sf);
-    if (unrank) k_sticky<<<1, 64, 0, sf>>>(w.err, e->sticky);   // (otherwise the final unscatter did it)
-    if (e->stats()) {
-        // lease statistics: behind the batch's last reply-writing kernel and before the events
-        // that release the caller's stream and this workspace (the kernels read the caller's
-        // keys, the final reply bytes and w.err)
-        const unsigned sgrid = (unsigned)std::min<uint64_t>((n + kStatsTile - 1) / kStatsTile, kStatsMaxBlocks);
-        k_stats_batch<<<sgrid, kStatsBlock, 0, sf>>>(keys, granted, n, w.err, e->stats_view());
-        // NewestFirst evictions fail the evicted lease.  A chunk of a chunked host batch
-        // (in_ready) leaves them to its caller: the log runs on over the chunks.
-        const int32_t order = approx ? (int32_t)e->a_newest : (int32_t)e->q_newest;   // (some class evicts)
-        if (wait && e->wait_mode == 1 && order == 1 && !in_ready && e->ev_cause)
-            k_stats_log<<<64, kStatsBlock, 0, sf>>>(e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu),
-                                                    e->ev_cause, keys, n, ai_base, nullptr, e->cfg.n_keys, w.err,
-                                                    e->st_failed, e->st_tot + 1);
-        if (e->qtick.ts >= 0 && e->qtick.count)  // the fused tick's grants (tbe_wait_batch_tick_device)
-            k_stats_log<<<64, kStatsBlock, 0, sf>>>(e->qtick.count, e->qtick.cap, nullptr, nullptr, 0, 0,
-                                                    e->qtick.keyseq, e->cfg.n_keys, w.err, e->st_ok, e->st_tot);
-    }
+    if ((rc = stage_fold(b)) != TBE_OK) return rc;
+    if (b.hot && (rc = stage_hot(b)) != TBE_OK) return rc;
+    if ((rc = stage_unpartition(b)) != TBE_OK) return rc;
+    if (e->stats()) batch_stats(b, in_ready != nullptr);
     HIP_TRY(e, hipGetLastError());
     if (pipe) {
         HIP_TRY(e, hipEventRecord(w.done, sf));
@@ -5882,45 +5908,22 @@ static const char *class_params(int32_t token_limit, int32_t tokens_per_period, 
     return nullptr;
 }
 
-static tbe_status create_engine(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
-                                tbe_engine **out_engine, const tbe_queue_class *qextra = nullptr,
-                                const tbe_queue_class *aextra = nullptr);
-
-tbe_status tbe_create(const tbe_config *config, tbe_engine **out_engine) {
-    return create_engine(config, nullptr, 0, out_engine);
-}
-
-// The checks tbe_create makes on a queueing config's own options, on one class.
-static const char *queue_class_params(const tbe_queue_class &q, TbParams *out) {
-    if (const char *msg = class_params(q.token_limit, q.tokens_per_period, q.replenishment_period_ticks, out))
-        return msg;
-    if (q.queue_limit < 0 || q.queue_limit > 0xFFFF) return "QueueLimit must lie in [0, 65535]";
+// The checks tbe_create makes on a queueing or approximate config's own options, on one class.
+static const char *queue_opts_check(const tbe_queue_class &q) {
+    if (q.queue_limit < 0 || q.queue_limit > 0xFFFF) return "QueueLimit must lie in [0, 65535]";                // Q ctor
     if (q.queue_order != 0 && q.queue_order != 1)
         return "QueueProcessingOrder must be OldestFirst (0) or NewestFirst (1)";
-    if (q.token_limit >= (int32_t)kRemNone) return "TokenLimit must be < 2^30 - 1 for queueing limiters";
+    if (q.token_limit >= (int32_t)kRemNone) return "TokenLimit must be < 2^30 - 1 for queueing limiters";     // reply packing
     return nullptr;
 }
 
-tbe_status tbe_create_queue_classes(const tbe_config *config, const tbe_queue_class *extra, uint32_t n_extra,
-                                    tbe_engine **out_engine) {
-    if (!out_engine) return create_fail(TBE_EINVAL, "out_engine is NULL");
-    *out_engine = nullptr;
-    if (!config || config->struct_size < offsetof(tbe_config, zero_wait_slots))
-        return create_fail(TBE_EINVAL, "config is NULL or struct_size too small");
-    if (config->kind != TBE_KIND_QUEUEING)
-        return create_fail(TBE_EINVAL, "queueing limit classes: queueing kind only");
-    if (n_extra == 0) return create_engine(config, nullptr, 0, out_engine);
-    if (n_extra > kMaxClasses - 1) return create_fail(TBE_EINVAL, "an engine holds at most 256 limit classes (255 extra)");
-    if (!extra) return create_fail(TBE_EINVAL, "extra is NULL with n_extra > 0");
-    for (uint32_t i = 0; i < n_extra; ++i) {
-        TbParams p;
-        if (const char *msg = queue_class_params(extra[i], &p)) return create_fail(TBE_EINVAL, msg);
-    }
-    return create_engine(config, nullptr, n_extra, out_engine, extra);
+static const char *queue_class_params(const tbe_queue_class &q, TbParams *out) {
+    if (const char *msg = class_params(q.token_limit, q.tokens_per_period, q.replenishment_period_ticks, out))
+        return msg;
+    return queue_opts_check(q);
 }
 
-// The checks tbe_create makes on an approximate config's own options, on one class; the ring
-// length includes the engine-wide zero_wait_slots.
+// The ring length of an approximate class includes the engine-wide zero_wait_slots.
 static const char *approx_class_params(const tbe_queue_class &q, int32_t zero_wait_slots, TbParams *out) {
     if (const char *msg = queue_class_params(q, out)) return msg;
     if ((int64_t)std::max(1, q.queue_limit) + zero_wait_slots > 0xFFFF)
@@ -5928,57 +5931,83 @@ static const char *approx_class_params(const tbe_queue_class &q, int32_t zero_wa
     return nullptr;
 }
 
-tbe_status tbe_create_approx_classes(const tbe_config *config, const tbe_queue_class *extra, uint32_t n_extra,
-                                     tbe_engine **out_engine) {
+// The classes an engine gets beside its config's own (class 0): n of the kind's class records,
+// tbe_class for the token bucket and tbe_queue_class for the other two kinds.  n == 0: none.
+// A classed engine is laid out with wide records (TBE_FLAG_NO_PACK), the forms whose folds know
+// about classes; the token bucket also without hot runs and with 4-byte replies, the queueing
+// kind with replies of at least 2 bytes; the approximate kind's replies take two bytes when the
+// largest TokenLimit of any class allows it.
+struct ExtraClasses {
+    int32_t kind = TBE_KIND_TOKEN_BUCKET;
+    const void *p = nullptr;
+    uint32_t n = 0;
+};
+
+static tbe_status create_engine(const tbe_config *config, ExtraClasses x, tbe_engine **out_engine);
+
+tbe_status tbe_create(const tbe_config *config, tbe_engine **out_engine) {
+    return create_engine(config, ExtraClasses{}, out_engine);
+}
+
+// The three tbe_create_*classes entry points: the call's own arguments, then every extra class
+// as its kind checks it.  The token-bucket form looks at its classes before its config (and
+// with none creates an engine of whatever kind the config names), the other two at the config first.
+static tbe_status create_classes(const tbe_config *config, ExtraClasses x, tbe_engine **out_engine) {
     if (!out_engine) return create_fail(TBE_EINVAL, "out_engine is NULL");
     *out_engine = nullptr;
-    if (!config || config->struct_size < offsetof(tbe_config, zero_wait_slots))
-        return create_fail(TBE_EINVAL, "config is NULL or struct_size too small");
-    if (config->kind != TBE_KIND_APPROXIMATE)
-        return create_fail(TBE_EINVAL, "approximate limit classes: approximate kind only");
-    if (n_extra == 0) return create_engine(config, nullptr, 0, out_engine);
-    if (n_extra > kMaxClasses - 1) return create_fail(TBE_EINVAL, "an engine holds at most 256 limit classes (255 extra)");
-    if (!extra) return create_fail(TBE_EINVAL, "extra is NULL with n_extra > 0");
+    const bool tb = x.kind == TBE_KIND_TOKEN_BUCKET, approx = x.kind == TBE_KIND_APPROXIMATE;
+    auto check_config = [&]() -> const char * {
+        if (!config || config->struct_size < offsetof(tbe_config, zero_wait_slots))
+            return "config is NULL or struct_size too small";
+        if (config->kind == x.kind) return nullptr;
+        return tb ? "limit classes: token-bucket kind only"
+                  : approx ? "approximate limit classes: approximate kind only"
+                           : "queueing limit classes: queueing kind only";
+    };
+    static_assert(kMaxClasses == 256, "class bytes");
+    auto check_extra = [&]() -> const char * {
+        if (x.n > kMaxClasses - 1) return "an engine holds at most 256 limit classes (255 extra)";
+        return x.p ? nullptr : "extra is NULL with n_extra > 0";
+    };
+    if (tb && x.n == 0) return create_engine(config, ExtraClasses{}, out_engine);
+    const char *msg = tb ? check_extra() : check_config();
+    if (!msg && !tb && x.n == 0) return create_engine(config, ExtraClasses{}, out_engine);
+    if (!msg) msg = tb ? check_config() : check_extra();
+    if (msg) return create_fail(TBE_EINVAL, msg);
     // (a config from the round-1 header has no zero_wait_slots: it reads as 0)
-    const int32_t zs = config->struct_size >= offsetof(tbe_config, zero_wait_slots) + sizeof(int32_t)
+    const int32_t zs = approx && config->struct_size >= offsetof(tbe_config, zero_wait_slots) + sizeof(int32_t)
                            ? config->zero_wait_slots : 0;
     if (zs < 0) return create_fail(TBE_EINVAL, "zero_wait_slots must be >= 0");
-    for (uint32_t i = 0; i < n_extra; ++i) {
+    for (uint32_t i = 0; i < x.n && !msg; ++i) {
         TbParams p;
-        if (const char *msg = approx_class_params(extra[i], zs, &p)) return create_fail(TBE_EINVAL, msg);
+        if (tb) {
+            const tbe_class &o = static_cast<const tbe_class *>(x.p)[i];
+            msg = class_params(o.token_limit, o.tokens_per_period, o.replenishment_period_ticks, &p);
+        } else {
+            const tbe_queue_class &q = static_cast<const tbe_queue_class *>(x.p)[i];
+            msg = approx ? approx_class_params(q, zs, &p) : queue_class_params(q, &p);
+        }
     }
-    return create_engine(config, nullptr, n_extra, out_engine, nullptr, extra);
+    if (msg) return create_fail(TBE_EINVAL, msg);
+    return create_engine(config, x, out_engine);
 }
 
 tbe_status tbe_create_classes(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
                               tbe_engine **out_engine) {
-    if (!out_engine) return create_fail(TBE_EINVAL, "out_engine is NULL");
-    *out_engine = nullptr;
-    if (n_extra == 0) return create_engine(config, nullptr, 0, out_engine);
-    static_assert(kMaxClasses == 256, "class bytes");
-    if (n_extra > kMaxClasses - 1) return create_fail(TBE_EINVAL, "an engine holds at most 256 limit classes (255 extra)");
-    if (!extra) return create_fail(TBE_EINVAL, "extra is NULL with n_extra > 0");
-    if (!config || config->struct_size < offsetof(tbe_config, zero_wait_slots))
-        return create_fail(TBE_EINVAL, "config is NULL or struct_size too small");
-    if (config->kind != TBE_KIND_TOKEN_BUCKET)
-        return create_fail(TBE_EINVAL, "limit classes: token-bucket kind only");
-    for (uint32_t i = 0; i < n_extra; ++i) {
-        TbParams p;
-        if (const char *msg = class_params(extra[i].token_limit, extra[i].tokens_per_period,
-                                           extra[i].replenishment_period_ticks, &p))
-            return create_fail(TBE_EINVAL, msg);
-    }
-    return create_engine(config, extra, n_extra, out_engine);
+    return create_classes(config, ExtraClasses{TBE_KIND_TOKEN_BUCKET, extra, n_extra}, out_engine);
 }
 
-// extra != NULL: a classed engine, laid out as TBE_FLAG_NO_PACK | NO_HOT | NO_NARROW (wide
-// records, 4-byte replies, no hot runs: the forms whose folds know about classes).
-// qextra != NULL: a classed queueing engine, laid out as TBE_FLAG_NO_PACK | NO_NARROW.
-// aextra != NULL: a classed approximate engine, laid out as TBE_FLAG_NO_PACK; its replies
-// take two bytes when the largest TokenLimit of any class allows it.
-static tbe_status create_engine(const tbe_config *config, const tbe_class *extra, uint32_t n_extra,
-                                tbe_engine **out_engine, const tbe_queue_class *qextra,
-                                const tbe_queue_class *aextra) {
+tbe_status tbe_create_queue_classes(const tbe_config *config, const tbe_queue_class *extra, uint32_t n_extra,
+                                    tbe_engine **out_engine) {
+    return create_classes(config, ExtraClasses{TBE_KIND_QUEUEING, extra, n_extra}, out_engine);
+}
+
+tbe_status tbe_create_approx_classes(const tbe_config *config, const tbe_queue_class *extra, uint32_t n_extra,
+                                     tbe_engine **out_engine) {
+    return create_classes(config, ExtraClasses{TBE_KIND_APPROXIMATE, extra, n_extra}, out_engine);
+}
+
+static tbe_status create_engine(const tbe_config *config, ExtraClasses x, tbe_engine **out_engine) {
     if (!out_engine) return create_fail(TBE_EINVAL, "out_engine is NULL");
     *out_engine = nullptr;
     // struct_size versions the config: a caller built against the round-1 header (which
@@ -5989,24 +6018,20 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
     tbe_config c_in;
     std::memset(&c_in, 0, sizeof c_in);
     std::memcpy(&c_in, config, std::min<size_t>(config->struct_size, sizeof c_in));
-    if (extra) c_in.flags |= TBE_FLAG_NO_PACK | TBE_FLAG_NO_HOT | TBE_FLAG_NO_NARROW;
-    if (qextra) c_in.flags |= TBE_FLAG_NO_PACK | TBE_FLAG_NO_NARROW;
-    if (aextra) {
-        c_in.flags |= TBE_FLAG_NO_PACK;
-        qextra = nullptr;
-    }
+    const bool classed = x.n != 0;
+    if (classed) c_in.flags |= TBE_FLAG_NO_PACK;
+    if (classed && x.kind == TBE_KIND_TOKEN_BUCKET) c_in.flags |= TBE_FLAG_NO_HOT | TBE_FLAG_NO_NARROW;
+    if (classed && x.kind == TBE_KIND_QUEUEING) c_in.flags |= TBE_FLAG_NO_NARROW;
+    const bool qextra = classed && x.kind == TBE_KIND_QUEUEING, aextra = classed && x.kind == TBE_KIND_APPROXIMATE;
     const tbe_config &c = c_in;
-    const bool classed = extra || qextra || aextra;
+    // class 0: the config's own options, checked like every other class's
+    const tbe_queue_class c0{c.token_limit, c.tokens_per_period, c.replenishment_period_ticks, c.queue_limit,
+                             c.queue_order};
     if (c.kind != TBE_KIND_TOKEN_BUCKET && c.kind != TBE_KIND_QUEUEING &&
         c.kind != TBE_KIND_APPROXIMATE)
         return create_fail(TBE_EINVAL, "unknown kind");
     if (c.kind != TBE_KIND_TOKEN_BUCKET) {
-        if (c.queue_limit < 0 || c.queue_limit > 0xFFFF)                            // Q ctor
-            return create_fail(TBE_EINVAL, "QueueLimit must lie in [0, 65535]");
-        if (c.queue_order != 0 && c.queue_order != 1)
-            return create_fail(TBE_EINVAL, "QueueProcessingOrder must be OldestFirst (0) or NewestFirst (1)");
-        if (c.token_limit >= (int32_t)kRemNone)                                     // reply packing
-            return create_fail(TBE_EINVAL, "TokenLimit must be < 2^30 - 1 for queueing limiters");
+        if (const char *msg = queue_opts_check(c0)) return create_fail(TBE_EINVAL, msg);
         if (c.zero_wait_slots < 0 || (c.kind == TBE_KIND_QUEUEING && c.zero_wait_slots != 0) ||
             std::max(1, c.queue_limit) + c.zero_wait_slots > 0xFFFF)
             return create_fail(TBE_EINVAL, "zero_wait_slots must be >= 0 (approximate kind only) with "
@@ -6014,62 +6039,41 @@ static tbe_status create_engine(const tbe_config *config, const tbe_class *extra
     }
     if (c.n_keys == 0 || c.n_keys > (1ull << 32))
         return create_fail(TBE_EINVAL, "n_keys must lie in [1, 2^32]");
-    if (c.token_limit <= 0 || c.tokens_per_period <= 0)                       // TB:29-32
-        return create_fail(TBE_EINVAL, "Both TokenLimit and TokensPerPeriod must be set to values greater than 0.");
-    if (c.replenishment_period_ticks <= 0)                                    // TB:34-37 (+ "inf")
-        return create_fail(TBE_EINVAL, "ReplenishmentPeriod must be greater than TimeSpan.Zero");
-    const double rate = tbe_fill_rate(c.tokens_per_period, c.replenishment_period_ticks);
-    if (!std::isfinite(rate) || !(rate > 0.0)) return create_fail(TBE_EINVAL, "fill rate is not finite and positive");
+    TbParams p0{};
+    if (const char *msg = class_params(c0.token_limit, c0.tokens_per_period, c0.replenishment_period_ticks, &p0))
+        return create_fail(TBE_EINVAL, msg);
+    const double rate = p0.rate;
 
     tbe_engine *e = new (std::nothrow) tbe_engine();
     if (!e) return create_fail(TBE_ENOMEM, "host allocation failed");
     e->cfg = c;
-    e->params.cap = (double)c.token_limit;
-    e->params.rate = rate;
-    {
-        // TB:234: math.ceil(math.min(math.max(capacity / fill_rate, 1), 31536000))
-        double q = (double)c.token_limit / rate;
-        q = (1.0 > q) ? 1.0 : q;
-        q = (31536000.0 < q) ? 31536000.0 : q;
-        e->params.ttl_ms = (int64_t)std::ceil(q) * 1000;
-    }
+    e->params = p0;
     const int kb = ceil_log2(c.n_keys);
     e->r_bits = std::min(kMaxRBits, std::max(4, kb - 10));
     e->nbuckets = (uint32_t)((c.n_keys + (1ull << e->r_bits) - 1) >> e->r_bits);
-    e->class_opts.push_back(tbe_class{c.token_limit, c.tokens_per_period, c.replenishment_period_ticks});
-    e->class_par.push_back(e->params);
-    for (uint32_t i = 0; i < n_extra; ++i) {   // (validated by tbe_create_classes / tbe_create_queue_classes)
-        TbParams p{};
-        const tbe_queue_class *five = qextra ? qextra : aextra;
-        const tbe_class o = five ? tbe_class{five[i].token_limit, five[i].tokens_per_period,
-                                             five[i].replenishment_period_ticks}
-                                 : extra[i];
-        (void)class_params(o.token_limit, o.tokens_per_period, o.replenishment_period_ticks, &p);
-        e->class_opts.push_back(o);
-        e->class_par.push_back(p);
-    }
-    if (c.kind == TBE_KIND_QUEUEING) {
-        // the five options per class and the records the CLS kernels read (class 0: the config's)
-        e->qclass_opts.push_back(tbe_queue_class{c.token_limit, c.tokens_per_period, c.replenishment_period_ticks,
-                                                 c.queue_limit, c.queue_order});
-        for (uint32_t i = 0; i < n_extra && qextra; ++i) e->qclass_opts.push_back(qextra[i]);
-        for (size_t i = 0; i < e->qclass_opts.size(); ++i) {
-            const tbe_queue_class &q = e->qclass_opts[i];
-            e->qclass_par.push_back(QClsPar{e->class_par[i], QOpt{q.token_limit, q.queue_limit, q.queue_order,
-                                                                     (uint32_t)std::max(1, q.queue_limit)}});
-        }
-    }
+    // every class's options, parameters and the records the CLS kernels read; class 0 is the config's
     int32_t max_token_limit = c.token_limit;   // of any class: the reply width of the approximate kind
-    if (c.kind == TBE_KIND_APPROXIMATE) {
-        e->aclass_opts.push_back(tbe_queue_class{c.token_limit, c.tokens_per_period, c.replenishment_period_ticks,
-                                                 c.queue_limit, c.queue_order});
-        for (uint32_t i = 0; i < n_extra && aextra; ++i) e->aclass_opts.push_back(aextra[i]);
-        for (size_t i = 0; i < e->aclass_opts.size(); ++i) {
-            const tbe_queue_class &q = e->aclass_opts[i];
+    for (uint32_t i = 0; i <= x.n; ++i) {      // (the extra classes: validated by create_classes)
+        tbe_queue_class q = c0;
+        if (i && x.kind == TBE_KIND_TOKEN_BUCKET) {
+            const tbe_class &o = static_cast<const tbe_class *>(x.p)[i - 1];
+            q = tbe_queue_class{o.token_limit, o.tokens_per_period, o.replenishment_period_ticks, 0, 0};
+        } else if (i) {
+            q = static_cast<const tbe_queue_class *>(x.p)[i - 1];
+        }
+        TbParams p{};
+        (void)class_params(q.token_limit, q.tokens_per_period, q.replenishment_period_ticks, &p);
+        e->class_opts.push_back(tbe_class{q.token_limit, q.tokens_per_period, q.replenishment_period_ticks});
+        e->class_par.push_back(p);
+        if (c.kind == TBE_KIND_QUEUEING) {
+            e->qclass_opts.push_back(q);
+            e->qclass_par.push_back(QClsPar{p, QOpt{q.token_limit, q.queue_limit, q.queue_order,
+                                                    (uint32_t)std::max(1, q.queue_limit)}});
+        } else if (c.kind == TBE_KIND_APPROXIMATE) {
+            e->aclass_opts.push_back(q);
             e->aclass_par.push_back(AClsPar{AOpt{q.token_limit, q.queue_limit, q.queue_order,
                                                  (uint32_t)(std::max(1, q.queue_limit) + c.zero_wait_slots)},
-                                            e->class_par[i].rate,
-                                            (double)q.replenishment_period_ticks / 10000000.0});
+                                            p.rate, (double)q.replenishment_period_ticks / 10000000.0});
             max_token_limit = std::max(max_token_limit, q.token_limit);
             e->a_newest |= q.queue_order == 1;
             e->q_per_key = std::max<uint64_t>(
@@ -6569,21 +6573,16 @@ tbe_status tbe_expired_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint
     }
     const int64_t exp_lt = (ts_us / 1000 - e->params.ttl_ms) * 1000;
     const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
-    if (e->cls && e->cfg.kind == TBE_KIND_QUEUEING)   // per key, and a queued key is never dead
-        with_qhdr(e, [&](auto *qh) {
-            k_expired<<<blocks, kBlock, 0, st>>>(e->table, qh, first, count, ts_us / 1000, e->params.cap, clear,
-                                                 d_dead, e->cls_view());
-        });
-    else if (e->cls)   // per key: the kernel takes each key's ttl_ms from its class
-        k_expired<<<blocks, kBlock, 0, st>>>(e->table, (const uint64_t *)nullptr, first, count, ts_us / 1000,
-                                             e->params.cap, clear, d_dead, e->cls_view());
-    else if (e->cfg.kind == TBE_KIND_QUEUEING)
-        with_qhdr(e, [&](auto *qh) {
-            k_expired<<<blocks, kBlock, 0, st>>>(e->table, qh, first, count, exp_lt, e->params.cap, clear, d_dead);
-        });
-    else
-        k_expired<<<blocks, kBlock, 0, st>>>(e->table, (const uint64_t *)nullptr, first, count, exp_lt,
-                                             e->params.cap, clear, d_dead);
+    // x: the engine-wide bound, or with the class view the millisecond snapshot each key's own
+    // ttl_ms is taken from.  Queue headers: a queued key is never dead.
+    auto launch = [&](auto *qh, int64_t x, auto... cv) {
+        k_expired<<<blocks, kBlock, 0, st>>>(e->table, qh, first, count, x, e->params.cap, clear, d_dead, cv...);
+    };
+    const bool queueing = e->cfg.kind == TBE_KIND_QUEUEING;
+    if (e->cls && queueing) with_qhdr(e, [&](auto *qh) { launch(qh, ts_us / 1000, e->cls_view()); });
+    else if (e->cls) launch((const uint64_t *)nullptr, ts_us / 1000, e->cls_view());
+    else if (queueing) with_qhdr(e, [&](auto *qh) { launch(qh, exp_lt); });
+    else launch((const uint64_t *)nullptr, exp_lt);
     // lease statistics are per id: a key flagged dead hands its id on with both counters at 0
     if (clear && e->stats()) k_stats_zero<<<blocks, kBlock, 0, st>>>(d_dead, first, count, e->stats_view());
     HIP_TRY(e, hipGetLastError());
@@ -6621,18 +6620,16 @@ tbe_status tbe_export_live_device(tbe_engine *e, int64_t ts_us, uint64_t first, 
         const uint64_t ntiles = (count + kLiveTile - 1) / kLiveTile;
         // classed engine with a lapse test: per key, from ts_us / 1000 and the key's class
         const bool by_class = e->cls && ts_us >= 0;
-        if (by_class)
-            k_live_count<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, ts_us / 1000, e->live_tiles,
-                                                              e->cls_view());
-        else
-            k_live_count<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, exp_lt, e->live_tiles);
-        k_live_scan<<<1, kLiveScan, 0, st>>>(e->live_tiles, ntiles, reinterpret_cast<unsigned long long *>(d_n_live));
-        if (capacity && by_class)
-            k_live_write<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, ts_us / 1000, e->live_tiles,
-                                                              capacity, d_ids, d_v, d_t_us, e->cls_view());
-        else if (capacity)
-            k_live_write<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, exp_lt, e->live_tiles,
-                                                              capacity, d_ids, d_v, d_t_us);
+        auto launch = [&](int64_t x, auto... cv) {
+            k_live_count<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, x, e->live_tiles, cv...);
+            k_live_scan<<<1, kLiveScan, 0, st>>>(e->live_tiles, ntiles,
+                                                 reinterpret_cast<unsigned long long *>(d_n_live));
+            if (capacity)
+                k_live_write<<<(unsigned)ntiles, kBlock, 0, st>>>(e->table, first, count, x, e->live_tiles, capacity,
+                                                                  d_ids, d_v, d_t_us, cv...);
+        };
+        if (by_class) launch(ts_us / 1000, e->cls_view());
+        else launch(exp_lt);
         HIP_TRY(e, hipGetLastError());
     }
     if (caller && caller != st) {
@@ -6755,6 +6752,21 @@ tbe_status tbe_approx_classes(const tbe_engine *e, tbe_queue_class *out, uint32_
     return TBE_OK;
 }
 
+// The validating pass of a class assignment on `st`, into e->rows_bad: the kind's own rule.
+static void launch_set_class_check(tbe_engine *e, const uint64_t *d_ids, const uint8_t *d_cls, uint64_t n,
+                                   unsigned blocks, hipStream_t st) {
+    const uint32_t n_classes = (uint32_t)e->class_par.size();
+    if (e->acls_par)   // approximate classes: an id with anything queued voids the call
+        k_set_class_check_a<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys, n_classes, e->alocal,
+                                                       e->rows_bad);
+    else if (e->qcls_par)   // queueing classes: ids with queued entries void the call
+        with_qhdr(e, [&](auto *qh) {
+            k_set_class_check_q<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys, n_classes, qh, e->rows_bad);
+        });
+    else
+        k_set_class_check<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys, n_classes, e->rows_bad);
+}
+
 // On the engine's stream, where every kernel that touches table or classes runs, a caller's
 // stream joined before and after: tbe_import_rows_device's ordering.
 tbe_status tbe_set_class_device(tbe_engine *e, const uint64_t *d_ids, const uint8_t *d_cls, uint64_t n,
@@ -6772,26 +6784,19 @@ tbe_status tbe_set_class_device(tbe_engine *e, const uint64_t *d_ids, const uint
     HIP_TRY(e, hipMemsetAsync(e->rows_bad, 0, sizeof(uint32_t), st));
     const unsigned blocks = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192);
     // the validating pass ends before the first class is written (one stream)
-    if (e->acls_par) {   // approximate classes: the same rule, written ids get a fresh limiter's client side
-        k_set_class_check_a<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys, (uint32_t)e->class_par.size(),
-                                                       e->alocal, e->rows_bad);
+    launch_set_class_check(e, d_ids, d_cls, n, blocks, st);
+    // (a write of n = 0 ids only raises the sticky flag of a void call)
+    auto write = [&](unsigned grid, unsigned block, uint64_t m, auto *qh) {
+        k_set_class_write<<<grid, block, 0, st>>>(e->cls, d_ids, d_cls, m, e->rows_bad, e->sticky, qh);
+    };
+    if (e->acls_par)   // written ids get a fresh limiter's client side
         k_set_class_write_a<<<blocks, kBlock, 0, st>>>(e->cls, d_ids, d_cls, n, e->rows_bad, e->sticky, e->acls_par,
                                                        e->alocal, e->aclient);
-    } else if (e->qcls_par) {   // queueing classes: ids with queued entries void the call, written ids get head 0
-        with_qhdr(e, [&](auto *qh) {
-            k_set_class_check_q<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys,
-                                                           (uint32_t)e->class_par.size(), qh, e->rows_bad);
-            k_set_class_write<<<blocks, kBlock, 0, st>>>(e->cls, d_ids, d_cls, n, e->rows_bad, e->sticky, qh);
-        });
-    } else if (e->cls) {
-        k_set_class_check<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys, (uint32_t)e->class_par.size(),
-                                                     e->rows_bad);
-        k_set_class_write<<<blocks, kBlock, 0, st>>>(e->cls, d_ids, d_cls, n, e->rows_bad, e->sticky);
-    } else {   // no extra classes: class 0 is all a valid call can ask for, so there is nothing to write
-        k_set_class_check<<<blocks, kBlock, 0, st>>>(d_ids, d_cls, n, e->cfg.n_keys, (uint32_t)e->class_par.size(),
-                                                     e->rows_bad);
-        k_set_class_write<<<1, 1, 0, st>>>(nullptr, d_ids, d_cls, 0, e->rows_bad, e->sticky);
-    }
+    else if (e->qcls_par)   // written ids get head 0
+        with_qhdr(e, [&](auto *qh) { write(blocks, kBlock, n, qh); });
+    else if (e->cls) write(blocks, kBlock, n, (uint64_t *)nullptr);
+    else   // no extra classes: class 0 is all a valid call can ask for, so there is nothing to write
+        write(1, 1, 0, (uint64_t *)nullptr);
     HIP_TRY(e, hipGetLastError());
     if (caller && caller != st) {
         HIP_TRY(e, hipEventRecord(e->ev_out, st));
@@ -6828,16 +6833,7 @@ tbe_status tbe_set_class(tbe_engine *e, const uint64_t *ids, const uint8_t *cls,
         if (hrc == hipSuccess) hrc = hipMemsetAsync(e->rows_bad, 0, sizeof(uint32_t), e->stream);
         if (hrc == hipSuccess) {
             const unsigned blocks = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192);
-            if (e->acls_par)
-                k_set_class_check_a<<<blocks, kBlock, 0, e->stream>>>(d_ids, d_cls, n, e->cfg.n_keys,
-                                                                      (uint32_t)e->class_par.size(), e->alocal,
-                                                                      e->rows_bad);
-            else
-                with_qhdr(e, [&](auto *qh) {
-                    k_set_class_check_q<<<blocks, kBlock, 0, e->stream>>>(d_ids, d_cls, n, e->cfg.n_keys,
-                                                                          (uint32_t)e->class_par.size(), qh,
-                                                                          e->rows_bad);
-                });
+            launch_set_class_check(e, d_ids, d_cls, n, blocks, e->stream);
             hrc = hipGetLastError();
         }
         if (hrc == hipSuccess) hrc = hipMemcpyAsync(&bad, e->rows_bad, sizeof bad, hipMemcpyDeviceToHost, e->stream);
@@ -6928,13 +6924,11 @@ static tbe_status sync_queued(tbe_engine *e) {
     hipStream_t st = e->stream;
     HIP_TRY(e, hipMemsetAsync(e->qcount, 0, sizeof(unsigned long long), st));
     const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
-    if (e->cfg.kind == TBE_KIND_QUEUEING)
-        with_qhdr(e, [&](auto *qh) {
-            k_count_queued<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, qh, e->alocal, e->qcount);
-        });
-    else
-        k_count_queued<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, (const uint64_t *)nullptr, e->alocal,
-                                                            e->qcount);
+    auto launch = [&](const auto *qh) {   // queue headers, or none: the approximate kind's counts
+        k_count_queued<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, qh, e->alocal, e->qcount);
+    };
+    if (e->cfg.kind == TBE_KIND_QUEUEING) with_qhdr(e, [&](auto *qh) { launch(qh); });
+    else launch((const uint64_t *)nullptr);
     HIP_TRY(e, hipGetLastError());
     unsigned long long q = 0;
     HIP_TRY(e, hipMemcpyAsync(&q, e->qcount, sizeof q, hipMemcpyDeviceToHost, st));
@@ -7135,7 +7129,7 @@ static tbe_status status_chunked(tbe_engine *e, const uint64_t *keys, const int3
     const int32_t order = e->cfg.kind == TBE_KIND_APPROXIMATE ? (int32_t)e->a_newest : (int32_t)e->q_newest;
     if (e->stats() && e->wait_mode == 1 && order == 1) {
         // the evictions of all chunks, once: their causes index the whole staged batch
-        k_stats_log<<<64, kStatsBlock, 0, e->stream>>>(e->counters, (uint32_t)std::min<uint64_t>(e->ev_cap, 0xFFFFFFFFu),
+        k_stats_log<<<64, kStatsBlock, 0, e->stream>>>(e->counters, ev_cap32(e),
                                                        e->ev_cause, e->d_keys, n, 0u, nullptr, e->cfg.n_keys, nullptr,
                                                        e->st_failed, e->st_tot + 1);
         HIP_TRY(e, hipGetLastError());
@@ -7271,17 +7265,16 @@ static void launch_drain(tbe_engine *e, int64_t ts_us, uint64_t *keyseq, int64_t
     const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
     with_qhdr(e, [&](auto *qh) {
         using HW = std::remove_pointer_t<decltype(qh)>;
-        if (e->qcls_par && mask)
-            k_drain<HW, true, QClsBits><<<(unsigned)blocks, kBlock, 0, st>>>(
-                e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us, keyseq, id, rem, count, cap,
-                e->qcls_view(), qcls_bits(mask));
-        else if (e->qcls_par)
-            k_drain<HW, true><<<(unsigned)blocks, kBlock, 0, st>>>(
-                e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us, keyseq, id, rem, count, cap,
-                e->qcls_view());
-        else
-            k_drain<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us,
-                                                        keyseq, id, rem, count, cap);
+        auto launch = [&](auto cls, auto... mk) {   // cls: a classed engine; mk: none or the mask's QClsBits
+            constexpr bool CLS = decltype(cls)::value;
+            std::conditional_t<CLS, QClsView, NoQCls> qc{};
+            if constexpr (CLS) qc = e->qcls_view();
+            k_drain<HW, CLS, decltype(mk)...><<<(unsigned)blocks, kBlock, 0, st>>>(
+                e->cfg.n_keys, e->table, qh, e->ring, e->params, e->qp, ts_us, keyseq, id, rem, count, cap, qc, mk...);
+        };
+        if (e->qcls_par && mask) launch(std::true_type{}, qcls_bits(mask));
+        else if (e->qcls_par) launch(std::true_type{});
+        else launch(std::false_type{});
     });
 }
 
@@ -7307,9 +7300,8 @@ static tbe_status queue_refresh(tbe_engine *e, int64_t ts_us, uint64_t *n_grante
     }
     hipStream_t st = e->stream;
     HIP_TRY(e, hipMemsetAsync(e->counters + 1, 0, sizeof(uint32_t), st));
-    launch_drain(e, ts_us, e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
-                 (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), mask, st);
-    stats_drained(e, e->log_keyseq, e->counters + 1, (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), st);
+    launch_drain(e, ts_us, e->log_keyseq, e->log_id, e->log_rem, e->counters + 1, cap32(e->log_cap), mask, st);
+    stats_drained(e, e->log_keyseq, e->counters + 1, cap32(e->log_cap), st);
     HIP_TRY(e, hipGetLastError());
     uint32_t cnt = 0;
     HIP_TRY(e, hipMemcpyAsync(&cnt, e->counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -7474,11 +7466,12 @@ static tbe_status approx_collect(tbe_engine *e, int32_t *d_counts, void *stream,
     HIP_TRY(e, hipSetDevice(e->device));
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
     const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
-    if (e->acls_par)
-        k_approx_collect<true><<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->alocal, d_counts,
-                                                                    e->acls_mask(mask));
-    else if (mask[0] & 1u)
-        k_approx_collect<<<(unsigned)blocks, kBlock, 0, st>>>(e->cfg.n_keys, e->alocal, d_counts);
+    auto launch = [&](auto m) {   // m: the classes' mask, or none
+        k_approx_collect<std::is_same_v<decltype(m), AClsMask>><<<(unsigned)blocks, kBlock, 0, st>>>(
+            e->cfg.n_keys, e->alocal, d_counts, m);
+    };
+    if (e->acls_par) launch(e->acls_mask(mask));
+    else if (mask[0] & 1u) launch(NoACls{});
     else   // a plain engine without class 0: every key gives 0 and keeps its count
         HIP_TRY(e, hipMemsetAsync(d_counts, 0, e->cfg.n_keys * sizeof(int32_t), st));
     HIP_TRY(e, hipGetLastError());
@@ -7569,17 +7562,18 @@ static tbe_status approx_sync(tbe_engine *e, const int32_t *d_all_counts, uint32
     hipStream_t st = e->stream;
     HIP_TRY(e, hipMemsetAsync(e->counters + 1, 0, sizeof(uint32_t), st));
     const uint64_t blocks = std::min<uint64_t>((e->cfg.n_keys + kBlock - 1) / kBlock, 8192);
-    if (e->acls_par)   // (views written at every sync: a classed engine is never aclient_lazy)
-        k_approx_sync<true><<<(unsigned)blocks, kBlock, 0, st>>>(
-            e->cfg.n_keys, e->alocal, e->aclient, e->gv, e->gp, e->gt, e->ring, e->ap, d_all_counts,
-            n_clients, my_client, ts_us, stagger_us, e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
-            (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), 1u, e->acls_mask(mask));
-    else
-        k_approx_sync<<<(unsigned)blocks, kBlock, 0, st>>>(
-            e->cfg.n_keys, e->alocal, e->aclient, e->gv, e->gp, e->gt, e->ring, e->ap, d_all_counts,
-            n_clients, my_client, ts_us, stagger_us, e->log_keyseq, e->log_id, e->log_rem, e->counters + 1,
-            (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), n_clients != 1 ? 1u : 0u);
-    stats_drained(e, e->log_keyseq, e->counters + 1, (uint32_t)std::min<uint64_t>(e->log_cap, 0xFFFFFFFFu), st);
+    const uint32_t log_cap = cap32(e->log_cap);
+    // (views written at every sync of a classed engine: it is never aclient_lazy)
+    const uint32_t write_client = (e->acls_par || n_clients != 1) ? 1u : 0u;
+    auto launch = [&](auto m) {   // m: the classes' mask, or none
+        k_approx_sync<std::is_same_v<decltype(m), AClsMask>><<<(unsigned)blocks, kBlock, 0, st>>>(
+            e->cfg.n_keys, e->alocal, e->aclient, e->gv, e->gp, e->gt, e->ring, e->ap, d_all_counts, n_clients,
+            my_client, ts_us, stagger_us, e->log_keyseq, e->log_id, e->log_rem, e->counters + 1, log_cap,
+            write_client, m);
+    };
+    if (e->acls_par) launch(e->acls_mask(mask));
+    else launch(NoACls{});
+    stats_drained(e, e->log_keyseq, e->counters + 1, log_cap, st);
     HIP_TRY(e, hipGetLastError());
     e->aclient_lazy = n_clients == 1 && !e->acls_par;   // a classed engine keeps written views
     uint32_t cnt = 0;
@@ -7721,12 +7715,13 @@ tbe_status tbe_approx_idle_device(tbe_engine *e, int64_t ts_us, uint64_t first, 
     hipStream_t caller = (hipStream_t)stream;
     if (tbe_status rc = join_in(e, caller); rc != TBE_OK) return rc;
     const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
-    if (e->acls_par)
-        k_approx_idle<true><<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient, e->gv, e->gt, first, count, ts_us,
-                                                              e->ap.decay_rate, d_idle, e->acls_view());
-    else
-        k_approx_idle<<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient_lazy ? nullptr : e->aclient, e->gv, e->gt,
-                                                        first, count, ts_us, e->ap.decay_rate, d_idle);
+    auto launch = [&](auto cv) {   // cv: the class view, or none.  (A classed engine is never aclient_lazy.)
+        k_approx_idle<std::is_same_v<decltype(cv), AClsView>><<<blocks, kBlock, 0, e->stream>>>(
+            e->alocal, e->aclient_lazy ? nullptr : e->aclient, e->gv, e->gt, first, count, ts_us, e->ap.decay_rate,
+            d_idle, cv);
+    };
+    if (e->acls_par) launch(e->acls_view());
+    else launch(NoACls{});
     HIP_TRY(e, hipGetLastError());
     return join_out(e, caller);
 }
@@ -7744,12 +7739,12 @@ tbe_status tbe_approx_reset_device(tbe_engine *e, uint64_t first, uint64_t count
     // write every view the last one-client sync left to be derived, then reset
     if (tbe_status rc = materialise_aclient(e, e->stream); rc != TBE_OK) return rc;
     const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
-    if (e->acls_par)
-        k_approx_reset<true><<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient, e->gv, e->gp, e->gt, first, count,
-                                                               d_flags, e->ap.token_limit, e->acls_view());
-    else
-        k_approx_reset<<<blocks, kBlock, 0, e->stream>>>(e->alocal, e->aclient, e->gv, e->gp, e->gt, first, count,
-                                                         d_flags, e->ap.token_limit);
+    auto launch = [&](auto cv) {   // cv: the class view, or none
+        k_approx_reset<std::is_same_v<decltype(cv), AClsView>><<<blocks, kBlock, 0, e->stream>>>(
+            e->alocal, e->aclient, e->gv, e->gp, e->gt, first, count, d_flags, e->ap.token_limit, cv);
+    };
+    if (e->acls_par) launch(e->acls_view());
+    else launch(NoACls{});
     if (e->stats()) k_stats_zero<<<blocks, kBlock, 0, e->stream>>>(d_flags, first, count, e->stats_view());
     HIP_TRY(e, hipGetLastError());
     e->queued_exact = false;   // a flagged key's queue, if it had one, is gone: queued_total is a bound
@@ -8076,16 +8071,14 @@ tbe_status tbe_queue_cancel(tbe_engine *e, const uint64_t *keys, const int64_t *
     const bool approx = e->cfg.kind == TBE_KIND_APPROXIMATE;
     const uint32_t rcap = approx ? e->ap.cap : e->qp.cap;
     with_qhdr(e, [&](auto *qh) {
-        if (e->acls_par)
+        auto launch = [&](auto... av) {   // av: the approximate class view, or none
             k_cancel<<<(n_runs + 255) / 256, 256, 0, e->stream>>>(
-                (const uint64_t *)s.p, (const int64_t *)(s.p + off_ids), (const uint32_t *)(s.p + off_runs),
-                n_runs, 1, qh, e->alocal, e->ring, rcap, (uint8_t *)(s.p + off_hit), QClsView{nullptr, nullptr},
-                e->acls_view());
-        else
-            k_cancel<<<(n_runs + 255) / 256, 256, 0, e->stream>>>(
-                (const uint64_t *)s.p, (const int64_t *)(s.p + off_ids), (const uint32_t *)(s.p + off_runs),
-                n_runs, approx ? 1 : 0, qh, e->alocal, e->ring, rcap, (uint8_t *)(s.p + off_hit),
-                e->qcls_par ? e->qcls_view() : QClsView{nullptr, nullptr});
+                (const uint64_t *)s.p, (const int64_t *)(s.p + off_ids), (const uint32_t *)(s.p + off_runs), n_runs,
+                approx ? 1 : 0, qh, e->alocal, e->ring, rcap, (uint8_t *)(s.p + off_hit),
+                e->qcls_par ? e->qcls_view() : QClsView{nullptr, nullptr}, av...);
+        };
+        if (e->acls_par) launch(e->acls_view());
+        else launch();
     });
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -8126,32 +8119,19 @@ tbe_status tbe_stats_batch_device(tbe_engine *e, const uint64_t *d_keys, uint64_
     k_stats_check<<<blocks, kBlock, 0, st>>>(d_keys, n, e->cfg.n_keys, e->rows_bad);
     auto *ok = reinterpret_cast<unsigned long long *>(d_ok);
     auto *failed = reinterpret_cast<unsigned long long *>(d_failed);
-    const uint64_t *no_qhdr = nullptr;
-    if (approx)
-        k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)nullptr, e->params, no_qhdr, e->alocal,
-                                                e->stats_view(), ok, failed, d_available, d_queued, e->rows_bad,
-                                                e->sticky);
-    else if (e->cfg.kind == TBE_KIND_QUEUEING)
-        with_qhdr(e, [&](auto *qh) {
-            using HW = std::remove_pointer_t<decltype(qh)>;
-            if (e->cls)   // per key: `available` by the key's class
-                k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)e->table, e->params,
-                                                        (const HW *)qh, (const ALocal *)nullptr, e->stats_view(), ok,
-                                                        failed, d_available, d_queued, e->rows_bad, e->sticky,
-                                                        e->cls_view());
-            else
-                k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)e->table, e->params,
-                                                        (const HW *)qh, (const ALocal *)nullptr, e->stats_view(), ok,
-                                                        failed, d_available, d_queued, e->rows_bad, e->sticky);
-        });
-    else if (e->cls)   // per key: the kernel takes each key's parameters from its class
-        k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)e->table, e->params, no_qhdr,
-                                                (const ALocal *)nullptr, e->stats_view(), ok, failed, d_available,
-                                                d_queued, e->rows_bad, e->sticky, e->cls_view());
-    else
-        k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, (const Slot *)e->table, e->params, no_qhdr,
-                                                (const ALocal *)nullptr, e->stats_view(), ok, failed, d_available,
-                                                d_queued, e->rows_bad, e->sticky);
+    // approximate kind: no table; cv: the class view of a classed token-bucket or queueing engine
+    // (`available` by the key's class), or none
+    auto launch = [&](const auto *qh, auto... cv) {
+        k_stats_read<<<blocks, kBlock, 0, st>>>(d_keys, n, ts_us, approx ? (const Slot *)nullptr : e->table, e->params,
+                                                qh, approx ? e->alocal : (const ALocal *)nullptr, e->stats_view(), ok,
+                                                failed, d_available, d_queued, e->rows_bad, e->sticky, cv...);
+    };
+    auto by_class = [&](const auto *qh) {
+        if (e->cls && !approx) launch(qh, e->cls_view());
+        else launch(qh);
+    };
+    if (e->cfg.kind == TBE_KIND_QUEUEING) with_qhdr(e, [&](auto *qh) { by_class(qh); });
+    else by_class((const uint64_t *)nullptr);
     HIP_TRY(e, hipGetLastError());
     if (caller && caller != st) {
         HIP_TRY(e, hipEventRecord(e->ev_out, st));
