@@ -50,7 +50,8 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_create_queue_classes", "tbe_queue_classes", "tbe_create_approx_classes", "tbe_approx_classes",
             "tbe_approx_collect_classes", "tbe_approx_sync_classes", "tbe_approx_sync_classes_stream",
             "tbe_approx_refresh_classes",
-            "tbe_refresh_classes", "tbe_refresh_classes_device", "tbe_wait_batch_tick_classes_device")
+            "tbe_refresh_classes", "tbe_refresh_classes_device", "tbe_wait_batch_tick_classes_device",
+            "tbe_migrate_out_device", "tbe_migrate_out")
 # k_stats_batch's shape (csrc/tbe_stats.hpp): requests per workgroup trip and slots of its
 # LDS table; the tests size their cases by them
 STATS_TILE, STATS_SLOTS = 4096, 2048
@@ -191,6 +192,12 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_import_rows_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]
     lib.tbe_import_rows.restype = c_int32
     lib.tbe_import_rows.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
+    lib.tbe_migrate_out_device.restype = c_int32
+    lib.tbe_migrate_out_device.argtypes = [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_uint32, c_uint32,
+                                           c_void_p, c_uint64, c_void_p, c_void_p, c_int32, c_void_p]
+    lib.tbe_migrate_out.restype = c_int32
+    lib.tbe_migrate_out.argtypes = [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_uint32, c_uint32,
+                                    c_void_p, c_uint64, c_void_p, c_void_p, c_int32]
     lib.tbe_wait_batch.restype = c_int32
     lib.tbe_wait_batch.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_int64, c_void_p,
                                    c_void_p, POINTER(c_uint64)]

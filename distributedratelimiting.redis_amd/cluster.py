@@ -766,6 +766,234 @@ def _check(st: int) -> None:
         raise _capi.TbeError(st, "routing kernel launch failed")
 
 
+# ------------------------------------------------------------------ live owner-map change
+ABSENT = np.iinfo(np.int64).min          # t_us of a row never granted (tbe.h)
+_CLASS_WORDS = 1 + 3 * 256               # the class table as int64 words: count, then three options each
+
+
+def class_ttl_ms(token_limit: int, tokens_per_period: int, period_ticks: int) -> int:
+    """EXPIRE of one limiter's buckets in ms (TB:234), as the engine computes it."""
+    rate = np.float64(tokens_per_period) / (np.float64(period_ticks) / np.float64(1e7))
+    q = min(max(np.float64(token_limit) / rate, 1.0), 31536000.0)
+    return int(np.ceil(q)) * 1000
+
+
+def rows_live(t_us, ts_us: int, ttl_ms) -> np.ndarray:
+    """Which rows are live at ts_us, as a bool array: present and not lapsed
+    (tbe_export_live_device's rule); ttl_ms a number or one per row; ts_us < 0 skips the
+    lapse test."""
+    t_us = np.asarray(t_us, dtype=np.int64)
+    live = t_us != ABSENT
+    if ts_us >= 0:
+        live &= ~(t_us < 1000 * (int(ts_us) // 1000 - np.asarray(ttl_ms, dtype=np.int64)))
+    return live
+
+
+def plan_migration(keys_of_id, v, t_us, cls, live, owner_map, world: int, rank: int):
+    """What one owner sends when `owner_map` (None: the hash partition) comes into force:
+    tbe_migrate_out_device's rule in numpy, its reference and the body of ``migrate``'s host
+    path.  keys_of_id[i]: the key holding id i, UINT64_MAX where none does; v, t_us, cls
+    (None: class 0) and live (``rows_live``) describe row i.  An id is *leaving* when its key's
+    new owner is not `rank`; a leaving id with a live row sends {key, bits of v, t_us, class},
+    one with an absent or lapsed row sends nothing (its new owner starts it from a full
+    bucket).  Returns (rows int64 [n, 4] grouped by destination ascending and by id inside
+    one, counts int64 [world + 2]: rows per owner, leaving ids, orphans -- live rows whose id
+    no key holds, never sent --, leaving uint8 [ids]).  A map entry >= world: ValueError."""
+    keys = np.ascontiguousarray(keys_of_id, dtype=np.uint64)
+    n = keys.shape[0]
+    if not 1 <= world <= 256 or not 0 <= rank < world:
+        raise ValueError("world in 1..256 and rank < world")
+    if owner_map is not None:
+        check_owner_map(owner_map, world)
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    t_us = np.ascontiguousarray(t_us, dtype=np.int64)
+    cls = np.zeros(n, dtype=np.uint8) if cls is None else np.asarray(cls, dtype=np.uint8)
+    live = np.asarray(live, dtype=bool)
+    if not (v.shape[0] == t_us.shape[0] == cls.shape[0] == live.shape[0] == n):
+        raise ValueError("one entry per id in every column")
+    held = keys != NO_ID
+    dest = np.full(n, rank, dtype=np.int64)
+    dest[held] = key_owner(keys[held], world, owner_map)
+    leaving = held & (dest != rank)
+    send = np.flatnonzero(leaving & live)
+    send = send[np.argsort(dest[send], kind="stable")]
+    rows = np.stack([keys[send].view(np.int64), v[send].view(np.int64), t_us[send], cls[send].astype(np.int64)],
+                    axis=1).reshape(-1, 4)
+    counts = np.zeros(world + 2, dtype=np.int64)
+    counts[:world] = np.bincount(dest[send], minlength=world)
+    counts[world] = int(leaving.sum())
+    counts[world + 1] = int((live & ~held).sum())
+    return rows, counts, leaving.astype(np.uint8)
+
+
+def _class_table(engine):
+    """[(token_limit, tokens_per_period, period_ticks)], class 0 first."""
+    if hasattr(engine, "classes"):
+        return [tuple(int(x) for x in c) for c in engine.classes()]
+    c = engine.config
+    return [(int(c.token_limit), int(c.tokens_per_period), int(c.replenishment_period_ticks))]
+
+
+def _preflight(local_error, classes, like, group) -> None:
+    """Every rank raises ValueError when any rank has a `local_error` or the ranks' class
+    tables differ; nothing has been changed anywhere yet.  `like`: a tensor on the device the
+    exchanges run on (a CUDA tensor on the device path)."""
+    import torch
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    words = torch.zeros(_CLASS_WORDS, dtype=torch.int64)
+    words[0] = len(classes)
+    words[1:1 + 3 * len(classes)] = torch.tensor(classes, dtype=torch.int64).reshape(-1)
+    words = words.to(like.device)
+    allw = torch.empty(world * _CLASS_WORDS, dtype=torch.int64, device=like.device)
+    _all_gather(allw, words, group=group)
+    if local_error is None and not bool((allw.view(world, -1) == words).all().item()):
+        local_error = "the ranks' engines hold different class tables"
+    bad = torch.tensor([0 if local_error is None else 1], dtype=torch.int64, device=like.device)
+    _all_reduce_sum(bad, group=group)
+    if int(bad.item()):
+        raise ValueError("cluster.migrate refused, nothing changed: "
+                         + (local_error or "another rank failed its pre-flight check"))
+
+
+def _room_error(engine_keys, directory, held, counts, incoming, world):
+    if engine_keys < directory.capacity:
+        return "the engine has fewer keys than the directory has ids"
+    if counts[world + 1]:
+        return f"{counts[world + 1]} live rows' ids are held by no key of the directory"
+    if held - counts[world] + incoming > directory.capacity:
+        return (f"the directory holds {held} keys, {counts[world]} leave and {incoming} arrive: "
+                f"more than its {directory.capacity} ids")
+    return None
+
+
+def migrate(engine, directory, new_map, ts_us: int, group=None) -> Tuple[int, int]:
+    """Bring a new owner map into force while the tables stay where they are (DESIGN.md §7
+    "Migrating buckets").  A collective: every rank calls it between batches with the same
+    `new_map` (None: the hash partition) and ts_us.  Each rank finds the keys it holds that
+    the new map gives to another rank, sends their live bucket rows (with class byte) to the
+    new owners in one all-to-all, clears those rows, drops the keys from its directory and
+    installs the rows it receives behind its own directory.  Afterwards
+    ``route_batch(..., owner_map=new_map)`` decides as if the new map had been in force from
+    the start.  Returns (rows sent, rows received).
+
+    With a ``DeviceDirectory`` everything stays in HBM (``migrate_out_device``,
+    ``reclaim_device``, ``assign``, ``set_class_device``, ``import_rows``); only the world
+    group sizes go through the host.  With a ``HostDirectory`` the same steps run on numpy
+    arrays over ``export_state`` / ``import_state`` (and ``get_class`` / ``set_class`` on a
+    classed engine).  Before anything changes every rank checks that no live row is an orphan,
+    that its directory has room for what arrives, that its engine covers its directory and
+    that all ranks hold the same class table; a failure on any rank raises ValueError on all
+    of them.  Token bucket kind only; lease counters are not carried (the source zeroes
+    them)."""
+    import torch.distributed as dist
+    from . import _capi
+    kind = int(getattr(engine, "KIND", _capi.TBE_KIND_TOKEN_BUCKET))
+    if kind == _capi.TBE_KIND_QUEUEING:
+        raise ValueError("cluster.migrate: the queueing kind's rings and the host's request-id futures "
+                         "would have to move too; it is not supported")
+    if kind == _capi.TBE_KIND_APPROXIMATE:
+        raise ValueError("cluster.migrate: the approximate kind's tier is replicated and its requests "
+                         "are not routed, so there is nothing to move")
+    if hasattr(directory, "text_of"):
+        raise TypeError("cluster.migrate routes by u64 key: a StringDirectory has none")
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    if new_map is not None and not _is_cuda(new_map):
+        check_owner_map(new_map, world)
+    if isinstance(directory, DeviceDirectory):
+        return _migrate_device(engine, directory, new_map, int(ts_us), world, rank, group)
+    return _migrate_host(engine, directory, new_map, int(ts_us), world, rank, group)
+
+
+def _migrate_device(engine, directory, new_map, ts_us, world, rank, group):
+    import torch
+    from . import _capi
+    dev = torch.device("cuda", engine.config.device if engine.config.device >= 0 else torch.cuda.current_device())
+    st = device_stream(dev)
+    cap = directory.capacity
+    dmap = _device_map(new_map, dev, world)
+    counts = torch.zeros(world + 2, dtype=torch.int64, device=dev)
+    leaving = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    covered = engine.n_keys >= cap
+    if covered:
+        kof = directory.keys_of(torch.arange(cap, dtype=torch.int64, device=dev))
+        engine.migrate_out_device(ts_us, kof, dmap, world, rank, None, counts, leaving, stream=st)
+    rc = torch.empty(world, dtype=torch.int64, device=dev)
+    _all_to_all(rc, counts[:world].contiguous(), group=group)
+    sc_l, rc_l = counts.tolist(), rc.tolist()
+    try:
+        held = directory.size()
+        err = _room_error(engine.n_keys, directory, held, sc_l, sum(rc_l), world)
+    except _capi.TbeError as ex:
+        err = str(ex)
+    _preflight(err, _class_table(engine), counts, group)
+    n_send = sum(sc_l[:world])
+    rows = torch.empty((n_send, 4), dtype=torch.int64, device=dev)
+    engine.migrate_out_device(ts_us, kof, dmap, world, rank, rows if n_send else None, counts, leaving, commit=True,
+                              capacity=n_send, stream=st)
+    directory.reclaim_device(leaving)
+    recv = torch.empty((sum(rc_l), 4), dtype=torch.int64, device=dev)
+    _all_to_all(recv, rows, rc_l, sc_l[:world], group=group)
+    if recv.shape[0]:
+        ids = directory.assign(recv[:, 0].contiguous())
+        directory.check()
+        if getattr(engine, "classed", False):   # first: a reused id still carries its previous key's class
+            engine.set_class_device(ids, recv[:, 3].to(torch.uint8), stream=st)
+        engine.import_rows(ids, recv[:, 1].contiguous().view(torch.float64), recv[:, 2].contiguous(), stream=st)
+    return n_send, sum(rc_l)
+
+
+def _migrate_host(engine, directory, new_map, ts_us, world, rank, group):
+    import torch
+    import torch.distributed as dist
+    from . import _capi
+    cap = directory.capacity
+    classes = _class_table(engine)
+    classed = bool(getattr(engine, "classed", False))
+    v, t = engine.export_state()
+    v, t = np.array(v, dtype=np.float64), np.array(t, dtype=np.int64)
+    n_keys = int(getattr(engine, "n_keys", v.shape[0]))
+    err = None
+    if n_keys < cap or v.shape[0] < cap:
+        err = "the engine has fewer keys than the directory has ids"
+        rows, counts = np.zeros((0, 4), dtype=np.int64), np.zeros(world + 2, dtype=np.int64)
+        leaving = np.zeros(cap, dtype=np.uint8)
+    else:
+        v, t = v[:cap], t[:cap]
+        keys_of_id = np.full(cap, NO_ID, dtype=np.uint64)
+        for k, i in directory.ids.items():
+            keys_of_id[i] = k
+        cls = engine.get_class(np.arange(cap, dtype=np.uint64)) if classed else np.zeros(cap, dtype=np.uint8)
+        ttl = np.array([class_ttl_ms(*c) for c in classes], dtype=np.int64)[cls]
+        rows, counts, leaving = plan_migration(keys_of_id, v, t, cls, rows_live(t, ts_us, ttl), new_map, world, rank)
+    sc = torch.from_numpy(counts[:world].copy())
+    rc = torch.empty_like(sc)
+    dist.all_to_all_single(rc, sc, group=group)
+    sc_l, rc_l = counts.tolist(), rc.tolist()
+    if err is None:
+        err = "the directory is over capacity" if directory.overflow else \
+            _room_error(n_keys, directory, directory.size(), sc_l, sum(rc_l), world)
+    _preflight(err, classes, sc, group)
+    gone = np.flatnonzero(leaving)
+    v[gone] = np.array([c[0] for c in classes], dtype=np.float64)[cls[gone]]
+    t[gone] = ABSENT
+    engine.import_state(v, t)
+    directory.reclaim(gone)
+    recv = torch.empty((sum(rc_l), 4), dtype=torch.int64)
+    dist.all_to_all_single(recv, torch.from_numpy(np.ascontiguousarray(rows)), output_split_sizes=rc_l,
+                           input_split_sizes=sc_l[:world], group=group)
+    r = recv.numpy()
+    if r.shape[0]:
+        ids = directory.assign(r[:, 0].copy().view(np.uint64))
+        directory.check()
+        if classed:   # first: a reused id still carries its previous key's class
+            engine.set_class(ids, r[:, 3].astype(np.uint8))
+        v[ids.astype(np.int64)] = r[:, 1].copy().view(np.float64)
+        t[ids.astype(np.int64)] = r[:, 2]
+        engine.import_state(v, t)
+    return int(rows.shape[0]), int(r.shape[0])
+
+
 # ------------------------------------------------------------------ approximate global tier
 def approx_epoch(engine, counts, ts_us: int, stagger_us: int, mode: str = "clients",
                  group=None):

@@ -45,6 +45,7 @@
 #include "../../include/tbe.h"
 #include "tbe_device.hpp"
 #include "tbe_codec.hpp"
+#include "tbe_hash.hpp"
 #include "tbe_numfmt.hpp"
 #include "tbe_retry.hpp"
 
@@ -4644,6 +4645,239 @@ __global__ void k_rows_write(Slot *__restrict__ table, const uint64_t *__restric
     }
 }
 
+// ---- live owner-map change (tbe_migrate_out_device, DESIGN.md §7 "Migrating buckets"):
+// the live rows of the ids whose key a new owner map gives to another owner, packed as
+// {key, bits(v), t_us, class} grouped by destination (ascending) and by id inside one.  The
+// multi-bin relative of the export above, on its tiles and element order, with no spinning
+// between workgroups and no atomic on an output position:
+//   k_mig_pass<false>  per tile: flags every leaving id, ranks the rows to send by destination
+//                      (ballot match in a wave, count matrix [item][wave][owner] in LDS, one
+//                      thread per owner scans its column) and stores the tile's count per
+//                      owner at tile_n[owner * ntiles + tile]; two more columns take the
+//                      tile's leaving ids and orphans
+//   k_mig_scan         the owners' columns as one flat array, owner-major, scanned in place:
+//                      entry [o][tile] becomes the first output row of that tile's rows for o
+//   k_mig_finish       counts[o] from the scanned starts, the two sums, the verdict of the call
+//   k_mig_pass<true>   the same ranking again over whole rows, stored from those starts
+//   k_mig_commit       leaving ids' rows rewritten absent, their lease counters zeroed
+// flags[0]: a map entry >= n_owners (nothing is written); flags[1]: the commit is refused.
+struct MigArgs {
+    const Slot *table;
+    const uint64_t *key_of_id;   // count entries, kMigNoKey: no key holds the id
+    const uint8_t *map;          // kOwnerMapSize entries or nullptr (hash partition)
+    const uint8_t *cls;          // class byte per id, or nullptr
+    const TbParams *par;         // class table (read when by_class)
+    uint64_t first, count, ntiles;
+    int64_t x;                   // lapse bound, or ts_us / 1000 when by_class
+    uint32_t n_owners, self;
+    int32_t by_class;
+};
+constexpr uint64_t kMigNoKey = ~0ull;
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+static_assert(kBlock == kDigits, "k_mig_pass: one thread per owner column");
+
+__device__ __forceinline__ uint32_t mig_dest(const MigArgs &A, uint64_t key) {
+    return A.map ? (uint32_t)A.map[key_vnode(key)] : key_owner(key, A.n_owners);
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(kBlock) void k_mig_pass(MigArgs A, unsigned long long *__restrict__ tile_n,
+                                                     uint8_t *__restrict__ leaving, uint32_t *__restrict__ flags,
+                                                     int64_t *__restrict__ rows, uint64_t capacity) {
+    __shared__ uint16_t cnt[kLiveItems * kWaves * kDigits];   // [item][wave][owner], 16 KB
+    __shared__ unsigned long long start[kDigits];
+    __shared__ uint32_t part[2 * kWaves];
+    if (WRITE && flags[0]) return;   // (the whole grid)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    {
+        uint4 *z = reinterpret_cast<uint4 *>(cnt);
+        const uint4 zero = {0u, 0u, 0u, 0u};
+        for (int i = tid; i < kLiveItems * kWaves * kDigits * 2 / 16; i += kBlock) z[i] = zero;
+    }
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * kLiveTile;
+    const uint64_t lt = lanemask_lt();
+    uint64_t key[kLiveItems];
+    Slot s[kLiveItems];
+    uint32_t dest[kLiveItems], rank[kLiveItems], cbyte[kLiveItems];
+    bool send[kLiveItems];
+    uint32_t n_leave = 0, n_orphan = 0, bad_map = 0;
+    // every load of the tile first, independent of one another, then the arithmetic
+#pragma unroll
+    for (int k = 0; k < kLiveItems; ++k) {
+        const uint64_t i = base + (uint64_t)k * kBlock + tid;
+        key[k] = kMigNoKey;
+        s[k].t_us = kAbsent;
+        cbyte[k] = 0;
+        if (i < A.count) {
+            const uint64_t id = A.first + i;
+            key[k] = ld_nt(A.key_of_id + i);
+            if constexpr (WRITE) s[k] = slot_load_nt(&A.table[id]);
+            else s[k].t_us = ld_nt(&A.table[id].t_us);
+            if (A.cls) cbyte[k] = A.cls[id];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kLiveItems; ++k) {
+        const uint64_t i = base + (uint64_t)k * kBlock + tid;
+        send[k] = false;
+        dest[k] = 0;
+        bool leave = false;
+        if (i < A.count) {
+            const int64_t exp_lt = A.by_class ? (A.x - A.par[cbyte[k]].ttl_ms) * 1000 : A.x;
+            const bool live = row_live(s[k].t_us, exp_lt);
+            if (key[k] != kMigNoKey) {
+                const uint32_t d = mig_dest(A, key[k]);
+                if (d >= A.n_owners) bad_map = 1;
+                else if (d != A.self) {
+                    leave = true;
+                    send[k] = live;
+                    dest[k] = d;
+                }
+            } else if (live) ++n_orphan;
+            if (!WRITE && leaving) leaving[i] = leave ? 1 : 0;
+        }
+        n_leave += leave ? 1u : 0u;
+        const uint64_t peers = digit_peers(dest[k], 0, __ballot(send[k]));
+        rank[k] = (uint32_t)__popcll(peers & lt);
+        if (send[k] && rank[k] == 0) cnt[(k * kWaves + w) * kDigits + dest[k]] = (uint16_t)__popcll(peers);
+    }
+    __syncthreads();
+    if ((uint32_t)tid < A.n_owners) {   // this owner's column, in tile order
+        uint32_t run = 0;
+#pragma unroll 8
+        for (int j = 0; j < kLiveItems * kWaves; ++j) {
+            const uint32_t c = cnt[j * kDigits + tid];
+            cnt[j * kDigits + tid] = (uint16_t)run;
+            run += c;
+        }
+        const uint64_t at = (uint64_t)tid * A.ntiles + blockIdx.x;
+        if constexpr (WRITE) start[tid] = tile_n[at];
+        else tile_n[at] = run;
+    }
+    if constexpr (!WRITE) {
+        // the tile's leaving ids and orphans: columns n_owners and n_owners + 1 of tile_n
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            n_leave += __shfl_down(n_leave, o);
+            n_orphan += __shfl_down(n_orphan, o);
+        }
+        if (lane == 0) {
+            part[w] = n_leave;
+            part[kWaves + w] = n_orphan;
+        }
+        if (bad_map) flags[0] = 1u;
+        __syncthreads();
+        if (tid < 2) {
+            uint32_t sum = 0;
+#pragma unroll
+            for (int j = 0; j < kWaves; ++j) sum += part[tid * kWaves + j];
+            tile_n[(uint64_t)(A.n_owners + tid) * A.ntiles + blockIdx.x] = sum;
+        }
+    } else {
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kLiveItems; ++k) {
+            if (!send[k]) continue;
+            const uint64_t pos = start[dest[k]] + cnt[(k * kWaves + w) * kDigits + dest[k]] + rank[k];
+            if (pos < capacity) {
+                i64x2 *out = reinterpret_cast<i64x2 *>(rows + 4 * pos);
+                const i64x2 a = {(long long)key[k], (long long)__double_as_longlong(s[k].v)};
+                const i64x2 b = {(long long)s[k].t_us, (long long)cbyte[k]};
+                st_nt(out, a);
+                st_nt(out + 1, b);
+            }
+        }
+    }
+}
+
+// The owners' columns of tile_n (n entries, owner-major) scanned in place to exclusive
+// prefixes, *total their sum: k_live_scan with eight consecutive entries per thread, so that
+// n_owners * ntiles entries take an eighth of the rounds.
+constexpr int kMigScanItems = 8;
+__global__ __launch_bounds__(kLiveScan) void k_mig_scan(unsigned long long *__restrict__ tile_n, uint64_t n,
+                                                        unsigned long long *__restrict__ total) {
+    __shared__ uint32_t wsum[kLiveScan / 64];
+    unsigned long long carry = 0;
+    for (uint64_t j0 = 0; j0 < n; j0 += (uint64_t)kLiveScan * kMigScanItems) {
+        const uint64_t j = j0 + (uint64_t)threadIdx.x * kMigScanItems;
+        uint32_t c[kMigScanItems], sum = 0;   // <= kLiveTile each
+#pragma unroll
+        for (int k = 0; k < kMigScanItems; ++k) {
+            c[k] = j + k < n ? (uint32_t)tile_n[j + k] : 0u;
+            sum += c[k];
+        }
+        uint32_t tot;
+        unsigned long long run = carry + block_excl_scan<kLiveScan>(sum, wsum, &tot);
+#pragma unroll
+        for (int k = 0; k < kMigScanItems; ++k) {
+            if (j + k < n) tile_n[j + k] = run;
+            run += c[k];
+        }
+        carry += tot;
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+// counts[o] = rows for owner o, from the scanned starts (*total: all rows); the leaving ids
+// and orphans summed over the tiles; then the verdict.
+__global__ __launch_bounds__(kBlock) void k_mig_finish(const unsigned long long *__restrict__ tile_n, uint64_t ntiles,
+                                                       const unsigned long long *__restrict__ total,
+                                                       uint32_t n_owners, uint64_t capacity, int32_t commit,
+                                                       unsigned long long *__restrict__ counts,
+                                                       uint32_t *__restrict__ flags, uint32_t *__restrict__ sticky) {
+    __shared__ unsigned long long part[2 * kWaves];
+    const uint32_t o = threadIdx.x;
+    if (o < n_owners) counts[o] = (o + 1 < n_owners ? tile_n[(uint64_t)(o + 1) * ntiles] : *total) - tile_n[(uint64_t)o * ntiles];
+    unsigned long long n_leave = 0, n_orphan = 0;
+    for (uint64_t j = o; j < ntiles; j += kBlock) {
+        n_leave += tile_n[(uint64_t)n_owners * ntiles + j];
+        n_orphan += tile_n[(uint64_t)(n_owners + 1) * ntiles + j];
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        n_leave += __shfl_down(n_leave, d);
+        n_orphan += __shfl_down(n_orphan, d);
+    }
+    if ((o & 63) == 0) {
+        part[o >> 6] = n_leave;
+        part[kWaves + (o >> 6)] = n_orphan;
+    }
+    __syncthreads();
+    if (o == 0) {
+        n_leave = n_orphan = 0;
+#pragma unroll
+        for (int j = 0; j < kWaves; ++j) {
+            n_leave += part[j];
+            n_orphan += part[kWaves + j];
+        }
+        counts[n_owners] = n_leave;
+        counts[n_owners + 1] = n_orphan;
+        const bool refuse = flags[0] || (commit && (*total > capacity || n_orphan != 0));
+        flags[1] = refuse ? 1u : 0u;
+        if (refuse) *sticky = 1u;
+    }
+}
+
+// Every leaving id's row becomes {TokenLimit of its class, absent}; with lease statistics
+// both of its counters become 0 (the totals stay), as k_expired(clear) + k_stats_zero do.
+__global__ __launch_bounds__(kBlock) void k_mig_commit(MigArgs A, Slot *__restrict__ table, double cap,
+                                                       const uint32_t *__restrict__ flags,
+                                                       unsigned long long *__restrict__ st_ok,
+                                                       unsigned long long *__restrict__ st_failed) {
+    if (flags[1]) return;
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= A.count) return;
+    const uint64_t key = ld_nt(A.key_of_id + i);
+    if (key == kMigNoKey || mig_dest(A, key) == A.self) return;
+    const uint64_t id = A.first + i;
+    table[id] = Slot{A.cls ? A.par[A.cls[id]].cap : cap, kAbsent};
+    if (st_ok) {
+        st_ok[id] = 0;
+        st_failed[id] = 0;
+    }
+}
+
 // ---- limit classes (tbe_set_class_device / tbe_get_class_device), shaped like the import by
 // id: k_set_class_check sets *bad for an id >= n_keys or a class >= n_classes, and
 // k_set_class_write then writes nothing and raises the sticky flag.
@@ -5071,6 +5305,11 @@ struct tbe_engine {
     // allocated by the first export) and k_rows_check's flag
     unsigned long long *live_tiles = nullptr;
     uint32_t *rows_bad = nullptr;
+    // tbe_migrate_out_device: [0] total rows, [1] its two flags (u32), then the tile counts
+    // per owner and of leaving ids and orphans ((n_owners + 2) * ntiles); allocated by the
+    // first call, grown by a larger one
+    unsigned long long *mig_ws = nullptr;
+    uint64_t mig_ws_cap = 0;
     // lease statistics (TBE_FLAG_STATS): ok[k] and failed[k] per key and the
     // engine's two totals, allocated at create on an engine with the flag and nowhere else
     unsigned long long *st_ok = nullptr, *st_failed = nullptr, *st_tot = nullptr;
@@ -6310,6 +6549,7 @@ void tbe_destroy(tbe_engine *e) {
     dfree(e->sticky);
     dfree(e->live_tiles);
     dfree(e->rows_bad);
+    dfree(e->mig_ws);
     dfree(e->st_ok);
     dfree(e->st_failed);
     dfree(e->st_tot);
@@ -6725,6 +6965,141 @@ tbe_status tbe_import_rows(tbe_engine *e, const uint64_t *ids, const double *v, 
     (void)hipFree(buf);
     if (rc != TBE_OK) return rc;
     HIP_TRY(e, hrc);
+    return TBE_OK;
+}
+
+// ---- live owner-map change: the source side (DESIGN.md §7 "Migrating buckets").  Stream
+// ordering is tbe_expired_device's: the kernels run on the engine's stream, a caller's
+// stream is joined before and after.
+static tbe_status migrate_args_ok(tbe_engine *e, uint64_t first, uint64_t count, const void *key_of_id,
+                                  uint32_t n_owners, uint32_t self, const void *rows, uint64_t capacity,
+                                  const void *counts) {
+    if (e->cfg.kind == TBE_KIND_QUEUEING)
+        return fail(e, TBE_EINVAL, "the queueing kind's rings and request ids do not migrate");
+    if (e->cfg.kind == TBE_KIND_APPROXIMATE)
+        return fail(e, TBE_EINVAL, "the approximate kind's tier is replicated: there is nothing to migrate");
+    if (n_owners < 1 || n_owners > 256 || self >= n_owners) return fail(e, TBE_EINVAL, "n_owners in 1..256, self < n_owners");
+    if (first > e->cfg.n_keys || count > e->cfg.n_keys - first)
+        return fail(e, TBE_EINVAL, "range out of bounds");
+    if (!counts || !key_of_id || (capacity && !rows)) return fail(e, TBE_EINVAL, "null buffer");
+    return TBE_OK;
+}
+
+tbe_status tbe_migrate_out_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count,
+                                  const uint64_t *d_key_of_id, const uint8_t *d_owner_map, uint32_t n_owners,
+                                  uint32_t self, int64_t *d_rows, uint64_t capacity, uint64_t *d_counts,
+                                  uint8_t *d_leaving, int32_t commit, void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (tbe_status rc = migrate_args_ok(e, first, count, d_key_of_id, n_owners, self, d_rows, capacity, d_counts))
+        return rc;
+    HIP_TRY(e, hipSetDevice(e->device));
+    const uint64_t ntiles = (count + kLiveTile - 1) / kLiveTile;
+    const uint64_t need = 2 + ((uint64_t)n_owners + 2) * ntiles;
+    if (need > e->mig_ws_cap) {
+        if (e->mig_ws) HIP_TRY(e, hipFree(e->mig_ws));   // (waits for the kernels that use it)
+        e->mig_ws = nullptr;
+        e->mig_ws_cap = 0;
+        if (hipMalloc(&e->mig_ws, need * sizeof(unsigned long long)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(e, TBE_ENOMEM, "migration workspace");
+        }
+        e->mig_ws_cap = need;
+    }
+    hipStream_t st = e->stream, caller = (hipStream_t)stream;
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_in, caller));
+        HIP_TRY(e, hipStreamWaitEvent(st, e->ev_in, 0));
+    }
+    HIP_TRY(e, hipMemsetAsync(d_counts, 0, (n_owners + 2) * sizeof(uint64_t), st));
+    if (count) {
+        unsigned long long *total = e->mig_ws, *tile_n = e->mig_ws + 2;
+        uint32_t *flags = reinterpret_cast<uint32_t *>(e->mig_ws + 1);
+        unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_counts);
+        HIP_TRY(e, hipMemsetAsync(flags, 0, 2 * sizeof(uint32_t), st));
+        MigArgs A{};
+        A.table = e->table;
+        A.key_of_id = d_key_of_id;
+        A.map = d_owner_map;
+        A.cls = e->cls;
+        A.par = e->cls_par;
+        A.first = first;
+        A.count = count;
+        A.ntiles = ntiles;
+        // classed engine with a lapse test: per key, from ts_us / 1000 and the key's class
+        A.by_class = e->cls && ts_us >= 0;
+        A.x = A.by_class ? ts_us / 1000 : (ts_us < 0 ? kAbsent : (ts_us / 1000 - e->params.ttl_ms) * 1000);
+        A.n_owners = n_owners;
+        A.self = self;
+        k_mig_pass<false><<<(unsigned)ntiles, kBlock, 0, st>>>(A, tile_n, d_leaving, flags, nullptr, 0);
+        k_mig_scan<<<1, kLiveScan, 0, st>>>(tile_n, (uint64_t)n_owners * ntiles, total);
+        k_mig_finish<<<1, kBlock, 0, st>>>(tile_n, ntiles, total, n_owners, capacity, commit, counts, flags, e->sticky);
+        if (capacity)
+            k_mig_pass<true><<<(unsigned)ntiles, kBlock, 0, st>>>(A, tile_n, nullptr, flags, d_rows, capacity);
+        if (commit)
+            k_mig_commit<<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, st>>>(A, e->table, e->params.cap, flags,
+                                                                                       e->st_ok, e->st_failed);
+        HIP_TRY(e, hipGetLastError());
+    }
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_out, st));
+        HIP_TRY(e, hipStreamWaitEvent(caller, e->ev_out, 0));
+    }
+    return TBE_OK;
+}
+
+tbe_status tbe_migrate_out(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, const uint64_t *key_of_id,
+                           const uint8_t *owner_map, uint32_t n_owners, uint32_t self, int64_t *rows,
+                           uint64_t capacity, uint64_t *counts, uint8_t *leaving, int32_t commit) {
+    if (!e) return TBE_EINVAL;
+    if (tbe_status rc = migrate_args_ok(e, first, count, key_of_id, n_owners, self, rows, capacity, counts)) return rc;
+    for (uint32_t v = 0; owner_map && v < kOwnerMapSize; ++v)
+        if (owner_map[v] >= n_owners) return fail(e, TBE_EINVAL, "owner map entry >= n_owners");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch, whatever its stream
+    const uint64_t cap = std::min(capacity, count);   // no more rows than the range holds
+    const uint64_t nc = (uint64_t)n_owners + 2;
+    // [counts | rows | key_of_id | map | leaving], every part 16-byte aligned
+    const uint64_t o_rows = (nc * 8 + 15) & ~15ull, o_keys = o_rows + cap * 32, o_map = (o_keys + count * 8 + 15) & ~15ull,
+                   o_leave = o_map + kOwnerMapSize;
+    char *buf = nullptr;
+    HIP_TRY(e, hipMalloc(&buf, o_leave + count + 16));
+    uint64_t *d_counts = reinterpret_cast<uint64_t *>(buf), *d_keys = reinterpret_cast<uint64_t *>(buf + o_keys);
+    int64_t *d_rows = reinterpret_cast<int64_t *>(buf + o_rows);
+    uint8_t *d_map = reinterpret_cast<uint8_t *>(buf + o_map), *d_leave = reinterpret_cast<uint8_t *>(buf + o_leave);
+    hipError_t hrc = count ? hipMemcpy(d_keys, key_of_id, count * 8, hipMemcpyHostToDevice) : hipSuccess;
+    if (hrc == hipSuccess && owner_map) hrc = hipMemcpy(d_map, owner_map, kOwnerMapSize, hipMemcpyHostToDevice);
+    tbe_status rc = TBE_OK;
+    auto run = [&](uint64_t c, int32_t cm) {
+        rc = tbe_migrate_out_device(e, ts_us, first, count, d_keys, owner_map ? d_map : nullptr, n_owners, self,
+                                    c ? d_rows : nullptr, c, d_counts, d_leave, cm, nullptr);
+        if (rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
+        if (rc == TBE_OK && hrc == hipSuccess) hrc = hipMemcpy(counts, d_counts, nc * 8, hipMemcpyDeviceToHost);
+    };
+    const char *refused = nullptr;
+    if (hrc == hipSuccess && commit) {
+        // the counting call alone first: a commit that would be refused returns TBE_EINVAL here
+        // and leaves the sticky flag of earlier device batches as it is (as tbe_set_class does)
+        run(0, 0);
+        if (rc == TBE_OK && hrc == hipSuccess) {
+            uint64_t total = 0;
+            for (uint32_t o = 0; o < n_owners; ++o) total += counts[o];
+            if (counts[n_owners + 1]) refused = "a live row's id is held by no key";
+            else if (total > capacity) refused = "rows do not fit in capacity";
+        }
+    }
+    if (hrc == hipSuccess && rc == TBE_OK && !refused) run(cap, commit);
+    if (hrc == hipSuccess && rc == TBE_OK && !refused) {
+        uint64_t total = 0;
+        for (uint32_t o = 0; o < n_owners; ++o) total += counts[o];
+        const uint64_t m = std::min(total, cap);
+        if (m) hrc = hipMemcpy(rows, d_rows, m * 32, hipMemcpyDeviceToHost);
+    }
+    if (hrc == hipSuccess && rc == TBE_OK && leaving && count)
+        hrc = hipMemcpy(leaving, d_leave, count, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
+    if (refused) return fail(e, TBE_EINVAL, refused);
     return TBE_OK;
 }
 

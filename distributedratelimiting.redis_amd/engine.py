@@ -265,6 +265,60 @@ class TokenBucketEngine:
                                                      d_t_us.data_ptr(), n, stream))
         self._rows_in_flight = (d_ids, d_v, d_t_us)   # read by the enqueued kernels
 
+    # ------------------------------------------------------------------ live owner-map change
+    def migrate_out_device(self, ts_us: int, d_key_of_id, d_owner_map, n_owners: int, self_rank: int, d_rows,
+                           d_counts, d_leaving=None, commit: bool = False, first: int = 0,
+                           capacity: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """One tbe_migrate_out_device call over ids [first, first + d_key_of_id.numel()): the
+        live rows of the ids whose key (int64 device tensor, -1 = unheld) `d_owner_map` (uint8
+        device tensor of 4096 owners, or None for the hash partition) gives to another owner
+        than self_rank, packed as int64 {key, bits of v, t_us, class} into d_rows grouped by
+        destination; d_counts (int64, n_owners + 2): rows per owner, leaving ids, orphans;
+        d_leaving (uint8, one per id, optional): 1 where the id's key leaves.  capacity (rows)
+        defaults to what d_rows holds; 0 with d_rows=None only counts.  commit=True also
+        rewrites the leaving rows absent.  Enqueued; a refused call raises at ``synchronize()``."""
+        count = d_key_of_id.numel()
+        if capacity is None:
+            capacity = 0 if d_rows is None else d_rows.numel() // 4
+        if capacity and (d_rows is None or d_rows.numel() < 4 * capacity or not d_rows.is_contiguous()):
+            raise ValueError("capacity exceeds d_rows")
+        if d_counts.numel() < n_owners + 2 or d_counts.element_size() != 8:
+            raise ValueError("d_counts must hold n_owners + 2 64-bit counters")
+        if d_leaving is not None and (d_leaving.numel() != count or d_leaving.element_size() != 1):
+            raise ValueError("d_leaving must hold one byte per id")
+        if d_owner_map is not None and (d_owner_map.numel() != 4096 or d_owner_map.element_size() != 1):
+            raise ValueError("the owner map must be 4096 uint8 entries")
+        if not d_key_of_id.is_contiguous() or d_key_of_id.element_size() != 8:
+            raise ValueError("d_key_of_id must be a contiguous 64-bit tensor")
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        self._check(self._lib.tbe_migrate_out_device(
+            self.handle, ts_us, first, count, d_key_of_id.data_ptr(), ptr(d_owner_map), n_owners, self_rank,
+            ptr(d_rows) if capacity else None, capacity, d_counts.data_ptr(), ptr(d_leaving), 1 if commit else 0, stream))
+        self._migrate_in_flight = (d_key_of_id, d_owner_map)   # read by the enqueued kernels
+
+    def migrate_out(self, ts_us: int, key_of_id, owner_map, n_owners: int, self_rank: int, commit: bool = False,
+                    first: int = 0, capacity: Optional[int] = None):
+        """The same with host arrays (tbe_migrate_out; synchronous): returns (rows int64
+        [capacity, 4] of which the first min(total, capacity) are written, counts uint64
+        [n_owners + 2], leaving uint8 [count]).  capacity defaults to the number of ids."""
+        key_of_id = np.ascontiguousarray(key_of_id, dtype=np.uint64)
+        count = key_of_id.shape[0]
+        if owner_map is not None:
+            owner_map = np.ascontiguousarray(owner_map, dtype=np.uint8)
+            if owner_map.shape != (4096,):
+                raise ValueError("the owner map must be 4096 uint8 entries")
+        if capacity is None:
+            capacity = count
+        rows = np.zeros((capacity, 4), dtype=np.int64)
+        counts = np.zeros(n_owners + 2, dtype=np.uint64)
+        leaving = np.zeros(count, dtype=np.uint8)
+        self._check(self._lib.tbe_migrate_out(
+            self.handle, ts_us, first, count, key_of_id.ctypes.data,
+            None if owner_map is None else owner_map.ctypes.data, n_owners, self_rank,
+            rows.ctypes.data if capacity else None, capacity, counts.ctypes.data, leaving.ctypes.data,
+            1 if commit else 0))
+        return rows, counts, leaving
+
     # ------------------------------------------------------------------ limit classes
     def classes(self):
         """Every class's (token_limit, tokens_per_period, period_ticks), class 0 first (tbe_classes)."""

@@ -379,6 +379,49 @@ tbe_status tbe_import_rows_device(tbe_engine *engine, const uint64_t *d_ids, con
 tbe_status tbe_import_rows(tbe_engine *engine, const uint64_t *ids, const double *v, const int64_t *t_us,
                            uint64_t n);
 
+/* Live owner-map change, the source side (DESIGN.md §7 "Migrating buckets"; the collective
+ * around it is cluster.migrate).  Token-bucket kind, plain or with limit classes; the
+ * queueing and approximate kinds: TBE_EINVAL.
+ *
+ * d_key_of_id[i] is the key that holds id first + i (tbe_dir_keys_of_device writes it),
+ * UINT64_MAX where no key does.  dest = d_owner_map ? d_owner_map[tbe_key_vnode(key)] :
+ * tbe_key_owner(key, n_owners), as in tbe_route_plan_map_device.  An id whose key has
+ * dest != self is leaving: d_leaving[i] = 1 (every other id 0; d_leaving may be NULL).  A
+ * leaving id whose row is live at ts_us (tbe_export_live_device's rule, by the key's own class
+ * on a classed engine; ts_us < 0 skips the lapse test) contributes one row of four int64
+ * {key, bits of v, t_us, class} (class 0 without classes); a leaving id with an absent or
+ * lapsed row contributes none: its new owner starts it from a full bucket, which decides the
+ * same at ts_us and later.  Rows are written to d_rows grouped by destination in ascending
+ * owner order and in ascending id order inside a destination, row j < capacity at
+ * d_rows + 4 j (16-byte aligned); nothing at or past capacity is touched, and capacity == 0
+ * (d_rows may be NULL) only counts and flags.  d_counts (device u64, n_owners + 2 entries)
+ * is always complete: [o] rows for owner o ([self] = 0), [n_owners] leaving ids,
+ * [n_owners + 1] orphans -- live rows of the range whose id no key holds, which are never
+ * sent and never touched.
+ *
+ * commit == 0 reads only.  commit != 0 then rewrites every leaving id's row absent
+ * ({TokenLimit of its class, absent}) and, with TBE_FLAG_STATS, zeroes both of its lease
+ * counters (class bytes and engine totals stay), as tbe_expired_device(clear) does for a
+ * dead key.  A commit whose rows do not all fit in capacity or that finds an orphan, and
+ * any call that meets a map entry >= n_owners, changes neither table nor counters (every row
+ * is judged before any is written; a bad map entry also leaves d_rows unwritten) and is
+ * reported like an invalid device batch: by tbe_synchronize.
+ *
+ * n_owners outside 1..256, self >= n_owners, a range past n_keys, a NULL d_key_of_id or
+ * d_counts: TBE_EINVAL, nothing enqueued.  Ordered after every batch enqueued before the
+ * call (pipelined ones included) and before every batch enqueued after it; `stream` as in
+ * tbe_expired_device.  The engine keeps 8 (n_owners + 2) bytes of
+ * workspace per 2048 ids of the range. */
+tbe_status tbe_migrate_out_device(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                                  const uint64_t *d_key_of_id, const uint8_t *d_owner_map, uint32_t n_owners,
+                                  uint32_t self, int64_t *d_rows, uint64_t capacity, uint64_t *d_counts,
+                                  uint8_t *d_leaving, int32_t commit, void *stream);
+/* The same with host buffers; synchronous.  A refused commit or a map entry >= n_owners:
+ * TBE_EINVAL, nothing changed (counts is still complete for a refused commit). */
+tbe_status tbe_migrate_out(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                           const uint64_t *key_of_id, const uint8_t *owner_map, uint32_t n_owners, uint32_t self,
+                           int64_t *rows, uint64_t capacity, uint64_t *counts, uint8_t *leaving, int32_t commit);
+
 /* ---------------------------------------------------------------- TokenBucketWithQueue
  * Engines created with kind = TBE_KIND_QUEUEING. The reference limiter
  * (TokenBucketWithQueue/RedisTokenBucketRateLimiter.cs, "Q") is commented out and does

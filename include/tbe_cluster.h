@@ -49,10 +49,16 @@ tbe_status tbe_route_plan_device(const uint64_t *d_keys, uint64_t n, uint32_t n_
  * v -> (v * n_owners) >> 12 is the hash partition above for a power-of-two n_owners; a
  * balanced map gives the virtual nodes of hot keys' owners fewer others, so a Zipf
  * stream's owner loads even out (SURVEY.md §7 hard part iii).  A key still has exactly
- * one owner.  Owners hold their buckets by dense id, so a live table cannot follow a map that
- * changes under it; a map (or the number of owners) changes through a snapshot: every owner
- * saves its live buckets by key (tbe_export_live_device, tbe_dir_keys_of_device) and each
- * new owner loads the keys the new map gives it (DESIGN.md §8 "Portable snapshots"). */
+ * one owner.  Owners hold their buckets by dense id, so a map changes between batches by
+ * migrating the buckets it reassigns (DESIGN.md §7 "Migrating buckets"): every owner packs
+ * the live rows of the keys the new map gives away (tbe_dir_keys_of_device over its ids,
+ * then tbe_migrate_out_device with commit), drops those keys (tbe_dir_reclaim_device with
+ * the leaving flags), the rows cross in one all-to-all, and each new owner installs them
+ * behind its own directory (tbe_dir_assign_device, tbe_set_class_device,
+ * tbe_import_rows_device); the tables stay in HBM.  The number of owners still changes
+ * through a snapshot: every owner saves its live buckets by key (tbe_export_live_device,
+ * tbe_dir_keys_of_device) and each new owner loads the keys the new map gives it
+ * (DESIGN.md §8 "Portable snapshots"). */
 #define TBE_OWNER_MAP_BITS 12
 #define TBE_OWNER_MAP_SIZE 4096
 uint32_t tbe_key_vnode(uint64_t key);

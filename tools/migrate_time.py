@@ -1,0 +1,165 @@
+#!/usr/bin/env python3
+"""Cost of a live owner-map change on one owner (cluster.migrate's local steps) beside the
+snapshot route, the only way to change a map before tbe_migrate_out_device existed.
+
+One GPU, no ranks.  A TokenBucketEngine and a DeviceDirectory hold --keys live keys (default
+2^26); the change is n_owners = 2, self = 0 and map B (the hash owner map with every odd
+virtual node moved to the other owner), which gives about half of the keys away.  Timed, HIP
+events around each call, after a warm-up of every call on a small engine:
+
+  count    migrate_out_device, counting and flagging only (capacity 0)       median of --repeats
+  commit   migrate_out_device(commit) into a buffer of the counted size      median of --repeats
+           (the rows are put back with import_rows between repeats)
+  reclaim  the source directory's reclaim_device(leaving flags)              once
+  install  assign + import_rows of the packed rows on a second engine and
+           directory on the same GPU                                        once
+  snapshot snapshot.save of the same table, then snapshot.load(owner=...)
+           of the file into fresh engines for both new owners               once (host clock)
+
+Bytes a migrate_out pass must move: 16 B per row of the table and 8 B per id of the key-of-id
+table, plus 32 B per row sent; the count call is one such pass, the commit call two (count,
+write) plus the clearing pass (8 B per id, 16 B per leaving row).  `of_copy_rate` is those
+bytes over the call's time as a fraction of the 6.29 TB/s an on-device copy reaches on this GPU.
+The exchange between owners (RCCL) is not part of this: it needs more than one GPU.
+Prints one JSON line and, with --out, writes it to that file (profiles/).
+
+    python tools/migrate_time.py [--keys 67108864] [--repeats 5] [--no-snapshot] [--out profiles/migrate_time.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+COPY_RATE = 6.29e12
+TS = 1_760_000_100_000_000
+OPTS = (5, 1, 10_000_000)      # TTL 5 s
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--keys", type=int, default=1 << 26)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--no-snapshot", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    from distributedratelimiting.redis_amd import TokenBucketEngine, cluster, snapshot
+
+    if not torch.cuda.is_available():
+        raise SystemExit("migrate_time.py measures on the GPU; none is visible")
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(0)
+    world, me = 2, 0
+    map_b = cluster.hash_owner_map(world).astype(np.int64)
+    map_b[1::2] = (map_b[1::2] + 1) % world
+    map_b = map_b.astype(np.uint8)
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b), out
+
+    def run(n: int, repeats: int, with_snapshot: bool) -> dict:
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        eng, directory = TokenBucketEngine(n, *OPTS, device=0), cluster.DeviceDirectory(n, device=0)
+        keys = torch.arange(n, dtype=torch.int64, device=dev)
+        g = torch.Generator(device=dev).manual_seed(7)
+        v = torch.rand(n, dtype=torch.float64, device=dev, generator=g) * OPTS[0]
+        t = TS - torch.randint(0, 2_000_000, (n,), dtype=torch.int64, device=dev, generator=g)   # every row live
+        ids = directory.assign(keys)
+        directory.check()
+        eng.import_rows(ids, v, t, stream=cur)
+        eng.synchronize()
+        dmap = torch.from_numpy(map_b).to(dev)
+        kof = directory.keys_of(torch.arange(n, dtype=torch.int64, device=dev))
+        counts = torch.zeros(world + 2, dtype=torch.int64, device=dev)
+        leaving = torch.empty(n, dtype=torch.uint8, device=dev)
+        res = {"keys": n}
+        ms = [timed(lambda: eng.migrate_out_device(TS, kof, dmap, world, me, None, counts, leaving, stream=cur))[0]
+              for _ in range(repeats)]
+        c = counts.tolist()
+        n_rows, n_leave = sum(c[:world]), c[world]
+        assert c[world + 1] == 0 and n_rows == n_leave
+        rows = torch.empty((n_rows, 4), dtype=torch.int64, device=dev)
+        res.update(rows_sent=n_rows, count_ms=round(statistics.median(ms), 4), count_all_ms=[round(x, 4) for x in ms])
+        ms = []
+        for r in range(repeats):
+            ms.append(timed(lambda: eng.migrate_out_device(TS, kof, dmap, world, me, rows, counts, leaving, commit=True,
+                                                           capacity=n_rows, stream=cur))[0])
+            eng.synchronize()
+            if r + 1 < repeats:     # put the cleared rows back for the next repeat
+                eng.import_rows(ids, v, t, stream=cur)
+                eng.synchronize()
+        res.update(commit_ms=round(statistics.median(ms), 4), commit_all_ms=[round(x, 4) for x in ms])
+        res["reclaim_ms"] = round(timed(lambda: directory.reclaim_device(leaving))[0], 4)
+        assert directory.size() == n - n_leave
+        # the receiving side: a second engine and directory on the same GPU
+        eng2, dir2 = TokenBucketEngine(n, *OPTS, device=0), cluster.DeviceDirectory(n, device=0)
+
+        def install():
+            rid = dir2.assign(rows[:, 0].contiguous())
+            eng2.import_rows(rid, rows[:, 1].contiguous().view(torch.float64), rows[:, 2].contiguous(), stream=cur)
+        res["install_ms"] = round(timed(install)[0], 4)
+        eng2.synchronize()
+        assert dir2.size() == n_rows
+        eng2.close()
+        dir2.close()
+        count_bytes = 24 * n + n
+        commit_bytes = count_bytes + 24 * n + 32 * n_rows + 8 * n + 16 * n_leave
+        res.update(count_bytes=count_bytes, commit_bytes=commit_bytes,
+                   count_of_copy_rate=round(count_bytes / (res["count_ms"] * 1e-3) / COPY_RATE, 4),
+                   commit_of_copy_rate=round(commit_bytes / (res["commit_ms"] * 1e-3) / COPY_RATE, 4),
+                   migrate_local_ms=round(res["count_ms"] + res["commit_ms"] + res["reclaim_ms"] + res["install_ms"], 4))
+        if with_snapshot:
+            # the same change by the snapshot route: the table as it was before the commit
+            eng.import_rows(ids, v, t, stream=cur)
+            eng.synchronize()
+            old = cluster.DeviceDirectory(n, device=0)
+            old.assign(keys)
+            with tempfile.TemporaryDirectory() as tmp:
+                path = os.path.join(tmp, "owner0.npz")
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                snapshot.save(path, eng, TS, old)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                res["snapshot_file_bytes"] = os.path.getsize(path)
+                eng.close()
+                old.close()
+                for owner in range(world):
+                    e, d = TokenBucketEngine(n, *OPTS, device=0), cluster.DeviceDirectory(n, device=0)
+                    snapshot.load(path, e, d, owner=(owner, world, map_b), stream=cur)
+                    e.synchronize()
+                    e.close()
+                    d.close()
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+            res.update(snapshot_save_ms=round((t1 - t0) * 1e3, 1), snapshot_load_ms=round((t2 - t1) * 1e3, 1),
+                       snapshot_ms=round((t2 - t0) * 1e3, 1))
+            res["snapshot_over_migrate"] = round(res["snapshot_ms"] / res["migrate_local_ms"], 1)
+        else:
+            eng.close()
+        directory.close()
+        return res
+
+    with torch.cuda.stream(torch.cuda.Stream(dev)):
+        run(1 << 16, 2, not args.no_snapshot)          # warm-up: every call once at a small size
+        line = run(args.keys, args.repeats, not args.no_snapshot)
+    line["repeats"] = args.repeats
+    print(json.dumps(line), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
