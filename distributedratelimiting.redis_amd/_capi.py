@@ -313,6 +313,22 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_route_pack_device.argtypes = [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.tbe_route_gather_device.restype = c_int32
     lib.tbe_route_gather_device.argtypes = [c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_void_p]
+    # routing text (include/tbe_cluster.h "routing text")
+    lib.tbe_text_route_key.restype = c_uint64
+    lib.tbe_text_route_key.argtypes = [c_void_p, c_uint64, c_uint64]
+    lib.tbe_route_text_keys_device.restype = c_int32
+    lib.tbe_route_text_keys_device.argtypes = [c_void_p, c_uint64, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
+                                               c_void_p]
+    lib.tbe_route_text_workspace_bytes.restype = c_uint64
+    lib.tbe_route_text_workspace_bytes.argtypes = [c_uint64]
+    lib.tbe_route_text_offsets_device.restype = c_int32
+    lib.tbe_route_text_offsets_device.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p]
+    lib.tbe_route_text_pack_device.restype = c_int32
+    lib.tbe_route_text_pack_device.argtypes = [c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]
+    lib.tbe_route_text_recv_offsets_device.restype = c_int32
+    lib.tbe_route_text_recv_offsets_device.argtypes = [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]
     lib.tbe_dir_create.restype = c_int32
     lib.tbe_dir_create.argtypes = [c_uint64, c_int32, POINTER(c_void_p)]
     lib.tbe_dir_destroy.restype = None

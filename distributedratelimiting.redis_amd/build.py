@@ -14,7 +14,7 @@ import sys
 HERE = os.path.dirname(os.path.realpath(__file__))   # also when imported through the distributedratelimiting/ symlink
 ROOT = os.path.dirname(HERE)
 SOURCES = [os.path.join(HERE, "csrc", n) for n in ("tbe_engine.hip", "tbe_tools.hip", "tbe_cluster.hip", "tbe_strdir.hip")]
-DEPS = SOURCES + [os.path.join(HERE, "csrc", n) for n in ("tbe_device.hpp", "tbe_codec.hpp", "tbe_numfmt.hpp", "tbe_hash.hpp", "tbe_retry.hpp", "tbe_idpool.hpp", "tbe_stats.hpp")] + \
+DEPS = SOURCES + [os.path.join(HERE, "csrc", n) for n in ("tbe_device.hpp", "tbe_codec.hpp", "tbe_numfmt.hpp", "tbe_hash.hpp", "tbe_retry.hpp", "tbe_idpool.hpp", "tbe_stats.hpp", "tbe_text.hpp")] + \
     [os.path.join(ROOT, "include", n) for n in ("tbe.h", "tbe_tools.h", "tbe_cluster.h", "tbe_strdir.h")]
 LIB = os.path.join(HERE, "libtbe.so")
 ARCH = "gfx950"

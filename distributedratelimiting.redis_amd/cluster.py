@@ -20,6 +20,10 @@ Exchanges:
   a valid serial order of the reference) and the replies come back in a reverse
   all-to-all.  On GPUs everything stays in HBM (``tbe_route_*`` kernels + RCCL); only the
   world group sizes go through the host, as the all-to-all's split sizes.
+* ``route_text_requests`` / ``route_text_batch``: the same for a batch keyed by text (the
+  reference's own strings): the owner follows from a 64-bit routing key of the text
+  (``text_route_keys``), every string travels with its bytes (a third all-to-all), and the
+  owner's string directory resolves them byte for byte (DESIGN.md §7 "Routing text").
 * ``route_cancel``: cancellations of queued requests travel to the key's owner the same
   way (one all-to-all each way).
 * ``approx_epoch``: the ApproximateTokenBucket global tier.  Each rank is one client
@@ -534,8 +538,12 @@ class RoutePlan:
     """What route_replies needs to send replies back: the arrival -> grouped permutation
     and the all-to-all split sizes of both directions."""
 
-    def __init__(self, order, send_counts, recv_counts, n):
+    def __init__(self, order, send_counts, recv_counts, n, error=None):
         self.order, self.send_counts, self.recv_counts, self.n = order, send_counts, recv_counts, n
+        # route_text_requests: this rank's batch was malformed and none of it was sent (n is 0
+        # then); the rank still takes part in the reply exchange, and route_text_batch raises
+        # this afterwards
+        self.error = error
 
 
 def _is_cuda(x) -> bool:
@@ -667,6 +675,280 @@ def route_batch(decide: Callable, keys, permits, ts_us, directory, group=None, o
     (lk, lp, lt), plan = route_requests(keys, permits, ts_us, directory, group, owner_map)
     cols = decide(lk, lp, lt)
     out = route_replies(plan, cols, group)
+    if _is_cuda(out[0]):
+        import torch
+        return (out[0].to(torch.uint8), out[1].to(torch.int32)) + tuple(out[2:])
+    return (out[0].astype(np.uint8), out[1].astype(np.int32)) + tuple(out[2:])
+
+
+# ------------------------------------------------------------------ routing text
+TEXT_MAX_LEN = 1 << 16               # a key's longest text (include/tbe_strdir.h)
+
+
+def _text_spans(offs, n_bytes: int):
+    """(start, length, malformed) of every string of an Arrow-style array, by the string
+    directory's rules (sd_span): end < start, end > n_bytes or a length over 65536 is
+    malformed, and such a string reads as the empty string at offset 0."""
+    o = np.ascontiguousarray(offs)
+    o = o.view(np.uint64) if o.dtype == np.int64 else o.astype(np.uint64)
+    a, b = o[:-1], o[1:]
+    with np.errstate(over="ignore"):
+        ok = (b >= a) & (b <= np.uint64(n_bytes)) & (b - a <= np.uint64(TEXT_MAX_LEN))
+        zero = np.uint64(0)
+        return np.where(ok, a, zero).astype(np.int64), np.where(ok, b - a, zero).astype(np.int64), ~ok
+
+
+def _as_u8(buf) -> np.ndarray:
+    return np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray)) else np.asarray(buf, dtype=np.uint8)
+
+
+def text_route_keys(buf, offs, seed: int = 0, n_bytes: Optional[int] = None) -> np.ndarray:
+    """The u64 routing key of every string (include/tbe_cluster.h "routing text";
+    tbe_text_route_key, tbe_route_text_keys_device): h = mix64(seed ^ len * GAMMA), then h =
+    mix64(h ^ w_k) over the little-endian 8-byte words of the text, the last one zero-padded.
+    buf: uint8 array (or bytes), offs: n + 1 offsets, n_bytes: the bytes in use (default: all
+    of buf).  The owner of a string is ``key_owner`` / ``key_vnode`` of this key.  A malformed
+    string (``_text_spans``) hashes as the empty string."""
+    buf = _as_u8(buf)
+    nb = buf.shape[0] if n_bytes is None else int(n_bytes)
+    start, length, _ = _text_spans(offs, nb)
+    pad = np.zeros(nb + 8, dtype=np.uint8)
+    pad[:nb] = buf[:nb]
+    with np.errstate(over="ignore"):
+        h = _mix64(np.uint64(seed & MASK64) ^ (length.astype(np.uint64) * np.uint64(GAMMA)))
+    idx = np.flatnonzero(length > 0)
+    k = 0
+    while idx.size:
+        p = start[idx] + 8 * k
+        rem = length[idx] - 8 * k
+        w = np.zeros(idx.size, dtype=np.uint64)
+        for b in range(8):
+            w |= np.where(b < rem, pad[np.minimum(p + b, nb)], 0).astype(np.uint64) << np.uint64(8 * b)
+        h[idx] = _mix64(h[idx] ^ w)
+        idx = idx[rem > 8]
+        k += 1
+    return h
+
+
+def plan_text_route(buf, offs, world: int, owner_map=None, seed: int = 0, n_bytes: Optional[int] = None) -> dict:
+    """What one rank sends when a batch keyed by text is routed: the rule of
+    tbe_route_text_keys_device, tbe_route_plan_map_device, tbe_route_text_offsets_device and
+    tbe_route_text_pack_device in numpy, their reference and the body of the host path.
+    Returns keys (u64), n_bad, lens (int64, arrival order), order (grouped -> arrival), pos
+    (arrival -> grouped), counts and byte_counts (int64 [world]), send_offs (int64 [n + 1]) and
+    out_bytes (uint8 [send_offs[n]]: every owner's strings, arrival order, tightly packed)."""
+    buf = _as_u8(buf)
+    nb = buf.shape[0] if n_bytes is None else int(n_bytes)
+    start, lens, bad = _text_spans(offs, nb)
+    n = lens.shape[0]
+    keys = text_route_keys(buf, offs, seed, nb)
+    owner = key_owner(keys, world, owner_map) if n else np.zeros(0, dtype=np.int64)
+    order = np.argsort(owner, kind="stable")
+    pos = np.empty(n, dtype=np.int64)
+    pos[order] = np.arange(n, dtype=np.int64)
+    counts = np.bincount(owner, minlength=world).astype(np.int64)
+    send_offs = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens[order], out=send_offs[1:])
+    src = np.repeat(start[order] - send_offs[:-1], lens[order]) + np.arange(int(send_offs[-1]), dtype=np.int64)
+    byte_counts = np.bincount(owner, weights=lens, minlength=world).astype(np.int64)
+    return {"keys": keys, "n_bad": int(bad.sum()), "lens": lens, "order": order, "pos": pos, "counts": counts,
+            "byte_counts": byte_counts, "send_offs": send_offs, "out_bytes": buf[src]}
+
+
+def _malformed(n_bad: int) -> ValueError:
+    return ValueError(f"route_text: {n_bad} strings of the batch have malformed offsets (end < start, end > n_bytes "
+                      f"or longer than {TEXT_MAX_LEN} bytes); none of the batch was sent")
+
+
+def route_text_requests(buf, offs, permits, ts_us, directory, group=None, owner_map=None, seed: int = 0,
+                        n_bytes: Optional[int] = None):
+    """``route_requests`` for a batch keyed by text (DESIGN.md §7 "Routing text"): an
+    Arrow-style string array -- buf (uint8), offs (n + 1 offsets), n_bytes (default: all of
+    buf) -- with permits and ts_us.  Each string goes to the owner of its routing key
+    (``text_route_keys``; owner maps apply to that key as to any u64), carrying its text; the
+    owner's string directory resolves the received strings byte for byte.  Returns what
+    ``route_requests`` returns, and ``route_replies`` takes the plan as it is.
+
+    CUDA tensors and a ``StringDirectory``: tbe_route_text_* kernels; text, offsets and records
+    stay in HBM, only the per-owner row and byte counts cross to the host.  numpy arrays and a
+    ``HostStringDirectory``: the same protocol on the host (gloo).  Three all-to-alls: the
+    {rows, bytes} counts together, the {len, ts_us, permits} rows, the bytes.
+
+    A batch with malformed offsets (``_text_spans``) is not sent: this rank announces zero
+    counts, takes part in every exchange (it still decides what the other ranks send it), and
+    the returned plan carries a ValueError in ``plan.error`` and describes an empty batch
+    (``plan.n`` = 0, an empty ``order``, zero send counts), so ``route_replies`` on it returns
+    empty columns on either path.  The other ranks are unaffected.
+
+    The device path synchronises with the host three times per batch: the sender's counts, the
+    received counts, and ``StringDirectory.size()`` after the assign (the directory's only
+    overflow check)."""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    if owner_map is not None and not _is_cuda(owner_map):
+        check_owner_map(owner_map, world)
+    if _is_cuda(buf):
+        if not hasattr(directory, "text_of"):
+            raise TypeError("route_text_requests with CUDA tensors needs a StringDirectory")
+        return _route_text_device(buf, offs, permits, ts_us, directory, world, group, owner_map, seed, n_bytes)
+    return _route_text_host(buf, offs, permits, ts_us, directory, world, group, owner_map, seed, n_bytes)
+
+
+def _route_text_host(buf, offs, permits, ts_us, directory, world, group, owner_map, seed, n_bytes):
+    import torch
+    import torch.distributed as dist
+    from . import _capi
+    buf = _as_u8(buf)
+    p = plan_text_route(buf, offs, world, owner_map, seed, n_bytes)
+    n = p["lens"].shape[0]
+    error = _malformed(p["n_bad"]) if p["n_bad"] else None
+    order = p["order"]
+    if error is None:
+        sc2 = np.stack([p["counts"], p["byte_counts"]], axis=1)
+        rows = np.stack([p["lens"][order], np.asarray(ts_us, dtype=np.int64)[order],
+                         np.asarray(permits, dtype=np.int64)[order]], axis=1)
+        out_bytes = p["out_bytes"]
+    else:
+        sc2 = np.zeros((world, 2), dtype=np.int64)
+        rows, out_bytes = np.zeros((0, 3), dtype=np.int64), np.zeros(0, dtype=np.uint8)
+    sc = torch.from_numpy(np.ascontiguousarray(sc2).reshape(-1))
+    rc = torch.empty_like(sc)
+    dist.all_to_all_single(rc, sc, group=group)
+    rc2 = rc.numpy().reshape(world, 2)
+    sc_rows, sc_bytes = sc2[:, 0].tolist(), sc2[:, 1].tolist()
+    rc_rows, rc_bytes = rc2[:, 0].tolist(), rc2[:, 1].tolist()
+    recv = torch.empty((sum(rc_rows), 3), dtype=torch.int64)
+    dist.all_to_all_single(recv, torch.from_numpy(np.ascontiguousarray(rows)), output_split_sizes=rc_rows,
+                           input_split_sizes=sc_rows, group=group)
+    recv_bytes = torch.empty(sum(rc_bytes), dtype=torch.uint8)
+    dist.all_to_all_single(recv_bytes, torch.from_numpy(np.ascontiguousarray(out_bytes)), output_split_sizes=rc_bytes,
+                           input_split_sizes=sc_bytes, group=group)
+    r = recv.numpy()
+    roffs = np.zeros(r.shape[0] + 1, dtype=np.int64)
+    np.cumsum(r[:, 0], out=roffs[1:])
+    blob = recv_bytes.numpy().tobytes()
+    local = directory.assign([blob[roffs[j]:roffs[j + 1]] for j in range(r.shape[0])])
+    if directory.overflow:
+        raise _capi.TbeError(_capi.TBE_ERANGE, f"string directory over capacity ({directory.capacity} ids)")
+    if error is not None:        # nothing was sent: the plan describes an empty batch
+        order, n = order[:0], 0
+    return (local, r[:, 2].astype(np.int32), r[:, 1].copy()), RoutePlan(order, sc_rows, rc_rows, n, error)
+
+
+def _text_columns(buf, offs, n_bytes):
+    """The device path's text contract: buf uint8, offs int64 (uint64 is reinterpreted) with
+    n + 1 entries on buf's device, n_bytes within buf.  The kernels read the text in 8-byte
+    words, so a buffer that does not start on an 8-byte boundary (a slice of a larger byte
+    tensor) is copied to one that does."""
+    import torch
+    if buf.dtype != torch.uint8:
+        raise TypeError(f"text bytes must be a uint8 tensor, not {buf.dtype}")
+    if offs.dtype == torch.uint64:
+        offs = offs.view(torch.int64)
+    if offs.dtype != torch.int64 or not _is_cuda(offs) or offs.device != buf.device or offs.numel() < 1:
+        raise TypeError("text offsets must be n + 1 int64 (or uint64) entries on the bytes' device")
+    nb = buf.numel() if n_bytes is None else int(n_bytes)
+    if not 0 <= nb <= buf.numel():
+        raise ValueError("n_bytes exceeds the byte buffer")
+    buf = buf.contiguous()
+    if buf.data_ptr() % 8:
+        buf = buf.clone()
+    return buf, offs.contiguous(), nb
+
+
+def _text_keys_device(lib, buf, offs, nb, seed, stream):
+    """(int64 routing keys, one-element int64 count of malformed strings), both on the device."""
+    import torch
+    n = offs.numel() - 1
+    keys = torch.empty(max(n, 1), dtype=torch.int64, device=buf.device)
+    n_bad = torch.zeros(1, dtype=torch.int64, device=buf.device)
+    _check(lib.tbe_route_text_keys_device(buf.data_ptr(), nb, offs.data_ptr(), n, int(seed) & MASK64, keys.data_ptr(),
+                                          n_bad.data_ptr(), stream))
+    return keys[:n], n_bad
+
+
+def text_vnode_loads(d_bytes, d_offs, seed: int = 0, n_bytes: Optional[int] = None):
+    """``vnode_loads`` of a device batch keyed by text: requests per virtual node of the
+    strings' routing keys, int64 [4096] -- what ``balanced_owner_map`` builds a map for text
+    traffic from."""
+    from . import _capi
+    lib = _capi.load()
+    d_bytes, d_offs, nb = _text_columns(d_bytes, d_offs, n_bytes)
+    keys, _ = _text_keys_device(lib, d_bytes, d_offs, nb, seed, device_stream(d_bytes.device))
+    return vnode_loads(keys)
+
+
+def _route_text_device(buf, offs, permits, ts_us, directory, world, group, owner_map, seed, n_bytes):
+    """route_text_requests on the device: keys, plan, send offsets and pack (tbe_route_text_*),
+    the counts, rows and bytes by all-to-all, the receiver's offsets, the directory."""
+    import torch
+    from . import _capi
+    lib = _capi.load()
+    buf, offs, nb = _text_columns(buf, offs, n_bytes)
+    dev = buf.device
+    stream = device_stream(dev)
+    n = offs.numel() - 1
+    cols = []
+    for c, dt in ((permits, torch.int32), (ts_us, torch.int64)):
+        if not _is_cuda(c) or c.device != dev:
+            raise ValueError("every column of a device-path batch must be on the bytes' device")
+        if c.numel() != n:
+            raise ValueError("columns differ in length")
+        cols.append(c.to(dt).contiguous())
+    permits, ts_us = cols
+    keys, n_bad = _text_keys_device(lib, buf, offs, nb, seed, stream)
+    pos = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    counts = torch.zeros(world, dtype=torch.int64, device=dev)
+    byte_counts = torch.zeros(world, dtype=torch.int64, device=dev)
+    work = torch.empty(max(8, lib.tbe_route_workspace_bytes(n, world), lib.tbe_route_text_workspace_bytes(n)),
+                       dtype=torch.uint8, device=dev)
+    dmap = _device_map(owner_map, dev, world)
+    _check(lib.tbe_route_plan_map_device(keys.data_ptr(), n, world, dmap.data_ptr() if dmap is not None else None,
+                                         work.data_ptr(), pos.data_ptr(), counts.data_ptr(), stream))
+    send_offs = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    _check(lib.tbe_route_text_offsets_device(offs.data_ptr(), nb, n, pos.data_ptr(), counts.data_ptr(), world,
+                                             work.data_ptr(), send_offs.data_ptr(), byte_counts.data_ptr(), stream))
+    send_bytes = torch.empty((nb + 7) // 8 * 8 + 8, dtype=torch.uint8, device=dev)
+    rows = torch.empty((n, 3), dtype=torch.int64, device=dev)
+    _check(lib.tbe_route_text_pack_device(buf.data_ptr(), nb, offs.data_ptr(), n, pos.data_ptr(), send_offs.data_ptr(),
+                                          permits.data_ptr(), ts_us.data_ptr(), send_bytes.data_ptr(),
+                                          send_bytes.numel(), rows.data_ptr(), stream))
+    head = torch.cat([torch.stack([counts, byte_counts], dim=1).reshape(-1), n_bad]).tolist()
+    error = _malformed(head[-1]) if head[-1] else None
+    sc2 = [0] * (2 * world) if error else head[:-1]
+    sc = torch.tensor(sc2, dtype=torch.int64, device=dev)
+    rc = torch.empty_like(sc)
+    _all_to_all(rc, sc, group=group)
+    rc2 = rc.tolist()
+    sc_rows, sc_bytes, rc_rows, rc_bytes = sc2[0::2], sc2[1::2], rc2[0::2], rc2[1::2]
+    recv = torch.empty((sum(rc_rows), 3), dtype=torch.int64, device=dev)
+    _all_to_all(recv, rows[:sum(sc_rows)], rc_rows, sc_rows, group=group)
+    mb = sum(rc_bytes)
+    recv_bytes = torch.empty((mb + 7) // 8 * 8 + 8, dtype=torch.uint8, device=dev)
+    recv_bytes[mb:] = 0
+    _all_to_all(recv_bytes[:mb], send_bytes[:sum(sc_bytes)], rc_bytes, sc_bytes, group=group)
+    m = recv.shape[0]
+    roffs = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    rwork = torch.empty(max(8, lib.tbe_route_text_workspace_bytes(m)), dtype=torch.uint8, device=dev)
+    _check(lib.tbe_route_text_recv_offsets_device(recv.data_ptr(), m, rwork.data_ptr(), roffs.data_ptr(), stream))
+    local = directory.assign(recv_bytes, roffs, mb)
+    directory.size()             # raises once a batch has overflowed the directory, before anything is decided
+    if error is not None:        # nothing was sent: the plan describes an empty batch
+        pos, n = pos[:0], 0
+    return (local, recv[:, 2].to(torch.int32), recv[:, 1].contiguous()), RoutePlan(pos, sc_rows, rc_rows, n, error)
+
+
+def route_text_batch(decide: Callable, buf, offs, permits, ts_us, directory, group=None, owner_map=None,
+                     seed: int = 0, n_bytes: Optional[int] = None):
+    """``route_batch`` for a batch keyed by text: ``route_text_requests``, ``decide`` on the
+    requests this rank owns, ``route_replies``.  A rank whose batch is malformed still decides
+    what it receives and takes part in the reply exchange, then raises ValueError with nothing
+    of its own batch decided."""
+    (lk, lp, lt), plan = route_text_requests(buf, offs, permits, ts_us, directory, group, owner_map, seed, n_bytes)
+    cols = decide(lk, lp, lt)
+    out = route_replies(plan, cols, group)
+    if plan.error is not None:
+        raise plan.error
     if _is_cuda(out[0]):
         import torch
         return (out[0].to(torch.uint8), out[1].to(torch.int32)) + tuple(out[2:])

@@ -18,6 +18,7 @@
 #include "tbe_device.hpp"
 #include "tbe_hash.hpp"
 #include "tbe_idpool.hpp"
+#include "tbe_text.hpp"
 
 using namespace tbe;
 
@@ -177,6 +178,206 @@ __global__ void k_route_gather(const uint32_t *__restrict__ pos, uint64_t n, con
         const uint64_t q = (uint64_t)pos[i] * cols;
         for (uint32_t c = 0; c < cols; ++c) out[i * cols + c] = in[q + c];
     }
+}
+
+// ---------------------------------------------------------------- routing text
+// A batch keyed by text (include/tbe_cluster.h "Routing text") is grouped by the owner of
+// H(text, seed), and each string travels with its bytes: the send buffer holds the strings
+// of owner 0, 1, ... tightly packed, arrival order inside an owner, so string i lands at
+// send_offs[pos[i]], the exclusive scan of the lengths in grouped order.  The scan is three
+// launches (block sums, one workgroup over the sums, write), as the directories' scans are.
+constexpr uint32_t kRtMaxLen = 1u << 16;   // a key's longest text (sd_span, tbe_strdir.hip)
+constexpr int kTxBlock = 256;
+constexpr int kTxTile = 1024;              // lengths per scan block (4 per thread)
+
+// Span of string i by sd_span's rules; a malformed one reads as the empty string (false).
+__device__ __forceinline__ bool rt_span(const uint64_t *__restrict__ offs, uint64_t i, uint64_t n_bytes,
+                                        uint64_t &off, uint32_t &len) {
+    const uint64_t a = offs[i], b = offs[i + 1];
+    const bool ok = b >= a && b <= n_bytes && b - a <= kRtMaxLen;
+    off = ok ? a : 0ull;
+    len = ok ? (uint32_t)(b - a) : 0u;
+    return ok;
+}
+
+__global__ __launch_bounds__(kTxBlock) void k_rt_text_keys(const uint8_t *__restrict__ bytes, uint64_t n_bytes,
+                                                           const uint64_t *__restrict__ offs, uint64_t n,
+                                                           uint64_t seed, uint64_t *__restrict__ keys,
+                                                           unsigned long long *__restrict__ n_bad) {
+    const uint64_t safe = n_bytes & ~7ull;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        uint64_t off;
+        uint32_t len;
+        if (!rt_span(offs, i, n_bytes, off, len)) atomicAdd(n_bad, 1ull);
+        keys[i] = sd_hash(bytes, safe, off, len, seed);
+    }
+}
+
+// lens[pos[i]] = length of string i: the lengths in owner-grouped order.
+__global__ __launch_bounds__(kTxBlock) void k_rt_len_scatter(const uint64_t *__restrict__ offs, uint64_t n,
+                                                             uint64_t n_bytes, const uint32_t *__restrict__ pos,
+                                                             uint32_t *__restrict__ lens) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        uint64_t off;
+        uint32_t len;
+        (void)rt_span(offs, i, n_bytes, off, len);
+        const uint32_t p = pos[i];
+        if (p < n) lens[p] = len;
+    }
+}
+
+// Where the scan reads length j: the scattered lengths of the sender, column 0 of the
+// receiver's rows (a length outside 0..65536 counts as 65536: the directory then refuses the
+// batch, whose offsets pass its bytes).
+struct LenOfList {
+    const uint32_t *lens;
+    __device__ uint32_t operator()(uint64_t j) const { return lens[j]; }
+};
+struct LenOfRows {
+    const int64_t *rows;
+    __device__ uint32_t operator()(uint64_t j) const {
+        const uint64_t v = (uint64_t)rows[3 * j];
+        return v > kRtMaxLen ? kRtMaxLen : (uint32_t)v;
+    }
+};
+
+// Bytes per block of kTxTile lengths (thread-contiguous; at most 2^26).
+template <class Len>
+__global__ __launch_bounds__(kTxBlock) void k_rt_len_count(Len len_of, uint64_t n, uint32_t *__restrict__ bsum) {
+    __shared__ uint32_t wsum[kTxBlock / 64];
+    constexpr int PER = kTxTile / kTxBlock;
+    const uint64_t base = (uint64_t)blockIdx.x * kTxTile + (uint64_t)threadIdx.x * PER;
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) c += base + k < n ? len_of(base + k) : 0u;
+    uint32_t tot;
+    (void)block_excl_scan<kTxBlock>(c, wsum, &tot);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+
+// One workgroup: bbase[b] (u64) = bytes before block b; offs_out[n] = all bytes.
+__global__ __launch_bounds__(kScanThreads) void k_rt_len_scan(const uint32_t *__restrict__ bsum, uint32_t nblk,
+                                                              uint64_t *__restrict__ bbase,
+                                                              uint64_t *__restrict__ total) {
+    __shared__ unsigned long long part[kScanThreads];
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (nblk + kScanThreads - 1) / kScanThreads;
+    unsigned long long s = 0;
+    for (uint32_t k = 0; k < per; ++k) {
+        const uint32_t j = t * per + k;
+        if (j < nblk) s += bsum[j];
+    }
+    part[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        unsigned long long acc = 0;
+        for (uint32_t k = 0; k < kScanThreads; ++k) {
+            const unsigned long long v = part[k];
+            part[k] = acc;
+            acc += v;
+        }
+        *total = acc;
+    }
+    __syncthreads();
+    unsigned long long run = part[t];
+    for (uint32_t k = 0; k < per; ++k) {
+        const uint32_t j = t * per + k;
+        if (j < nblk) {
+            bbase[j] = run;
+            run += bsum[j];
+        }
+    }
+}
+
+// offs_out[j] = bytes before length j.
+template <class Len>
+__global__ __launch_bounds__(kTxBlock) void k_rt_len_write(Len len_of, uint64_t n, const uint64_t *__restrict__ bbase,
+                                                           uint64_t *__restrict__ offs_out) {
+    __shared__ uint32_t wsum[kTxBlock / 64];
+    constexpr int PER = kTxTile / kTxBlock;
+    const uint64_t base = (uint64_t)blockIdx.x * kTxTile + (uint64_t)threadIdx.x * PER;
+    uint32_t l[PER], c = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        l[k] = base + k < n ? len_of(base + k) : 0u;
+        c += l[k];
+    }
+    uint32_t tot;
+    uint64_t at = bbase[blockIdx.x] + block_excl_scan<kTxBlock>(c, wsum, &tot);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        if (base + k < n) offs_out[base + k] = at;
+        at += l[k];
+    }
+}
+
+// Bytes per owner: the span of its group in the send offsets (counts: tbe_route_plan_map_device's).
+__global__ __launch_bounds__(kMaxOwners) void k_rt_owner_bytes(const uint64_t *__restrict__ counts, uint32_t G,
+                                                               uint64_t n, const uint64_t *__restrict__ send_offs,
+                                                               uint64_t *__restrict__ byte_counts) {
+    const uint32_t o = threadIdx.x;
+    if (o >= G) return;
+    uint64_t start = 0;
+    for (uint32_t j = 0; j < o; ++j) start += counts[j];
+    const uint64_t a = min(start, n), b = min(start + counts[o], n);
+    byte_counts[o] = send_offs[b] - send_offs[a];
+}
+
+// String i to out_bytes[send_offs[pos[i]] ..) and its record {len, ts_us, permits} to row
+// pos[i].  Neighbouring strings share the 8-byte granules of the destination, so a thread
+// stores whole words only where all eight bytes are its own string's: the bytes up to the
+// first 8-byte boundary and those after the last one go out one by one.  The source is
+// read through sd_word (8 bytes at any alignment, never outside [0, n_bytes)).  A string
+// that would pass out_cap is left out (a malformed batch's spans may overlap).
+__global__ __launch_bounds__(kTxBlock) void k_rt_text_pack(const uint8_t *__restrict__ bytes, uint64_t n_bytes,
+                                                           const uint64_t *__restrict__ offs, uint64_t n,
+                                                           const uint32_t *__restrict__ pos,
+                                                           const uint64_t *__restrict__ send_offs,
+                                                           const int32_t *__restrict__ permits,
+                                                           const int64_t *__restrict__ ts,
+                                                           uint8_t *__restrict__ out, uint64_t out_cap,
+                                                           int64_t *__restrict__ rows) {
+    const uint64_t safe = n_bytes & ~7ull;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        uint64_t off;
+        uint32_t len;
+        (void)rt_span(offs, i, n_bytes, off, len);
+        const uint64_t p = pos[i];
+        if (p >= n) continue;
+        rows[3 * p] = len;
+        rows[3 * p + 1] = ts[i];
+        rows[3 * p + 2] = permits[i];
+        const uint64_t d = send_offs[p];
+        if (len == 0 || d > out_cap || out_cap - d < len) continue;
+        const uint32_t lead = min(len, (uint32_t)((8u - (uint32_t)(d & 7)) & 7u));
+        if (lead) {
+            const uint64_t w = sd_word(bytes, safe, off, len, 0);
+            for (uint32_t b = 0; b < lead; ++b) out[d + b] = (uint8_t)(w >> (8 * b));
+        }
+        const uint64_t o2 = off + lead, d2 = d + lead;   // d2 is 8-byte aligned (or the string has ended)
+        const uint32_t l2 = len - lead;
+        for (uint32_t k = 0; 8u * k < l2; ++k) {
+            const uint64_t w = sd_word(bytes, safe, o2, l2, k);
+            const uint32_t rem = l2 - 8u * k;
+            if (rem >= 8) {
+                *reinterpret_cast<uint64_t *>(out + d2 + 8ull * k) = w;
+            } else {
+                for (uint32_t b = 0; b < rem; ++b) out[d2 + 8ull * k + b] = (uint8_t)(w >> (8 * b));
+            }
+        }
+    }
+}
+
+// The exclusive scan of n lengths into d_offs[n + 1] (n > 0); bbase and bsum: nblk entries each.
+template <class Len>
+void text_scan(Len len_of, uint64_t n, uint64_t *bbase, uint32_t *bsum, uint64_t *d_offs, hipStream_t st) {
+    const uint32_t nblk = (uint32_t)((n + kTxTile - 1) / kTxTile);
+    k_rt_len_count<<<nblk, kTxBlock, 0, st>>>(len_of, n, bsum);
+    k_rt_len_scan<<<1, kScanThreads, 0, st>>>(bsum, nblk, bbase, d_offs + n);
+    k_rt_len_write<<<nblk, kTxBlock, 0, st>>>(len_of, n, bbase, d_offs);
 }
 
 // ---------------------------------------------------------------- directory
@@ -546,6 +747,78 @@ tbe_status tbe_route_gather_device(const uint32_t *d_pos, uint64_t n, const int6
     if (n == 0) return TBE_OK;
     if (!d_pos || !d_in || !d_out || cols == 0 || cols > 8) return TBE_EINVAL;
     k_route_gather<<<grid_for(n, 256), 256, 0, (hipStream_t)stream>>>(d_pos, n, d_in, cols, d_out);
+    return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
+}
+
+uint64_t tbe_text_route_key(const uint8_t *text, uint64_t len, uint64_t seed) {
+    return text_hash_host(text, text ? len : 0, seed);
+}
+
+tbe_status tbe_route_text_keys_device(const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *d_offs, uint64_t n,
+                                      uint64_t seed, uint64_t *d_keys, uint64_t *d_n_bad, void *stream) {
+    if (!d_n_bad || n >= (1ull << 32) || (reinterpret_cast<uintptr_t>(d_bytes) & 7u)) return TBE_EINVAL;
+    if (n && (!d_offs || !d_keys || (n_bytes && !d_bytes))) return TBE_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(d_n_bad, 0, sizeof(uint64_t), st) != hipSuccess) return TBE_EDEVICE;
+    if (n == 0) return TBE_OK;
+    k_rt_text_keys<<<grid_for(n, kTxBlock), kTxBlock, 0, st>>>(d_bytes, n_bytes, d_offs, n, seed, d_keys,
+                                                               reinterpret_cast<unsigned long long *>(d_n_bad));
+    return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
+}
+
+uint64_t tbe_route_text_workspace_bytes(uint64_t n) {
+    const uint64_t nblk = (n + kTxTile - 1) / kTxTile;
+    return nblk * (sizeof(uint64_t) + sizeof(uint32_t)) + n * sizeof(uint32_t);
+}
+
+tbe_status tbe_route_text_offsets_device(const uint64_t *d_offs, uint64_t n_bytes, uint64_t n, const uint32_t *d_pos,
+                                         const uint64_t *d_counts, uint32_t n_owners, void *d_work,
+                                         uint64_t *d_send_offs, uint64_t *d_byte_counts, void *stream) {
+    if (n_owners == 0 || n_owners > kMaxOwners || n >= (1ull << 32) || !d_send_offs || !d_byte_counts)
+        return TBE_EINVAL;
+    if (n && (!d_offs || !d_pos || !d_counts || !d_work || (reinterpret_cast<uintptr_t>(d_work) & 7u)))
+        return TBE_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0)
+        return hipMemsetAsync(d_send_offs, 0, sizeof(uint64_t), st) == hipSuccess &&
+                       hipMemsetAsync(d_byte_counts, 0, n_owners * sizeof(uint64_t), st) == hipSuccess
+                   ? TBE_OK
+                   : TBE_EDEVICE;
+    const uint64_t nblk = (n + kTxTile - 1) / kTxTile;
+    uint64_t *bbase = static_cast<uint64_t *>(d_work);
+    uint32_t *bsum = reinterpret_cast<uint32_t *>(bbase + nblk);
+    uint32_t *lens = bsum + nblk;
+    k_rt_len_scatter<<<grid_for(n, kTxBlock), kTxBlock, 0, st>>>(d_offs, n, n_bytes, d_pos, lens);
+    text_scan(LenOfList{lens}, n, bbase, bsum, d_send_offs, st);
+    k_rt_owner_bytes<<<1, kMaxOwners, 0, st>>>(d_counts, n_owners, n, d_send_offs, d_byte_counts);
+    return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
+}
+
+tbe_status tbe_route_text_pack_device(const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *d_offs, uint64_t n,
+                                      const uint32_t *d_pos, const uint64_t *d_send_offs, const int32_t *d_permits,
+                                      const int64_t *d_ts_us, uint8_t *d_out_bytes, uint64_t out_capacity,
+                                      int64_t *d_out_rows, void *stream) {
+    if (n >= (1ull << 32) || (reinterpret_cast<uintptr_t>(d_bytes) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_out_bytes) & 7u))
+        return TBE_EINVAL;
+    if (n == 0) return TBE_OK;
+    if (!d_offs || !d_pos || !d_send_offs || !d_permits || !d_ts_us || !d_out_rows || (n_bytes && !d_bytes) ||
+        (out_capacity && !d_out_bytes))
+        return TBE_EINVAL;
+    k_rt_text_pack<<<grid_for(n, kTxBlock), kTxBlock, 0, (hipStream_t)stream>>>(
+        d_bytes, n_bytes, d_offs, n, d_pos, d_send_offs, d_permits, d_ts_us, d_out_bytes, out_capacity, d_out_rows);
+    return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
+}
+
+tbe_status tbe_route_text_recv_offsets_device(const int64_t *d_rows, uint64_t m, void *d_work, uint64_t *d_offs,
+                                              void *stream) {
+    if (!d_offs || m >= (1ull << 32)) return TBE_EINVAL;
+    if (m && (!d_rows || !d_work || (reinterpret_cast<uintptr_t>(d_work) & 7u))) return TBE_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (m == 0) return hipMemsetAsync(d_offs, 0, sizeof(uint64_t), st) == hipSuccess ? TBE_OK : TBE_EDEVICE;
+    const uint64_t nblk = (m + kTxTile - 1) / kTxTile;
+    uint64_t *bbase = static_cast<uint64_t *>(d_work);
+    text_scan(LenOfRows{d_rows}, m, bbase, reinterpret_cast<uint32_t *>(bbase + nblk), d_offs, st);
     return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
 }
 

@@ -31,7 +31,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from .cluster import key_owner
+from .cluster import key_owner, text_route_keys
 
 FORMAT_VERSION = 1
 ABSENT = np.iinfo(np.int64).min
@@ -179,9 +179,10 @@ def _form_of(directory) -> str:
 def merge(paths: Sequence, config, form: str, owner: Optional[Tuple] = None) -> dict:
     """The host half of ``load``: read the shard files in the order given, check each
     against the engine's options and the directory's key form, keep the rows of `owner`
-    and refuse a key that occurs twice.  Returns {form, v, t_us, keys | ids | text}, rows
-    in file order, plus p for an approximate engine.  Raises ValueError as ``load``
-    documents."""
+    (u64 keys by ``key_owner``; text by ``key_owner`` of ``text_route_keys(text, seed)``, seed
+    being the optional fourth entry of `owner`, default 0) and refuse a key that occurs twice.
+    Returns {form, v, t_us, keys | ids | text}, rows in file order, plus p for an approximate
+    engine.  Raises ValueError as ``load`` documents."""
     if isinstance(paths, (str, bytes, os.PathLike)):
         paths = [paths]
     want = option_meta(config, 0)
@@ -212,11 +213,17 @@ def merge(paths: Sequence, config, form: str, owner: Optional[Tuple] = None) -> 
         blob = b"".join(s["text"][0].tobytes() for s in shards)
         offs = np.zeros(lens.shape[0] + 1, dtype=np.int64)
         np.cumsum(lens, out=offs[1:])
-        if owner is not None:
-            raise ValueError("owner= selects by u64 key; text-keyed snapshots have none")
         texts = [blob[offs[i]:offs[i + 1]] for i in range(lens.shape[0])]
         if len(set(texts)) != len(texts):
             raise ValueError("a key occurs twice across the shards")
+        if owner is not None:            # by the routing key of the text (cluster.text_route_keys)
+            rank, world, owner_map = owner[:3]
+            seed = int(owner[3]) if len(owner) > 3 else 0
+            keep = key_owner(text_route_keys(blob, offs, seed), int(world), owner_map) == int(rank)
+            v, t_us, lens = v[keep], t_us[keep], lens[keep]
+            blob = b"".join(t for t, k in zip(texts, keep.tolist()) if k)
+            offs = np.zeros(lens.shape[0] + 1, dtype=np.int64)
+            np.cumsum(lens, out=offs[1:])
         out["text"] = (np.frombuffer(blob, dtype=np.uint8), offs.astype(np.uint64))
     else:
         k = np.concatenate([s[form] for s in shards]) if shards else np.zeros(0, dtype=np.uint64)
@@ -225,7 +232,7 @@ def merge(paths: Sequence, config, form: str, owner: Optional[Tuple] = None) -> 
         if owner is not None:
             if form != "keys":
                 raise ValueError("owner= selects by u64 key; id-keyed snapshots have none")
-            rank, world, owner_map = owner
+            rank, world, owner_map = owner[:3]
             keep = key_owner(k, int(world), owner_map) == int(rank)
             k, v, t_us = k[keep], v[keep], t_us[keep]
         out[form] = k
@@ -310,8 +317,10 @@ def load(paths, engine, directory=None, owner: Optional[Tuple] = None, stream: O
     order (which is the order the directory first sees the keys in, hence their ids).
     Raises ValueError when a file's token_limit or fill-rate bits differ from the engine's,
     when its key form does not match the directory, or when a key occurs twice across the
-    shards; nothing is imported then.  owner=(rank, world, owner_map_or_None) keeps only the
-    rows with ``cluster.key_owner(keys, world, owner_map) == rank`` (u64 keys only).  The
+    shards; nothing is imported then.  owner=(rank, world, owner_map_or_None[, seed]) keeps only
+    the rows with ``cluster.key_owner(keys, world, owner_map) == rank``, for a text-keyed file
+    with keys = ``cluster.text_route_keys(text, seed)`` (the key ``route_text_batch`` routes
+    by; seed defaults to 0), so text-keyed state re-shards as u64-keyed state does.  The
     kept keys are assigned through the directory and the rows imported under the resulting
     ids (``import_rows``), ordered before every batch enqueued afterwards.  An
     ``ApproximateEngine`` takes approximate-kind files only (and the other kinds none of

@@ -15,7 +15,9 @@
  * tbe_route_gather_device puts the replies back in arrival order.  On the owner, a
  * device-resident key directory (tbe_dir_*) turns the owned global keys into dense local
  * bucket ids, collision-free (it compares whole keys).  Everything stays in HBM; only the
- * n_owners group sizes cross to the host (the all-to-all's split sizes).
+ * n_owners group sizes cross to the host (the all-to-all's split sizes).  A batch keyed by
+ * text instead of u64 keys is routed by a hash of the text and carries its bytes to the owner,
+ * whose string directory (tbe_strdir.h) resolves them ("routing text" below).
  *
  * All calls enqueue on `stream` (hipStream_t, NULL = the default stream) and return
  * TBE_OK, or TBE_EINVAL for bad arguments (nothing enqueued).
@@ -80,6 +82,65 @@ tbe_status tbe_route_pack_device(const uint32_t *d_pos, uint64_t n, const uint64
 /* Replies back to arrival order: out[i*cols + c] = in[pos[i]*cols + c], 1 <= cols <= 8. */
 tbe_status tbe_route_gather_device(const uint32_t *d_pos, uint64_t n, const int64_t *d_in, uint32_t cols,
                                    int64_t *d_out, void *stream);
+
+/* ---------------------------------------------------------------- routing text
+ * The reference's bucket key is a string (InstanceName + resourceID, PTB:42), and a batch
+ * keyed by text is an Arrow-style string array as tbe_sdir_assign_device takes it
+ * (tbe_strdir.h): d_bytes (8-byte aligned), d_offs[n + 1], n_bytes.  Its strings are routed
+ * by a 64-bit routing key
+ *
+ *   text_route_key(text, seed) = H(text, seed):  h = mix64(seed ^ len * 0x9E3779B97F4A7C15),
+ *   then h = mix64(h ^ w_k) over the little-endian 8-byte words w_k of the text, the last
+ *   one zero-padded
+ *
+ * (the hash the string directory tags its slots with), and owner(text) is the owner of that
+ * u64 exactly as above: tbe_key_owner, or d_owner_map[tbe_key_vnode(.)], so owner maps,
+ * tbe_vnode_count_device and a balanced map serve text unchanged.  `seed` lets each limiter
+ * (InstanceName) spread its names on its own.  Two strings with one routing key merely
+ * share an owner: each string travels with its text, and the owner's string directory
+ * compares bytes.  Sender, per batch: tbe_route_text_keys_device, tbe_route_plan_map_device
+ * over the keys, tbe_route_text_offsets_device, tbe_route_text_pack_device; the per-owner row
+ * and byte counts are the split sizes of the two all-to-alls (rows, bytes).  Receiver:
+ * tbe_route_text_recv_offsets_device, then tbe_sdir_assign_device over the received bytes.
+ * The replies return through tbe_route_gather_device as for u64 keys.
+ *
+ * A string whose offsets are malformed by tbe_strdir.h's rules (end < start, end > n_bytes,
+ * longer than 65536 bytes) is counted and treated as the empty string by every step; no
+ * step reads outside [0, n_bytes) whatever the offsets say.  n < 2^32; byte totals are u64;
+ * n == 0 is valid. */
+uint64_t tbe_text_route_key(const uint8_t *text, uint64_t len, uint64_t seed);
+
+/* d_keys[i] = routing key of string i; *d_n_bad (u64, device memory) = malformed strings. */
+tbe_status tbe_route_text_keys_device(const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *d_offs,
+                                      uint64_t n, uint64_t seed, uint64_t *d_keys, uint64_t *d_n_bad,
+                                      void *stream);
+
+/* The send offsets: d_send_offs[j] (u64, n + 1 of them) = bytes in front of the string at
+ * position j of the owner-grouped order (d_pos and d_counts: tbe_route_plan_map_device's),
+ * d_send_offs[n] = all bytes; d_byte_counts[o] (u64) = bytes of owner o's group.  d_work:
+ * tbe_route_text_workspace_bytes(n) bytes, 8-byte aligned. */
+uint64_t tbe_route_text_workspace_bytes(uint64_t n);
+tbe_status tbe_route_text_offsets_device(const uint64_t *d_offs, uint64_t n_bytes, uint64_t n,
+                                         const uint32_t *d_pos, const uint64_t *d_counts, uint32_t n_owners,
+                                         void *d_work, uint64_t *d_send_offs, uint64_t *d_byte_counts,
+                                         void *stream);
+
+/* Send buffers of the two all-to-alls: the text of string i at d_out_bytes[d_send_offs[pos[i]]
+ * ..), tightly packed (an owner's segment is the concatenation of its strings in arrival
+ * order), and d_out_rows[pos[i]] = {len, ts_us, permits} as three int64 (d_out_rows holds
+ * 3n): tbe_route_pack_device's record with the length in the key's place.  d_out_bytes is
+ * 8-byte aligned and holds out_capacity bytes; bytes outside [0, d_send_offs[n]) are left
+ * alone, and a string that would pass out_capacity is left out (only a malformed batch,
+ * whose spans may overlap, can need more than n_bytes). */
+tbe_status tbe_route_text_pack_device(const uint8_t *d_bytes, uint64_t n_bytes, const uint64_t *d_offs,
+                                      uint64_t n, const uint32_t *d_pos, const uint64_t *d_send_offs,
+                                      const int32_t *d_permits, const int64_t *d_ts_us, uint8_t *d_out_bytes,
+                                      uint64_t out_capacity, int64_t *d_out_rows, void *stream);
+
+/* The receiver's offsets: d_offs[m + 1] = exclusive scan of column 0 of the m received
+ * rows (a length outside 0..65536 counts as 65536).  d_work as above, for m. */
+tbe_status tbe_route_text_recv_offsets_device(const int64_t *d_rows, uint64_t m, void *d_work, uint64_t *d_offs,
+                                              void *stream);
 
 /* ---------------------------------------------------------------- key directory
  * Global key (any u64 but UINT64_MAX) -> dense local id in [0, capacity), assigned when a
