@@ -51,7 +51,7 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_approx_collect_classes", "tbe_approx_sync_classes", "tbe_approx_sync_classes_stream",
             "tbe_approx_refresh_classes",
             "tbe_refresh_classes", "tbe_refresh_classes_device", "tbe_wait_batch_tick_classes_device",
-            "tbe_migrate_out_device", "tbe_migrate_out")
+            "tbe_migrate_out_device", "tbe_migrate_out", "tbe_migrate_out_ids_device", "tbe_migrate_out_ids")
 # k_stats_batch's shape (csrc/tbe_stats.hpp): requests per workgroup trip and slots of its
 # LDS table; the tests size their cases by them
 STATS_TILE, STATS_SLOTS = 4096, 2048
@@ -198,6 +198,10 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_migrate_out.restype = c_int32
     lib.tbe_migrate_out.argtypes = [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_uint32, c_uint32,
                                     c_void_p, c_uint64, c_void_p, c_void_p, c_int32]
+    lib.tbe_migrate_out_ids_device.restype = c_int32
+    lib.tbe_migrate_out_ids_device.argtypes = lib.tbe_migrate_out_device.argtypes[:-1] + [c_void_p, c_void_p]
+    lib.tbe_migrate_out_ids.restype = c_int32
+    lib.tbe_migrate_out_ids.argtypes = lib.tbe_migrate_out.argtypes + [c_void_p]
     lib.tbe_wait_batch.restype = c_int32
     lib.tbe_wait_batch.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_int64, c_void_p,
                                    c_void_p, POINTER(c_uint64)]
@@ -370,6 +374,10 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_sdir_text_lengths_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]
     lib.tbe_sdir_text_device.restype = c_int32
     lib.tbe_sdir_text_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]
+    lib.tbe_sdir_route_keys_device.restype = c_int32
+    lib.tbe_sdir_route_keys_device.argtypes = [c_void_p, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]
+    lib.tbe_sdir_usage.restype = c_int32
+    lib.tbe_sdir_usage.argtypes = [c_void_p, POINTER(c_uint64)]
     lib.tbe_sdir_set_hash_bits.restype = c_int32
     lib.tbe_sdir_set_hash_bits.argtypes = [c_void_p, ctypes.c_uint32]
     lib.tbe_sdir_set_mode.restype = c_int32

@@ -1081,6 +1081,11 @@ def plan_migration(keys_of_id, v, t_us, cls, live, owner_map, world: int, rank: 
     bucket).  Returns (rows int64 [n, 4] grouped by destination ascending and by id inside
     one, counts int64 [world + 2]: rows per owner, leaving ids, orphans -- live rows whose id
     no key holds, never sent --, leaving uint8 [ids]).  A map entry >= world: ValueError."""
+    return _plan_migration(keys_of_id, v, t_us, cls, live, owner_map, world, rank)[:3]
+
+
+def _plan_migration(keys_of_id, v, t_us, cls, live, owner_map, world: int, rank: int):
+    """``plan_migration`` and, fourth, the ids of the rows in send order (int64)."""
     keys = np.ascontiguousarray(keys_of_id, dtype=np.uint64)
     n = keys.shape[0]
     if not 1 <= world <= 256 or not 0 <= rank < world:
@@ -1105,7 +1110,47 @@ def plan_migration(keys_of_id, v, t_us, cls, live, owner_map, world: int, rank: 
     counts[:world] = np.bincount(dest[send], minlength=world)
     counts[world] = int(leaving.sum())
     counts[world + 1] = int((live & ~held).sum())
-    return rows, counts, leaving.astype(np.uint8)
+    return rows, counts, leaving.astype(np.uint8), send.astype(np.int64)
+
+
+def _arena_room(lens):
+    """Arena bytes the string directory takes for texts of these lengths: each rounded up to 8."""
+    return (lens + 7) & ~7
+
+
+def plan_text_migration(text_of_id, v, t_us, cls, live, owner_map, world: int, rank: int, seed: int = 0) -> dict:
+    """``plan_migration`` for an owner whose keys are text (DESIGN.md §7 "Migrating text-keyed
+    buckets"): tbe_sdir_route_keys_device, tbe_migrate_out_ids_device and the text pack in
+    numpy, their reference and the body of ``migrate``'s host path.  text_of_id[i]: the bytes
+    id i holds, None where none does; the other arguments as in ``plan_migration``.  The key of
+    an id is ``text_route_keys`` of its text under `seed` (a text whose key is UINT64_MAX reads
+    as unheld, as on the device), and from there on the rule is ``plan_migration``'s.  Returns
+    a dict: rows (column 0 = the routing key), counts and leaving as ``plan_migration``
+    returns them; row_ids (int64, the id of every row, send order); lens (int64, the rows'
+    text lengths); out_bytes (uint8, the rows' texts tightly packed in send order);
+    byte_counts and arena_counts (int64 [world]: per destination, the text bytes and the arena
+    bytes -- each length rounded up to 8 -- of its rows); arena_freed (the arena bytes of all
+    leaving ids, those that send no row included)."""
+    n = len(text_of_id)
+    held = np.array([t is not None for t in text_of_id], dtype=bool)
+    texts = [bytes(t) for t in text_of_id if t is not None]
+    lens_all = np.zeros(n, dtype=np.int64)
+    lens_all[held] = [len(t) for t in texts]
+    keys = np.full(n, NO_ID, dtype=np.uint64)
+    if texts:
+        offs = np.zeros(len(texts) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum(lens_all[held], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(texts), dtype=np.uint8)
+        keys[held] = text_route_keys(blob, offs, seed, blob.shape[0])
+    rows, counts, leaving, row_ids = _plan_migration(keys, v, t_us, cls, live, owner_map, world, rank)
+    lens = lens_all[row_ids]
+    out = b"".join(text_of_id[i] for i in row_ids.tolist())
+    dest = np.repeat(np.arange(world, dtype=np.int64), counts[:world])
+    return {"rows": rows, "counts": counts, "leaving": leaving, "row_ids": row_ids, "lens": lens,
+            "out_bytes": np.frombuffer(out, dtype=np.uint8).copy(),
+            "byte_counts": np.bincount(dest, weights=lens, minlength=world).astype(np.int64),
+            "arena_counts": np.bincount(dest, weights=_arena_room(lens), minlength=world).astype(np.int64),
+            "arena_freed": int(_arena_room(lens_all[leaving.astype(bool)]).sum())}
 
 
 def _class_table(engine):
@@ -1149,7 +1194,7 @@ def _room_error(engine_keys, directory, held, counts, incoming, world):
     return None
 
 
-def migrate(engine, directory, new_map, ts_us: int, group=None) -> Tuple[int, int]:
+def migrate(engine, directory, new_map, ts_us: int, group=None, seed: int = 0) -> Tuple[int, int]:
     """Bring a new owner map into force while the tables stay where they are (DESIGN.md §7
     "Migrating buckets").  A collective: every rank calls it between batches with the same
     `new_map` (None: the hash partition) and ts_us.  Each rank finds the keys it holds that
@@ -1167,9 +1212,18 @@ def migrate(engine, directory, new_map, ts_us: int, group=None) -> Tuple[int, in
     that its directory has room for what arrives, that its engine covers its directory and
     that all ranks hold the same class table; a failure on any rank raises ValueError on all
     of them.  Token bucket kind only; lease counters are not carried (the source zeroes
-    them)."""
+    them).
+
+    Text-keyed buckets (DESIGN.md §7 "Migrating text-keyed buckets"): with a ``StringDirectory``
+    (device path) or a ``HostStringDirectory`` (host path) a key's owner follows from the
+    routing key of its text under `seed`, the seed the caller passes to ``route_text_batch``
+    (the u64 paths ignore it); every row travels with its text, and afterwards
+    ``route_text_batch(..., owner_map=new_map, seed=seed)`` decides as if the new map had been
+    in force from the start.  The pre-flight of a ``StringDirectory`` also checks that its arena
+    has room for the text that arrives, so a migration never puts it into TBE_ERANGE."""
     import torch.distributed as dist
     from . import _capi
+    from .strdir import HostStringDirectory, StringDirectory
     kind = int(getattr(engine, "KIND", _capi.TBE_KIND_TOKEN_BUCKET))
     if kind == _capi.TBE_KIND_QUEUEING:
         raise ValueError("cluster.migrate: the queueing kind's rings and the host's request-id futures "
@@ -1177,11 +1231,13 @@ def migrate(engine, directory, new_map, ts_us: int, group=None) -> Tuple[int, in
     if kind == _capi.TBE_KIND_APPROXIMATE:
         raise ValueError("cluster.migrate: the approximate kind's tier is replicated and its requests "
                          "are not routed, so there is nothing to move")
-    if hasattr(directory, "text_of"):
-        raise TypeError("cluster.migrate routes by u64 key: a StringDirectory has none")
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     if new_map is not None and not _is_cuda(new_map):
         check_owner_map(new_map, world)
+    if isinstance(directory, StringDirectory):
+        return _migrate_text_device(engine, directory, new_map, int(ts_us), world, rank, group, int(seed))
+    if isinstance(directory, HostStringDirectory):
+        return _migrate_text_host(engine, directory, new_map, int(ts_us), world, rank, group, int(seed))
     if isinstance(directory, DeviceDirectory):
         return _migrate_device(engine, directory, new_map, int(ts_us), world, rank, group)
     return _migrate_host(engine, directory, new_map, int(ts_us), world, rank, group)
@@ -1268,6 +1324,160 @@ def _migrate_host(engine, directory, new_map, ts_us, world, rank, group):
     if r.shape[0]:
         ids = directory.assign(r[:, 0].copy().view(np.uint64))
         directory.check()
+        if classed:   # first: a reused id still carries its previous key's class
+            engine.set_class(ids, r[:, 3].astype(np.uint8))
+        v[ids.astype(np.int64)] = r[:, 1].copy().view(np.float64)
+        t[ids.astype(np.int64)] = r[:, 2]
+        engine.import_state(v, t)
+    return int(rows.shape[0]), int(r.shape[0])
+
+
+# Text-keyed buckets.  The protocol of the u64 paths with three differences: the key-of-id
+# table holds routing keys of the held text; the counts exchange carries {rows, text bytes,
+# arena bytes} per destination; every row travels with a fifth column, its text length, and
+# the texts themselves follow in a byte exchange whose splits are the byte counts (the layout
+# _route_text_device uses for requests).
+def _arena_error(used, freed, incoming, arena_bytes):
+    if used - freed + incoming > arena_bytes:
+        return (f"the directory's arena holds {used} bytes of key text, {freed} leave and {incoming} arrive: "
+                f"more than its {arena_bytes} bytes")
+    return None
+
+
+def _migrate_text_device(engine, directory, new_map, ts_us, world, rank, group, seed):
+    import torch
+    from . import _capi
+    lib = _capi.load()
+    dev = torch.device("cuda", engine.config.device if engine.config.device >= 0 else torch.cuda.current_device())
+    st = device_stream(dev)
+    cap = directory.capacity
+    dmap = _device_map(new_map, dev, world)
+    counts = torch.zeros(world + 2, dtype=torch.int64, device=dev)
+    leaving = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    covered = engine.n_keys >= cap
+    sc_l = [0] * (world + 2)
+    n_send = 0
+    head = torch.zeros(3 * world + 1, dtype=torch.int64, device=dev)   # {rows, bytes, arena} per owner, then freed
+    if covered:
+        rk = directory.route_keys(seed)
+        engine.migrate_out_device(ts_us, rk, dmap, world, rank, None, counts, leaving, stream=st)
+        sc_l = counts.tolist()
+        n_send = sum(sc_l[:world])
+        rows = torch.empty((n_send, 4), dtype=torch.int64, device=dev)
+        row_ids = torch.empty(n_send, dtype=torch.int64, device=dev)
+        if n_send:
+            engine.migrate_out_device(ts_us, rk, dmap, world, rank, rows, counts, None, capacity=n_send, stream=st,
+                                      row_ids=row_ids)
+        # the rows' text lengths and offsets; per destination (the rows are grouped by it) the
+        # differences of the byte and arena-byte prefix sums at the group boundaries
+        lens = torch.empty(n_send, dtype=torch.int64, device=dev)
+        _check(lib.tbe_sdir_text_lengths_device(directory._h, row_ids.data_ptr(), n_send, lens.data_ptr(), None, st))
+        offs = torch.zeros(n_send + 1, dtype=torch.int64, device=dev)
+        aoffs = torch.zeros(n_send + 1, dtype=torch.int64, device=dev)
+        if n_send:
+            torch.cumsum(lens, 0, out=offs[1:])
+            torch.cumsum(_arena_room(lens), 0, out=aoffs[1:])
+        bounds = torch.tensor(np.concatenate([[0], np.cumsum(sc_l[:world])]), dtype=torch.int64, device=dev)
+        all_ids = torch.arange(cap, dtype=torch.int64, device=dev)
+        lens_all = torch.empty(cap, dtype=torch.int64, device=dev)
+        _check(lib.tbe_sdir_text_lengths_device(directory._h, all_ids.data_ptr(), cap, lens_all.data_ptr(), None, st))
+        head[0:3 * world:3] = counts[:world]
+        head[1:3 * world:3] = offs[bounds].diff()
+        head[2:3 * world:3] = aoffs[bounds].diff()
+        head[3 * world] = (_arena_room(lens_all) * leaving).sum()
+    head_l = head.tolist()
+    freed = head_l[3 * world]
+    sc3 = head[:3 * world].contiguous()
+    rc3 = torch.empty_like(sc3)
+    _all_to_all(rc3, sc3, group=group)
+    rc_l = rc3.tolist()
+    sc_rows, sc_bytes = head_l[0:3 * world:3], head_l[1:3 * world:3]
+    rc_rows, rc_bytes, rc_arena = rc_l[0::3], rc_l[1::3], rc_l[2::3]
+    try:
+        held, used, arena_bytes = directory.usage()
+        err = _room_error(engine.n_keys, directory, held, sc_l, sum(rc_rows), world) or \
+            _arena_error(used, freed, sum(rc_arena), arena_bytes)
+    except _capi.TbeError as ex:
+        err = str(ex)
+    _preflight(err, _class_table(engine), counts, group)
+    # the text is packed before the reclaim, which compacts the arena and forgets the ids
+    nb = sum(sc_bytes)
+    send_bytes = torch.zeros((nb + 7) // 8 * 8 + 8, dtype=torch.uint8, device=dev)
+    _check(lib.tbe_sdir_text_device(directory._h, row_ids.data_ptr(), n_send, offs.data_ptr(), send_bytes.data_ptr(), st))
+    engine.migrate_out_device(ts_us, rk, dmap, world, rank, rows if n_send else None, counts, leaving, commit=True,
+                              capacity=n_send, stream=st)
+    directory.reclaim_device(leaving)
+    m = sum(rc_rows)
+    recv = torch.empty((m, 5), dtype=torch.int64, device=dev)
+    _all_to_all(recv, torch.cat([rows, lens.view(-1, 1)], dim=1), rc_rows, sc_rows, group=group)
+    mb = sum(rc_bytes)
+    recv_bytes = torch.empty((mb + 7) // 8 * 8 + 8, dtype=torch.uint8, device=dev)
+    recv_bytes[mb:] = 0
+    _all_to_all(recv_bytes[:mb], send_bytes[:nb], rc_bytes, sc_bytes, group=group)
+    if m:
+        roffs = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(recv[:, 4], 0, out=roffs[1:])
+        ids = directory.assign(recv_bytes, roffs, mb)
+        directory.size()         # raises on an overflow, which the pre-flight has made impossible
+        if getattr(engine, "classed", False):   # first: a reused id still carries its previous key's class
+            engine.set_class_device(ids, recv[:, 3].to(torch.uint8), stream=st)
+        engine.import_rows(ids, recv[:, 1].contiguous().view(torch.float64), recv[:, 2].contiguous(), stream=st)
+    return n_send, m
+
+
+def _migrate_text_host(engine, directory, new_map, ts_us, world, rank, group, seed):
+    import torch
+    import torch.distributed as dist
+    cap = directory.capacity
+    classes = _class_table(engine)
+    classed = bool(getattr(engine, "classed", False))
+    v, t = engine.export_state()
+    v, t = np.array(v, dtype=np.float64), np.array(t, dtype=np.int64)
+    n_keys = int(getattr(engine, "n_keys", v.shape[0]))
+    err = None
+    if n_keys < cap or v.shape[0] < cap:
+        err = "the engine has fewer keys than the directory has ids"
+        p = plan_text_migration([None] * cap, np.zeros(cap), np.full(cap, ABSENT), None, np.zeros(cap, dtype=bool),
+                                new_map, world, rank, seed)
+    else:
+        v, t = v[:cap], t[:cap]
+        text_of_id = [None] * cap
+        for k, i in directory.ids.items():
+            text_of_id[i] = k
+        cls = engine.get_class(np.arange(cap, dtype=np.uint64)) if classed else np.zeros(cap, dtype=np.uint8)
+        ttl = np.array([class_ttl_ms(*c) for c in classes], dtype=np.int64)[cls]
+        p = plan_text_migration(text_of_id, v, t, cls, rows_live(t, ts_us, ttl), new_map, world, rank, seed)
+    rows, counts, leaving = p["rows"], p["counts"], p["leaving"]
+    sc3 = torch.from_numpy(np.stack([counts[:world], p["byte_counts"], p["arena_counts"]], axis=1).reshape(-1).copy())
+    rc3 = torch.empty_like(sc3)
+    dist.all_to_all_single(rc3, sc3, group=group)
+    rc = rc3.numpy().reshape(world, 3)
+    sc_l, rc_rows, rc_bytes = counts.tolist(), rc[:, 0].tolist(), rc[:, 1].tolist()
+    if err is None:     # a HostStringDirectory has no arena: the arena bytes travel unchecked
+        err = "the directory is over capacity" if directory.overflow else \
+            _room_error(n_keys, directory, directory.size(), sc_l, sum(rc_rows), world)
+    _preflight(err, classes, sc3, group)
+    gone = np.flatnonzero(leaving)
+    v[gone] = np.array([c[0] for c in classes], dtype=np.float64)[cls[gone]]
+    t[gone] = ABSENT
+    engine.import_state(v, t)
+    directory.reclaim(gone)
+    recv = torch.empty((sum(rc_rows), 5), dtype=torch.int64)
+    send = np.concatenate([rows, p["lens"].reshape(-1, 1)], axis=1)
+    dist.all_to_all_single(recv, torch.from_numpy(np.ascontiguousarray(send)), output_split_sizes=rc_rows,
+                           input_split_sizes=sc_l[:world], group=group)
+    recv_bytes = torch.empty(sum(rc_bytes), dtype=torch.uint8)
+    dist.all_to_all_single(recv_bytes, torch.from_numpy(p["out_bytes"]), output_split_sizes=rc_bytes,
+                           input_split_sizes=p["byte_counts"].tolist(), group=group)
+    r = recv.numpy()
+    if r.shape[0]:
+        roffs = np.zeros(r.shape[0] + 1, dtype=np.int64)
+        np.cumsum(r[:, 4], out=roffs[1:])
+        blob = recv_bytes.numpy().tobytes()
+        ids = directory.assign([blob[roffs[j]:roffs[j + 1]] for j in range(r.shape[0])])
+        if directory.overflow:
+            from . import _capi
+            raise _capi.TbeError(_capi.TBE_ERANGE, f"string directory over capacity ({directory.capacity} ids)")
         if classed:   # first: a reused id still carries its previous key's class
             engine.set_class(ids, r[:, 3].astype(np.uint8))
         v[ids.astype(np.int64)] = r[:, 1].copy().view(np.float64)

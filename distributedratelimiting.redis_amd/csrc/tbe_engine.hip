@@ -4658,7 +4658,8 @@ __global__ void k_rows_write(Slot *__restrict__ table, const uint64_t *__restric
 //   k_mig_scan         the owners' columns as one flat array, owner-major, scanned in place:
 //                      entry [o][tile] becomes the first output row of that tile's rows for o
 //   k_mig_finish       counts[o] from the scanned starts, the two sums, the verdict of the call
-//   k_mig_pass<true>   the same ranking again over whole rows, stored from those starts
+//   k_mig_pass<true>   the same ranking again over whole rows, stored from those starts; with
+//                      row_ids (tbe_migrate_out_ids_device) each row's id beside it
 //   k_mig_commit       leaving ids' rows rewritten absent, their lease counters zeroed
 // flags[0]: a map entry >= n_owners (nothing is written); flags[1]: the commit is refused.
 struct MigArgs {
@@ -4683,7 +4684,8 @@ __device__ __forceinline__ uint32_t mig_dest(const MigArgs &A, uint64_t key) {
 template <bool WRITE>
 __global__ __launch_bounds__(kBlock) void k_mig_pass(MigArgs A, unsigned long long *__restrict__ tile_n,
                                                      uint8_t *__restrict__ leaving, uint32_t *__restrict__ flags,
-                                                     int64_t *__restrict__ rows, uint64_t capacity) {
+                                                     int64_t *__restrict__ rows, uint64_t capacity,
+                                                     uint64_t *__restrict__ row_ids) {
     __shared__ uint16_t cnt[kLiveItems * kWaves * kDigits];   // [item][wave][owner], 16 KB
     __shared__ unsigned long long start[kDigits];
     __shared__ uint32_t part[2 * kWaves];
@@ -4786,6 +4788,7 @@ __global__ __launch_bounds__(kBlock) void k_mig_pass(MigArgs A, unsigned long lo
                 const i64x2 b = {(long long)s[k].t_us, (long long)cbyte[k]};
                 st_nt(out, a);
                 st_nt(out + 1, b);
+                if (row_ids) row_ids[pos] = A.first + base + (uint64_t)k * kBlock + tid;
             }
         }
     }
@@ -6985,10 +6988,10 @@ static tbe_status migrate_args_ok(tbe_engine *e, uint64_t first, uint64_t count,
     return TBE_OK;
 }
 
-tbe_status tbe_migrate_out_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count,
-                                  const uint64_t *d_key_of_id, const uint8_t *d_owner_map, uint32_t n_owners,
-                                  uint32_t self, int64_t *d_rows, uint64_t capacity, uint64_t *d_counts,
-                                  uint8_t *d_leaving, int32_t commit, void *stream) {
+tbe_status tbe_migrate_out_ids_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count,
+                                      const uint64_t *d_key_of_id, const uint8_t *d_owner_map, uint32_t n_owners,
+                                      uint32_t self, int64_t *d_rows, uint64_t capacity, uint64_t *d_counts,
+                                      uint8_t *d_leaving, int32_t commit, uint64_t *d_row_ids, void *stream) {
     if (!e) return TBE_EINVAL;
     if (tbe_status rc = migrate_args_ok(e, first, count, d_key_of_id, n_owners, self, d_rows, capacity, d_counts))
         return rc;
@@ -7030,11 +7033,12 @@ tbe_status tbe_migrate_out_device(tbe_engine *e, int64_t ts_us, uint64_t first, 
         A.x = A.by_class ? ts_us / 1000 : (ts_us < 0 ? kAbsent : (ts_us / 1000 - e->params.ttl_ms) * 1000);
         A.n_owners = n_owners;
         A.self = self;
-        k_mig_pass<false><<<(unsigned)ntiles, kBlock, 0, st>>>(A, tile_n, d_leaving, flags, nullptr, 0);
+        k_mig_pass<false><<<(unsigned)ntiles, kBlock, 0, st>>>(A, tile_n, d_leaving, flags, nullptr, 0, nullptr);
         k_mig_scan<<<1, kLiveScan, 0, st>>>(tile_n, (uint64_t)n_owners * ntiles, total);
         k_mig_finish<<<1, kBlock, 0, st>>>(tile_n, ntiles, total, n_owners, capacity, commit, counts, flags, e->sticky);
         if (capacity)
-            k_mig_pass<true><<<(unsigned)ntiles, kBlock, 0, st>>>(A, tile_n, nullptr, flags, d_rows, capacity);
+            k_mig_pass<true><<<(unsigned)ntiles, kBlock, 0, st>>>(A, tile_n, nullptr, flags, d_rows, capacity,
+                                                                  d_row_ids);
         if (commit)
             k_mig_commit<<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, st>>>(A, e->table, e->params.cap, flags,
                                                                                        e->st_ok, e->st_failed);
@@ -7047,9 +7051,18 @@ tbe_status tbe_migrate_out_device(tbe_engine *e, int64_t ts_us, uint64_t first, 
     return TBE_OK;
 }
 
-tbe_status tbe_migrate_out(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, const uint64_t *key_of_id,
-                           const uint8_t *owner_map, uint32_t n_owners, uint32_t self, int64_t *rows,
-                           uint64_t capacity, uint64_t *counts, uint8_t *leaving, int32_t commit) {
+tbe_status tbe_migrate_out_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count,
+                                  const uint64_t *d_key_of_id, const uint8_t *d_owner_map, uint32_t n_owners,
+                                  uint32_t self, int64_t *d_rows, uint64_t capacity, uint64_t *d_counts,
+                                  uint8_t *d_leaving, int32_t commit, void *stream) {
+    return tbe_migrate_out_ids_device(e, ts_us, first, count, d_key_of_id, d_owner_map, n_owners, self, d_rows, capacity,
+                                      d_counts, d_leaving, commit, nullptr, stream);
+}
+
+tbe_status tbe_migrate_out_ids(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, const uint64_t *key_of_id,
+                               const uint8_t *owner_map, uint32_t n_owners, uint32_t self, int64_t *rows,
+                               uint64_t capacity, uint64_t *counts, uint8_t *leaving, int32_t commit,
+                               uint64_t *row_ids) {
     if (!e) return TBE_EINVAL;
     if (tbe_status rc = migrate_args_ok(e, first, count, key_of_id, n_owners, self, rows, capacity, counts)) return rc;
     for (uint32_t v = 0; owner_map && v < kOwnerMapSize; ++v)
@@ -7058,20 +7071,21 @@ tbe_status tbe_migrate_out(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_
     HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch, whatever its stream
     const uint64_t cap = std::min(capacity, count);   // no more rows than the range holds
     const uint64_t nc = (uint64_t)n_owners + 2;
-    // [counts | rows | key_of_id | map | leaving], every part 16-byte aligned
+    // [counts | rows | key_of_id | map | leaving | row ids], every part 16-byte aligned
     const uint64_t o_rows = (nc * 8 + 15) & ~15ull, o_keys = o_rows + cap * 32, o_map = (o_keys + count * 8 + 15) & ~15ull,
-                   o_leave = o_map + kOwnerMapSize;
+                   o_leave = o_map + kOwnerMapSize, o_ids = (o_leave + count + 15) & ~15ull;
     char *buf = nullptr;
-    HIP_TRY(e, hipMalloc(&buf, o_leave + count + 16));
+    HIP_TRY(e, hipMalloc(&buf, o_ids + (row_ids ? cap * 8 : 0) + 16));
     uint64_t *d_counts = reinterpret_cast<uint64_t *>(buf), *d_keys = reinterpret_cast<uint64_t *>(buf + o_keys);
     int64_t *d_rows = reinterpret_cast<int64_t *>(buf + o_rows);
     uint8_t *d_map = reinterpret_cast<uint8_t *>(buf + o_map), *d_leave = reinterpret_cast<uint8_t *>(buf + o_leave);
+    uint64_t *d_ids = row_ids ? reinterpret_cast<uint64_t *>(buf + o_ids) : nullptr;
     hipError_t hrc = count ? hipMemcpy(d_keys, key_of_id, count * 8, hipMemcpyHostToDevice) : hipSuccess;
     if (hrc == hipSuccess && owner_map) hrc = hipMemcpy(d_map, owner_map, kOwnerMapSize, hipMemcpyHostToDevice);
     tbe_status rc = TBE_OK;
     auto run = [&](uint64_t c, int32_t cm) {
-        rc = tbe_migrate_out_device(e, ts_us, first, count, d_keys, owner_map ? d_map : nullptr, n_owners, self,
-                                    c ? d_rows : nullptr, c, d_counts, d_leave, cm, nullptr);
+        rc = tbe_migrate_out_ids_device(e, ts_us, first, count, d_keys, owner_map ? d_map : nullptr, n_owners, self,
+                                        c ? d_rows : nullptr, c, d_counts, d_leave, cm, c ? d_ids : nullptr, nullptr);
         if (rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
         if (rc == TBE_OK && hrc == hipSuccess) hrc = hipMemcpy(counts, d_counts, nc * 8, hipMemcpyDeviceToHost);
     };
@@ -7093,6 +7107,7 @@ tbe_status tbe_migrate_out(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_
         for (uint32_t o = 0; o < n_owners; ++o) total += counts[o];
         const uint64_t m = std::min(total, cap);
         if (m) hrc = hipMemcpy(rows, d_rows, m * 32, hipMemcpyDeviceToHost);
+        if (m && d_ids && hrc == hipSuccess) hrc = hipMemcpy(row_ids, d_ids, m * 8, hipMemcpyDeviceToHost);
     }
     if (hrc == hipSuccess && rc == TBE_OK && leaving && count)
         hrc = hipMemcpy(leaving, d_leave, count, hipMemcpyDeviceToHost);
@@ -7101,6 +7116,13 @@ tbe_status tbe_migrate_out(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_
     HIP_TRY(e, hrc);
     if (refused) return fail(e, TBE_EINVAL, refused);
     return TBE_OK;
+}
+
+tbe_status tbe_migrate_out(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, const uint64_t *key_of_id,
+                           const uint8_t *owner_map, uint32_t n_owners, uint32_t self, int64_t *rows,
+                           uint64_t capacity, uint64_t *counts, uint8_t *leaving, int32_t commit) {
+    return tbe_migrate_out_ids(e, ts_us, first, count, key_of_id, owner_map, n_owners, self, rows, capacity, counts,
+                               leaving, commit, nullptr);
 }
 
 // ---- limit classes

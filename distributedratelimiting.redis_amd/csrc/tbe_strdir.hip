@@ -677,6 +677,32 @@ __global__ void k_sd_text(const uint64_t *__restrict__ ids, uint64_t n, const ui
     }
 }
 
+// Routing key of every held id (tbe_sdir_route_keys_device): keys[i] = sd_hash of the text id
+// first + i holds, seeded as tbe_route_text_keys_device seeds the sender's copy of the same
+// text; kNoKey for an id that is not held.  One id per thread: iloc is read coalesced, the
+// text straight out of the arena, where every key starts on an 8-byte boundary and its last
+// word is stored zero-padded, so sd_hash takes its aligned one-load path for every word
+// (A.safe covers the arena's 16 spare bytes).  The trip count is uniform in a block, so the
+// ballot sees whole waves: one atomic per wave and round for *n_held.
+constexpr uint64_t kNoKey = ~0ull;
+__global__ __launch_bounds__(kSdBlock) void k_sd_route_keys(const uint64_t *__restrict__ iloc, SdArena A,
+                                                            uint64_t first, uint64_t count, uint64_t seed,
+                                                            uint64_t *__restrict__ keys,
+                                                            unsigned long long *__restrict__ n_held) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x; t0 < count; t0 += stride) {
+        const uint64_t i = t0 + threadIdx.x;
+        bool held = false;
+        if (i < count) {
+            const uint64_t loc = iloc[first + i];
+            held = (loc & kLocValid) != 0;
+            keys[i] = held ? sd_hash(A.bytes, A.safe, loc_off(loc), loc_len(loc), seed) : kNoKey;
+        }
+        const uint64_t m = __ballot(held);
+        if (n_held && m && (threadIdx.x & 63) == 0) atomicAdd(n_held, (unsigned long long)__popcll(m));
+    }
+}
+
 // Host hash of the prefix (the seeds of the four rounds derive from it).
 uint64_t host_hash(const uint8_t *p, uint32_t len) {
     uint64_t h = mix64(0x243F6A8885A308D3ull ^ ((uint64_t)len * 0x9E3779B97F4A7C15ull));
@@ -1003,6 +1029,30 @@ tbe_status tbe_sdir_size(tbe_string_directory *d, uint64_t *n_ids) {
     *n_ids = st[kStFresh] - st[kStNfree];   // counters handed out less the ids waiting on the free stack
     if (st[kStErr] & (kErrRange | kErrRounds | kErrArena | kErrFull)) return TBE_ERANGE;
     return (st[kStErr] & kErrBatch) ? TBE_EINVAL : TBE_OK;
+}
+
+tbe_status tbe_sdir_usage(tbe_string_directory *d, uint64_t out[3]) {
+    if (!d || !out) return TBE_EINVAL;
+    const tbe_status rc = tbe_sdir_size(d, &out[0]);
+    if (rc == TBE_EDEVICE) return rc;
+    unsigned long long used = 0;
+    if (hipMemcpy(&used, d->state + kSdArena, sizeof used, hipMemcpyDeviceToHost) != hipSuccess) return TBE_EDEVICE;
+    out[1] = used;
+    out[2] = d->arena_bytes;
+    return rc;
+}
+
+tbe_status tbe_sdir_route_keys_device(tbe_string_directory *d, uint64_t seed, uint64_t first, uint64_t count,
+                                      uint64_t *d_keys, uint64_t *d_n_held, void *stream) {
+    if (!d || !d_keys || first > d->capacity || count > d->capacity - first) return TBE_EINVAL;
+    if (hipSetDevice(d->device) != hipSuccess) return TBE_EDEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    if (d_n_held && hipMemsetAsync(d_n_held, 0, sizeof(uint64_t), st) != hipSuccess) return TBE_EDEVICE;
+    if (count == 0) return TBE_OK;
+    const SdArena A{d->arena, d->arena_alloc & ~7ull};
+    k_sd_route_keys<<<grid_for(count, kSdBlock), kSdBlock, 0, st>>>(d->iloc, A, first, count, seed, d_keys,
+                                                                   reinterpret_cast<unsigned long long *>(d_n_held));
+    return hipGetLastError() == hipSuccess ? TBE_OK : TBE_EDEVICE;
 }
 
 tbe_status tbe_sdir_reclaim_device(tbe_string_directory *d, const uint8_t *d_dead, const uint64_t *d_keep_ids,

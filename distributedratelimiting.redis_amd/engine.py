@@ -268,7 +268,7 @@ class TokenBucketEngine:
     # ------------------------------------------------------------------ live owner-map change
     def migrate_out_device(self, ts_us: int, d_key_of_id, d_owner_map, n_owners: int, self_rank: int, d_rows,
                            d_counts, d_leaving=None, commit: bool = False, first: int = 0,
-                           capacity: Optional[int] = None, stream: Optional[int] = None) -> None:
+                           capacity: Optional[int] = None, stream: Optional[int] = None, row_ids=None) -> None:
         """One tbe_migrate_out_device call over ids [first, first + d_key_of_id.numel()): the
         live rows of the ids whose key (int64 device tensor, -1 = unheld) `d_owner_map` (uint8
         device tensor of 4096 owners, or None for the hash partition) gives to another owner
@@ -276,7 +276,9 @@ class TokenBucketEngine:
         destination; d_counts (int64, n_owners + 2): rows per owner, leaving ids, orphans;
         d_leaving (uint8, one per id, optional): 1 where the id's key leaves.  capacity (rows)
         defaults to what d_rows holds; 0 with d_rows=None only counts.  commit=True also
-        rewrites the leaving rows absent.  Enqueued; a refused call raises at ``synchronize()``."""
+        rewrites the leaving rows absent.  row_ids (int64 device tensor of at least capacity
+        entries, optional): row_ids[j] = the id whose row is d_rows[j] (tbe_migrate_out_ids_device).
+        Enqueued; a refused call raises at ``synchronize()``."""
         count = d_key_of_id.numel()
         if capacity is None:
             capacity = 0 if d_rows is None else d_rows.numel() // 4
@@ -290,17 +292,23 @@ class TokenBucketEngine:
             raise ValueError("the owner map must be 4096 uint8 entries")
         if not d_key_of_id.is_contiguous() or d_key_of_id.element_size() != 8:
             raise ValueError("d_key_of_id must be a contiguous 64-bit tensor")
+        if row_ids is not None and (row_ids.numel() < capacity or row_ids.element_size() != 8
+                                    or not row_ids.is_contiguous()):
+            raise ValueError("row_ids must be a contiguous 64-bit tensor of at least capacity entries")
         ptr = (lambda t: None if t is None else t.data_ptr())
-        self._check(self._lib.tbe_migrate_out_device(
+        self._check(self._lib.tbe_migrate_out_ids_device(
             self.handle, ts_us, first, count, d_key_of_id.data_ptr(), ptr(d_owner_map), n_owners, self_rank,
-            ptr(d_rows) if capacity else None, capacity, d_counts.data_ptr(), ptr(d_leaving), 1 if commit else 0, stream))
+            ptr(d_rows) if capacity else None, capacity, d_counts.data_ptr(), ptr(d_leaving), 1 if commit else 0,
+            ptr(row_ids) if capacity else None, stream))
         self._migrate_in_flight = (d_key_of_id, d_owner_map)   # read by the enqueued kernels
 
     def migrate_out(self, ts_us: int, key_of_id, owner_map, n_owners: int, self_rank: int, commit: bool = False,
-                    first: int = 0, capacity: Optional[int] = None):
+                    first: int = 0, capacity: Optional[int] = None, row_ids: bool = False):
         """The same with host arrays (tbe_migrate_out; synchronous): returns (rows int64
         [capacity, 4] of which the first min(total, capacity) are written, counts uint64
-        [n_owners + 2], leaving uint8 [count]).  capacity defaults to the number of ids."""
+        [n_owners + 2], leaving uint8 [count]).  capacity defaults to the number of ids.
+        row_ids=True (tbe_migrate_out_ids) appends the rows' ids, uint64 [capacity], written as
+        far as the rows are."""
         key_of_id = np.ascontiguousarray(key_of_id, dtype=np.uint64)
         count = key_of_id.shape[0]
         if owner_map is not None:
@@ -312,12 +320,13 @@ class TokenBucketEngine:
         rows = np.zeros((capacity, 4), dtype=np.int64)
         counts = np.zeros(n_owners + 2, dtype=np.uint64)
         leaving = np.zeros(count, dtype=np.uint8)
-        self._check(self._lib.tbe_migrate_out(
+        ids = np.zeros(capacity, dtype=np.uint64) if row_ids else None
+        self._check(self._lib.tbe_migrate_out_ids(
             self.handle, ts_us, first, count, key_of_id.ctypes.data,
             None if owner_map is None else owner_map.ctypes.data, n_owners, self_rank,
             rows.ctypes.data if capacity else None, capacity, counts.ctypes.data, leaving.ctypes.data,
-            1 if commit else 0))
-        return rows, counts, leaving
+            1 if commit else 0, ids.ctypes.data if row_ids and capacity else None))
+        return (rows, counts, leaving, ids) if row_ids else (rows, counts, leaving)
 
     # ------------------------------------------------------------------ limit classes
     def classes(self):

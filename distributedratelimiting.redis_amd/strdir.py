@@ -136,6 +136,41 @@ class StringDirectory(_DeviceReclaim):
                                  else "string directory error")
         return n.value
 
+    def usage(self) -> Tuple[int, int, int]:
+        """(keys held, arena bytes in use, arena_bytes) (tbe_sdir_usage; synchronises).  Raises
+        as ``size()`` does."""
+        import ctypes
+        from . import _capi
+        out = (ctypes.c_uint64 * 3)()
+        st = self._lib.tbe_sdir_usage(self._h, out)
+        if st != _capi.TBE_OK:
+            raise _capi.TbeError(st, "string directory over capacity" if st == _capi.TBE_ERANGE
+                                 else "string directory error")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def route_keys(self, seed: int = 0, first: int = 0, count: int = None, return_held: bool = False):
+        """Routing key of every id of [first, first + count) (default: all ``capacity`` ids), on
+        the current stream: an int64 device tensor, ``cluster.text_route_keys`` of the text a
+        held id holds and -1 (UINT64_MAX) for an id that is not held
+        (tbe_sdir_route_keys_device).  return_held=True appends a one-element int64 device
+        tensor that receives the number of held ids."""
+        import torch
+        from . import _capi
+        from .cluster import device_stream
+        if count is None:
+            count = self.capacity - first
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if first < 0 or count < 0:
+            raise ValueError("first and count must not be negative")
+        keys = torch.empty(max(count, 1), dtype=torch.int64, device=dev)
+        held = torch.zeros(1, dtype=torch.int64, device=dev) if return_held else None
+        st = self._lib.tbe_sdir_route_keys_device(self._h, int(seed) & MASK64, int(first), int(count), keys.data_ptr(),
+                                                  held.data_ptr() if return_held else None, device_stream(dev))
+        if st != _capi.TBE_OK:
+            raise _capi.TbeError(st, "tbe_sdir_route_keys_device failed")
+        keys = keys[:count]
+        return (keys, held) if return_held else keys
+
     def text_of(self, d_ids, return_missing: bool = False):
         """Key text of an int64 device tensor of ids, on the device: (uint8 bytes, int64 offsets
         [n + 1]), the layout ``assign`` takes (tbe_sdir_text_lengths_device, a scan,

@@ -421,6 +421,21 @@ tbe_status tbe_migrate_out_device(tbe_engine *engine, int64_t ts_us, uint64_t fi
 tbe_status tbe_migrate_out(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
                            const uint64_t *key_of_id, const uint8_t *owner_map, uint32_t n_owners, uint32_t self,
                            int64_t *rows, uint64_t capacity, uint64_t *counts, uint8_t *leaving, int32_t commit);
+/* tbe_migrate_out_device / tbe_migrate_out plus one output: d_row_ids[j] (device u64) = the id
+ * (first + i) whose row is written at d_rows + 4 j, for every j < capacity that holds a row;
+ * nothing at or past capacity is touched in either array.  A migration of text-keyed buckets
+ * fetches the rows' key text by these ids (tbe_sdir_text_device) before the reclaim forgets
+ * them (DESIGN.md §7 "Migrating text-keyed buckets"); there d_key_of_id holds the routing
+ * keys tbe_sdir_route_keys_device writes.  d_row_ids == NULL is exactly the call above: the
+ * two entry points above pass NULL.  The host form copies min(rows written, capacity) ids. */
+tbe_status tbe_migrate_out_ids_device(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                                      const uint64_t *d_key_of_id, const uint8_t *d_owner_map, uint32_t n_owners,
+                                      uint32_t self, int64_t *d_rows, uint64_t capacity, uint64_t *d_counts,
+                                      uint8_t *d_leaving, int32_t commit, uint64_t *d_row_ids, void *stream);
+tbe_status tbe_migrate_out_ids(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                               const uint64_t *key_of_id, const uint8_t *owner_map, uint32_t n_owners, uint32_t self,
+                               int64_t *rows, uint64_t capacity, uint64_t *counts, uint8_t *leaving, int32_t commit,
+                               uint64_t *row_ids);
 
 /* ---------------------------------------------------------------- TokenBucketWithQueue
  * Engines created with kind = TBE_KIND_QUEUEING. The reference limiter

@@ -57,7 +57,12 @@ tbe_status tbe_route_plan_device(const uint64_t *d_keys, uint64_t n, uint32_t n_
  * then tbe_migrate_out_device with commit), drops those keys (tbe_dir_reclaim_device with
  * the leaving flags), the rows cross in one all-to-all, and each new owner installs them
  * behind its own directory (tbe_dir_assign_device, tbe_set_class_device,
- * tbe_import_rows_device); the tables stay in HBM.  The number of owners still changes
+ * tbe_import_rows_device); the tables stay in HBM.  Buckets keyed by text migrate the same
+ * way (DESIGN.md §7 "Migrating text-keyed buckets"): the key-of-id table is
+ * tbe_sdir_route_keys_device's, tbe_migrate_out_ids_device also gives the packed rows' ids,
+ * whose text tbe_sdir_text_lengths_device / tbe_sdir_text_device fetch before
+ * tbe_sdir_reclaim_device forgets it, and the text crosses in an all-to-all of its own to the
+ * new owner's tbe_sdir_assign_device.  The number of owners still changes
  * through a snapshot: every owner saves its live buckets by key (tbe_export_live_device,
  * tbe_dir_keys_of_device) and each new owner loads the keys the new map gives it
  * (DESIGN.md §8 "Portable snapshots"). */

@@ -90,6 +90,28 @@ tbe_status tbe_sdir_text_lengths_device(tbe_string_directory *dir, const uint64_
 tbe_status tbe_sdir_text_device(tbe_string_directory *dir, const uint64_t *d_ids, uint64_t n,
                                 const uint64_t *d_offs, uint8_t *d_bytes, void *stream);
 
+/* Routing keys of the held ids, on the device: what a live owner-map change of text-keyed
+ * buckets hands to tbe_migrate_out_device as its key-of-id table (tbe_cluster.h "Migrating
+ * text-keyed buckets").  d_keys[i] = tbe_text_route_key(text, len, seed) of the resourceID
+ * (without the prefix) that id first + i holds -- the key tbe_route_text_keys_device computes
+ * for the same text on the sending side, bit for bit --, and UINT64_MAX for an id that is not
+ * held (never assigned, or reclaimed).  *d_n_held (device u64, may be NULL) = held ids of the
+ * range.  The text is read out of the arena in place.  A range past capacity or a NULL
+ * d_keys: TBE_EINVAL, nothing enqueued.  Contract as for a lookup: no assign or reclaim in
+ * flight on another stream.
+ * A held string whose routing key is itself UINT64_MAX (probability 2^-64 per key) reads as
+ * unheld.  The value is not remapped, because the senders route that string by the same
+ * unmapped key; if the id's row is live, the migration's pre-flight counts it as an orphan
+ * and refuses the change, so nothing is lost. */
+tbe_status tbe_sdir_route_keys_device(tbe_string_directory *dir, uint64_t seed, uint64_t first, uint64_t count,
+                                      uint64_t *d_keys, uint64_t *d_n_held, void *stream);
+
+/* out = {keys held (what tbe_sdir_size reports), arena bytes in use (every held key's length
+ * rounded up to 8), arena_bytes}.  Synchronises; statuses as tbe_sdir_size (out is filled for
+ * TBE_ERANGE and TBE_EINVAL too).  The room check of a migration reads it, so that no
+ * incoming key can push the arena into the sticky TBE_ERANGE state. */
+tbe_status tbe_sdir_usage(tbe_string_directory *dir, uint64_t out[3]);
+
 /* Remove the keys flagged dead and reuse what they held.  d_dead: `capacity` bytes of
  * device memory indexed by id (tbe_expired_device over [0, capacity) writes them);
  * d_keep_ids: n_keep ids (device memory) that are never removed.  For every id that is

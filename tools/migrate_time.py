@@ -24,6 +24,27 @@ The exchange between owners (RCCL) is not part of this: it needs more than one G
 Prints one JSON line and, with --out, writes it to that file (profiles/).
 
     python tools/migrate_time.py [--keys 67108864] [--repeats 5] [--no-snapshot] [--out profiles/migrate_time.json]
+
+--text: the same change for text-keyed buckets (cluster.migrate with a StringDirectory).  The
+engine's ids are held by --keys names ``resource-<k>`` (strdir.synthetic_key_text) in a
+StringDirectory, every row live.  Each of the --repeats rounds runs the local steps of one
+rank once, each between HIP events, and the medians are reported:
+
+  route_keys  StringDirectory.route_keys: iloc and the arena text in, 8 B per id out
+  count       migrate_out_device over the routing keys, counting and flagging only
+  pack        migrate_out_device(capacity = rows, row_ids): rows and their ids, no commit
+  text        the rows' text (StringDirectory.text_of): tbe_sdir_text_lengths_device, a scan, one
+              read-back of the byte total, a zero-filled buffer, tbe_sdir_text_device
+  commit      migrate_out_device(commit) into the same row buffer
+  reclaim     reclaim_device(leaving flags)
+  install     the receiver's side, on the same directory and engine: assign of the packed text
+              (into the ids the reclaim freed, beside the names that stayed) + import_rows
+
+The install puts every name and row back under other ids, so the next round finds the same
+table.  Bytes: what each step must read and write at least (see the code); `of_copy_rate` as
+above.  Single-GPU local steps only: the three exchanges need more than one GPU.
+
+    python tools/migrate_time.py --text [--keys 67108864] [--repeats 5] [--out profiles/migrate_text_time.json]
 """
 import argparse
 import json
@@ -45,6 +66,7 @@ def main() -> None:
     ap.add_argument("--keys", type=int, default=1 << 26)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--no-snapshot", action="store_true")
+    ap.add_argument("--text", action="store_true", help="text-keyed buckets behind a StringDirectory")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -151,9 +173,91 @@ def main() -> None:
         directory.close()
         return res
 
+    def run_text(n: int, repeats: int) -> dict:
+        from distributedratelimiting.redis_amd import _capi
+        from distributedratelimiting.redis_amd.strdir import StringDirectory, synthetic_key_text
+        lib = _capi.load()
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        buf, offs, nb = synthetic_key_text(torch.arange(n, dtype=torch.int64, device=dev))
+        arena = int(((offs[1:] - offs[:-1] + 7) & ~7).sum().item())
+        eng, directory = TokenBucketEngine(n, *OPTS, device=0), StringDirectory(n, arena + (1 << 20), device=0)
+        g = torch.Generator(device=dev).manual_seed(7)
+        v = torch.rand(n, dtype=torch.float64, device=dev, generator=g) * OPTS[0]
+        t = TS - torch.randint(0, 2_000_000, (n,), dtype=torch.int64, device=dev, generator=g)   # every row live
+        ids = directory.assign(buf, offs, nb)
+        assert directory.usage()[:2] == (n, arena)
+        eng.import_rows(ids, v, t, stream=cur)
+        eng.synchronize()
+        del buf, offs, ids, v, t
+        dmap = torch.from_numpy(map_b).to(dev)
+        counts = torch.zeros(world + 2, dtype=torch.int64, device=dev)
+        leaving = torch.empty(n, dtype=torch.uint8, device=dev)
+        steps = ("route_keys", "count", "pack", "text", "commit", "reclaim", "install")
+        ms = {k: [] for k in steps}
+        for _ in range(repeats):
+            dt, rk = timed(lambda: directory.route_keys(0))
+            ms["route_keys"].append(dt)
+            ms["count"].append(timed(lambda: eng.migrate_out_device(TS, rk, dmap, world, me, None, counts, leaving,
+                                                                    stream=cur))[0])
+            c = counts.tolist()
+            n_rows, n_leave = sum(c[:world]), c[world]
+            assert c[world + 1] == 0 and n_rows == n_leave
+            rows = torch.empty((n_rows, 4), dtype=torch.int64, device=dev)
+            row_ids = torch.empty(n_rows, dtype=torch.int64, device=dev)
+            ms["pack"].append(timed(lambda: eng.migrate_out_device(TS, rk, dmap, world, me, rows, counts, None,
+                                                                   capacity=n_rows, stream=cur, row_ids=row_ids))[0])
+            dt, (sbuf, soffs) = timed(lambda: directory.text_of(row_ids))
+            ms["text"].append(dt)
+            n_bytes = int(soffs[-1].item())
+            room = int(((soffs[1:] - soffs[:-1] + 7) & ~7).sum().item())
+            ms["commit"].append(timed(lambda: eng.migrate_out_device(TS, rk, dmap, world, me, rows, counts, leaving,
+                                                                     commit=True, capacity=n_rows, stream=cur))[0])
+            eng.synchronize()
+            ms["reclaim"].append(timed(lambda: directory.reclaim_device(leaving))[0])
+            assert directory.usage()[:2] == (n - n_leave, arena - room)
+
+            def install():
+                rid = directory.assign(sbuf, soffs, n_bytes)
+                eng.import_rows(rid, rows[:, 1].contiguous().view(torch.float64), rows[:, 2].contiguous(), stream=cur)
+            ms["install"].append(timed(install)[0])
+            eng.synchronize()
+            assert directory.usage()[:2] == (n, arena)
+            del rk, rows, row_ids, sbuf, soffs
+        ns = 1
+        while ns < 2 * n:
+            ns <<= 1
+        stay = n - n_leave
+        count_bytes = 24 * n + n
+        # at least: per step, the arrays it must read and write once
+        nbytes = {
+            "route_keys": 16 * n + arena,                             # iloc, the padded text, the keys
+            "count": count_bytes,
+            "pack": count_bytes + 24 * n + 40 * n_rows,               # count pass, row pass, rows + ids out
+            # lengths (ids, iloc in, lens out), scan, bytes (ids, iloc, offsets in), zero fill, text in and out
+            "text": 24 * n_rows + 16 * n_rows + 24 * n_rows + 3 * n_bytes,
+            "commit": count_bytes + 24 * n + 32 * n_rows + 8 * n + 16 * n_leave,
+            "reclaim": 9 * n + 8 * n_leave + 20 * ns + 2 * (arena - room) + 40 * stay + 16 * ns + 20 * stay,
+            "install": 2 * n_bytes + 16 * n_rows + room + 20 * n_rows + 40 * n_rows,
+        }
+        res = {"keys": n, "rows_sent": n_rows, "text_bytes_sent": n_bytes, "arena_bytes": arena, "arena_bytes_sent": room}
+        for k in steps:
+            med = statistics.median(ms[k])
+            res[f"{k}_ms"] = round(med, 4)
+            res[f"{k}_all_ms"] = [round(x, 4) for x in ms[k]]
+            res[f"{k}_bytes"] = nbytes[k]
+            res[f"{k}_of_copy_rate"] = round(nbytes[k] / (med * 1e-3) / COPY_RATE, 4)
+        res["migrate_local_ms"] = round(sum(res[f"{k}_ms"] for k in steps), 4)
+        eng.close()
+        directory.close()
+        return res
+
     with torch.cuda.stream(torch.cuda.Stream(dev)):
-        run(1 << 16, 2, not args.no_snapshot)          # warm-up: every call once at a small size
-        line = run(args.keys, args.repeats, not args.no_snapshot)
+        if args.text:
+            run_text(1 << 16, 2)                       # warm-up: every call at a small size
+            line = run_text(args.keys, args.repeats)
+        else:
+            run(1 << 16, 2, not args.no_snapshot)      # warm-up: every call once at a small size
+            line = run(args.keys, args.repeats, not args.no_snapshot)
     line["repeats"] = args.repeats
     print(json.dumps(line), flush=True)
     if args.out:
