@@ -51,7 +51,9 @@ EXPORTED = ("tbe_fill_rate", "tbe_create", "tbe_destroy", "tbe_last_error", "tbe
             "tbe_approx_collect_classes", "tbe_approx_sync_classes", "tbe_approx_sync_classes_stream",
             "tbe_approx_refresh_classes",
             "tbe_refresh_classes", "tbe_refresh_classes_device", "tbe_wait_batch_tick_classes_device",
-            "tbe_migrate_out_device", "tbe_migrate_out", "tbe_migrate_out_ids_device", "tbe_migrate_out_ids")
+            "tbe_migrate_out_device", "tbe_migrate_out", "tbe_migrate_out_ids_device", "tbe_migrate_out_ids",
+            "tbe_queue_export_ids_device", "tbe_queue_export_ids", "tbe_queue_import_ids_device",
+            "tbe_queue_import_ids", "tbe_queue_migrate_out_ids_device", "tbe_queue_migrate_out_ids")
 # k_stats_batch's shape (csrc/tbe_stats.hpp): requests per workgroup trip and slots of its
 # LDS table; the tests size their cases by them
 STATS_TILE, STATS_SLOTS = 4096, 2048
@@ -202,6 +204,20 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.tbe_migrate_out_ids_device.argtypes = lib.tbe_migrate_out_device.argtypes[:-1] + [c_void_p, c_void_p]
     lib.tbe_migrate_out_ids.restype = c_int32
     lib.tbe_migrate_out_ids.argtypes = lib.tbe_migrate_out.argtypes + [c_void_p]
+    lib.tbe_queue_migrate_out_ids_device.restype = c_int32
+    lib.tbe_queue_migrate_out_ids_device.argtypes = lib.tbe_migrate_out_ids_device.argtypes
+    lib.tbe_queue_migrate_out_ids.restype = c_int32
+    lib.tbe_queue_migrate_out_ids.argtypes = lib.tbe_migrate_out_ids.argtypes
+    lib.tbe_queue_export_ids_device.restype = c_int32
+    lib.tbe_queue_export_ids_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64,
+                                                c_void_p, c_int32, c_void_p]
+    lib.tbe_queue_export_ids.restype = c_int32
+    lib.tbe_queue_export_ids.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64,
+                                         c_void_p, c_int32]
+    lib.tbe_queue_import_ids_device.restype = c_int32
+    lib.tbe_queue_import_ids_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]
+    lib.tbe_queue_import_ids.restype = c_int32
+    lib.tbe_queue_import_ids.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64]
     lib.tbe_wait_batch.restype = c_int32
     lib.tbe_wait_batch.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_int64, c_void_p,
                                    c_void_p, POINTER(c_uint64)]

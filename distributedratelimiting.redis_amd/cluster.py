@@ -26,6 +26,11 @@ Exchanges:
   owner's string directory resolves them byte for byte (DESIGN.md §7 "Routing text").
 * ``route_cancel``: cancellations of queued requests travel to the key's owner the same
   way (one all-to-all each way).
+* ``migrate`` / ``migrate_queueing``: a new owner map comes into force between two batches;
+  the buckets whose owner changes travel to their new owners (one all-to-all of rows), and for
+  a queueing engine their queued waits travel with them, in order and with their request ids
+  (a second all-to-all of ring entries), which therefore must be unique across owners
+  (DESIGN.md §7 "Migrating buckets", "Migrating queued waits").
 * ``approx_epoch``: the ApproximateTokenBucket global tier.  Each rank is one client
   (A:9-599) holding a local tier for every shared key; at every refresh epoch the
   per-key consumed counts are exchanged -- all-gather for exact per-client prefix
@@ -1330,6 +1335,218 @@ def _migrate_host(engine, directory, new_map, ts_us, world, rank, group):
         t[ids.astype(np.int64)] = r[:, 2]
         engine.import_state(v, t)
     return int(rows.shape[0]), int(r.shape[0])
+
+
+# ------------------------------------------------------------------ migrating queued waits
+def plan_queue_migration(keys_of_id, v, t_us, cls, live, qcount, owner_map, world: int, rank: int):
+    """``plan_migration`` for a queueing engine (tbe_queue_migrate_out_ids_device's rule in
+    numpy, its reference and the body of ``migrate_queueing``'s host path).  qcount[i]: the
+    entries queued on id i.  A leaving id sends a row when its bucket row is live OR its queue
+    is not empty (a key with queued requests is never dead); such a row travels verbatim, a
+    lapsed or absent t_us included, and its word 3 is ``class | qcount << 8``.  An orphan is an
+    id no key holds whose row is live or whose queue is not empty.  Returns (rows, counts,
+    leaving, row_ids): ``plan_migration``'s three and the rows' ids in send order (int64)."""
+    qcount = np.asarray(qcount, dtype=np.int64)
+    alive = np.asarray(live, dtype=bool) | (qcount > 0)
+    rows, counts, leaving, row_ids = _plan_migration(keys_of_id, v, t_us, cls, alive, owner_map, world, rank)
+    rows[:, 3] |= qcount[row_ids] << 8
+    return rows, counts, leaving, row_ids
+
+
+def _preflight_queue(local_error, classes, like, group) -> None:
+    """``_preflight`` for ``migrate_queueing``: the class tables compared hold the five options
+    of every queueing class."""
+    import torch
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    width = 5
+    n_words = 1 + width * 256
+    words = torch.zeros(n_words, dtype=torch.int64)
+    words[0] = len(classes)
+    words[1:1 + width * len(classes)] = torch.tensor(classes, dtype=torch.int64).reshape(-1)
+    words = words.to(like.device)
+    allw = torch.empty(world * n_words, dtype=torch.int64, device=like.device)
+    _all_gather(allw, words, group=group)
+    if local_error is None and not bool((allw.view(world, -1) == words).all().item()):
+        local_error = "the ranks' engines hold different class tables"
+    bad = torch.tensor([0 if local_error is None else 1], dtype=torch.int64, device=like.device)
+    _all_reduce_sum(bad, group=group)
+    if int(bad.item()):
+        raise ValueError("cluster.migrate_queueing refused, nothing changed: "
+                         + (local_error or "another rank failed its pre-flight check"))
+
+
+def _queue_class_table(engine):
+    """[(token_limit, tokens_per_period, period_ticks, queue_limit, order)], class 0 first."""
+    return [tuple(int(x) for x in c) for c in engine.queue_classes()]
+
+
+def migrate_queueing(engine, directory, new_map, ts_us: int, group=None) -> Tuple[int, int, int, int]:
+    """``migrate`` for a queueing engine (TokenBucketWithQueue), plain or with queueing limit
+    classes: a moved key keeps its bucket row, its class and its queued waits, in order and with
+    their request ids, and the new owner's replenish tick grants them exactly as the old
+    owner's would have (DESIGN.md §7 "Migrating queued waits").  A collective with ``migrate``'s
+    calling convention; returns (rows sent, rows received, entries sent, entries received).
+
+    A leaving key sends a row when its bucket row is live at ts_us or its queue is not empty
+    (``plan_queue_migration``); word 3 of a row carries the class and the number of queued
+    entries, and the entries themselves (``request_id << 16 | permits``, oldest first) follow
+    in a second all-to-all whose splits both sides derive from the rows.  The receiver assigns
+    ids, sets the classes (first: a class assignment requires an empty queue and resets the
+    header), installs the rows and then the queues.  With a ``DeviceDirectory`` everything
+    stays in HBM (``queue_migrate_out_device``, ``queue_export_ids_device(clear=True)``,
+    ``reclaim_device``, ``assign``, ``set_class_device``, ``import_rows``,
+    ``queue_import_ids_device``); with a ``HostDirectory`` the same steps run on numpy arrays
+    over ``export_state`` / ``import_state`` and the host-buffer queue calls.  The pre-flight is
+    ``migrate``'s; the class tables compared hold all five options of every class.
+
+    Request ids travel verbatim, so after a migration a key's queue mixes ids minted by its
+    old and its new owner: the owners must mint ids that are unique across owners, e.g.
+    ``id_base = (rank << 40) + counter``, which stays below 2^47.  Afterwards
+    ``route_batch(wait, ..., owner_map=new_map)`` and ``route_cancel(..., owner_map=new_map)``
+    behave as if the new map had been in force from the start.  NewestFirst evictions of the
+    last wait batch (``evicted()``) must be fetched before migrating.  Text-keyed directories,
+    lease counters and the approximate kind are not covered."""
+    import torch.distributed as dist
+    from . import _capi
+    from .strdir import HostStringDirectory, StringDirectory
+    kind = int(getattr(engine, "KIND", _capi.TBE_KIND_TOKEN_BUCKET))
+    if kind == _capi.TBE_KIND_TOKEN_BUCKET:
+        raise ValueError("cluster.migrate_queueing: a token-bucket engine has no queues; use cluster.migrate")
+    if kind == _capi.TBE_KIND_APPROXIMATE:
+        raise ValueError("cluster.migrate_queueing: the approximate kind's tier is replicated and its requests "
+                         "are not routed, so there is nothing to move")
+    if isinstance(directory, (StringDirectory, HostStringDirectory)):
+        raise ValueError("cluster.migrate_queueing: text-keyed queueing migration is out of scope")
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    if new_map is not None and not _is_cuda(new_map):
+        check_owner_map(new_map, world)
+    if isinstance(directory, DeviceDirectory):
+        return _migrate_queue_device(engine, directory, new_map, int(ts_us), world, rank, group)
+    return _migrate_queue_host(engine, directory, new_map, int(ts_us), world, rank, group)
+
+
+def _migrate_queue_device(engine, directory, new_map, ts_us, world, rank, group):
+    import torch
+    from . import _capi
+    dev = torch.device("cuda", engine.config.device if engine.config.device >= 0 else torch.cuda.current_device())
+    st = device_stream(dev)
+    cap = directory.capacity
+    dmap = _device_map(new_map, dev, world)
+    counts = torch.zeros(world + 2, dtype=torch.int64, device=dev)
+    leaving = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    covered = engine.n_keys >= cap
+    if covered:
+        kof = directory.keys_of(torch.arange(cap, dtype=torch.int64, device=dev))
+        engine.queue_migrate_out_device(ts_us, kof, dmap, world, rank, None, counts, leaving, stream=st)
+    rc = torch.empty(world, dtype=torch.int64, device=dev)
+    _all_to_all(rc, counts[:world].contiguous(), group=group)
+    sc_l, rc_l = counts.tolist(), rc.tolist()
+    try:
+        held = directory.size()
+        err = _room_error(engine.n_keys, directory, held, sc_l, sum(rc_l), world)
+    except _capi.TbeError as ex:
+        err = str(ex)
+    _preflight_queue(err, _queue_class_table(engine), counts, group)
+    n_send = sum(sc_l[:world])
+    rows = torch.empty((n_send, 4), dtype=torch.int64, device=dev)
+    row_ids = torch.empty(n_send, dtype=torch.int64, device=dev)
+    engine.queue_migrate_out_device(ts_us, kof, dmap, world, rank, rows if n_send else None, counts, leaving,
+                                    commit=True, capacity=n_send, stream=st, row_ids=row_ids if n_send else None)
+    # the rows' queues, next and with nothing in between; the entry splits are the rows' counts
+    # summed over each destination's group (the one host synchronisation of the source side)
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    ends = torch.cumsum(torch.tensor(sc_l[:world], dtype=torch.int64, device=dev), 0)
+    cum = torch.cat([zero, torch.cumsum(rows[:, 3] >> 8, 0)])
+    es_l = torch.diff(cum[ends], prepend=zero).tolist()
+    n_ent = sum(es_l)
+    entries = torch.empty(n_ent, dtype=torch.int64, device=dev)
+    if n_send:
+        qcount = torch.empty(n_send, dtype=torch.int32, device=dev)
+        n_out = torch.zeros(1, dtype=torch.int64, device=dev)
+        engine.queue_export_ids_device(row_ids, qcount, None, entries if n_ent else None, n_out, clear=True,
+                                       capacity=n_ent, stream=st)
+    directory.reclaim_device(leaving)
+    recv = torch.empty((sum(rc_l), 4), dtype=torch.int64, device=dev)
+    _all_to_all(recv, rows, rc_l, sc_l[:world], group=group)
+    rq = (recv[:, 3] >> 8).contiguous()
+    rcum = torch.cat([zero, torch.cumsum(rq, 0)])
+    er_l = torch.diff(rcum[torch.cumsum(torch.tensor(rc_l, dtype=torch.int64, device=dev), 0)], prepend=zero).tolist()
+    rent = torch.empty(sum(er_l), dtype=torch.int64, device=dev)
+    _all_to_all(rent, entries, er_l, es_l, group=group)
+    if recv.shape[0]:
+        ids = directory.assign(recv[:, 0].contiguous())
+        directory.check()
+        if getattr(engine, "classed", False):   # first: it requires an empty queue and resets the header
+            engine.set_class_device(ids, (recv[:, 3] & 0xFF).to(torch.uint8), stream=st)
+        engine.import_rows(ids, recv[:, 1].contiguous().view(torch.float64), recv[:, 2].contiguous(), stream=st)
+        engine.queue_import_ids_device(ids.contiguous(), rq.to(torch.int32), rent if rent.numel() else None, stream=st)
+    return n_send, sum(rc_l), n_ent, sum(er_l)
+
+
+def _migrate_queue_host(engine, directory, new_map, ts_us, world, rank, group):
+    import torch
+    import torch.distributed as dist
+    cap = directory.capacity
+    classes = _queue_class_table(engine)
+    classed = bool(getattr(engine, "classed", False))
+    v, t = engine.export_state()
+    v, t = np.array(v, dtype=np.float64), np.array(t, dtype=np.int64)
+    n_keys = int(getattr(engine, "n_keys", v.shape[0]))
+    err = None
+    if n_keys < cap or v.shape[0] < cap:
+        err = "the engine has fewer keys than the directory has ids"
+        rows, counts = np.zeros((0, 4), dtype=np.int64), np.zeros(world + 2, dtype=np.int64)
+        leaving, row_ids = np.zeros(cap, dtype=np.uint8), np.zeros(0, dtype=np.int64)
+    else:
+        v, t = v[:cap], t[:cap]
+        keys_of_id = np.full(cap, NO_ID, dtype=np.uint64)
+        for k, i in directory.ids.items():
+            keys_of_id[i] = k
+        all_ids = np.arange(cap, dtype=np.uint64)
+        cls = engine.get_class(all_ids) if classed else np.zeros(cap, dtype=np.uint8)
+        ttl = np.array([class_ttl_ms(*c[:3]) for c in classes], dtype=np.int64)[cls]
+        qcount = engine.queue_export_ids(all_ids, capacity=0)[0]
+        rows, counts, leaving, row_ids = plan_queue_migration(keys_of_id, v, t, cls, rows_live(t, ts_us, ttl), qcount,
+                                                              new_map, world, rank)
+    sc = torch.from_numpy(counts[:world].copy())
+    rc = torch.empty_like(sc)
+    dist.all_to_all_single(rc, sc, group=group)
+    sc_l, rc_l = counts.tolist(), rc.tolist()
+    if err is None:
+        err = "the directory is over capacity" if directory.overflow else \
+            _room_error(n_keys, directory, directory.size(), sc_l, sum(rc_l), world)
+    _preflight_queue(err, classes, sc, group)
+    gone = np.flatnonzero(leaving)
+    v[gone] = np.array([c[0] for c in classes], dtype=np.float64)[cls[gone]]
+    t[gone] = ABSENT
+    engine.import_state(v, t)
+    _, start, entries, _ = engine.queue_export_ids(row_ids.astype(np.uint64), clear=True)
+    directory.reclaim(gone)
+    recv = torch.empty((sum(rc_l), 4), dtype=torch.int64)
+    dist.all_to_all_single(recv, torch.from_numpy(np.ascontiguousarray(rows)), output_split_sizes=rc_l,
+                           input_split_sizes=sc_l[:world], group=group)
+    r = recv.numpy()
+    # rows are grouped by destination and entries follow row order: the entry splits are the
+    # entry starts at the group boundaries; the receiver reads its own from the rows' word 3
+    ends = np.cumsum(np.asarray(sc_l[:world], dtype=np.int64))
+    es_l = np.diff(np.asarray(start, dtype=np.int64)[ends], prepend=0).tolist()
+    rq = r[:, 3] >> 8
+    rcum = np.concatenate([[0], np.cumsum(rq)])
+    er_l = np.diff(rcum[np.cumsum(np.asarray(rc_l, dtype=np.int64))], prepend=0).tolist()
+    rent = torch.empty(int(sum(er_l)), dtype=torch.int64)
+    dist.all_to_all_single(rent, torch.from_numpy(np.ascontiguousarray(entries).view(np.int64).copy()),
+                           output_split_sizes=er_l, input_split_sizes=es_l, group=group)
+    if r.shape[0]:
+        ids = directory.assign(r[:, 0].copy().view(np.uint64))
+        directory.check()
+        if classed:   # first: it requires an empty queue and resets the header
+            engine.set_class(ids, (r[:, 3] & 0xFF).astype(np.uint8))
+        v[ids.astype(np.int64)] = r[:, 1].copy().view(np.float64)
+        t[ids.astype(np.int64)] = r[:, 2]
+        engine.import_state(v, t)
+        engine.queue_import_ids(ids, rq.astype(np.uint32), rent.numpy().view(np.uint64))
+    return int(rows.shape[0]), int(r.shape[0]), int(sum(es_l)), int(sum(er_l))
 
 
 # Text-keyed buckets.  The protocol of the u64 paths with three differences: the key-of-id

@@ -4662,6 +4662,10 @@ __global__ void k_rows_write(Slot *__restrict__ table, const uint64_t *__restric
 //                      row_ids (tbe_migrate_out_ids_device) each row's id beside it
 //   k_mig_commit       leaving ids' rows rewritten absent, their lease counters zeroed
 // flags[0]: a map entry >= n_owners (nothing is written); flags[1]: the commit is refused.
+// With the queue headers as a trailing argument (tbe_queue_migrate_out_ids_device, "Migrating
+// queued waits") k_mig_pass also loads the tile's headers: an id with queued entries counts as
+// live whatever its row holds, and word 3 of its row is class | entries << 8.  The token-bucket
+// entry points launch the forms without that argument.
 struct MigArgs {
     const Slot *table;
     const uint64_t *key_of_id;   // count entries, kMigNoKey: no key holds the id
@@ -4681,11 +4685,12 @@ __device__ __forceinline__ uint32_t mig_dest(const MigArgs &A, uint64_t key) {
     return A.map ? (uint32_t)A.map[key_vnode(key)] : key_owner(key, A.n_owners);
 }
 
-template <bool WRITE>
+template <bool WRITE, typename... QH>   // QH: empty, or the queueing kind's `const HW *` headers
 __global__ __launch_bounds__(kBlock) void k_mig_pass(MigArgs A, unsigned long long *__restrict__ tile_n,
                                                      uint8_t *__restrict__ leaving, uint32_t *__restrict__ flags,
                                                      int64_t *__restrict__ rows, uint64_t capacity,
-                                                     uint64_t *__restrict__ row_ids) {
+                                                     uint64_t *__restrict__ row_ids, QH... qh) {
+    static_assert(sizeof...(QH) <= 1, "at most one header array");
     __shared__ uint16_t cnt[kLiveItems * kWaves * kDigits];   // [item][wave][owner], 16 KB
     __shared__ unsigned long long start[kDigits];
     __shared__ uint32_t part[2 * kWaves];
@@ -4702,6 +4707,7 @@ __global__ __launch_bounds__(kBlock) void k_mig_pass(MigArgs A, unsigned long lo
     uint64_t key[kLiveItems];
     Slot s[kLiveItems];
     uint32_t dest[kLiveItems], rank[kLiveItems], cbyte[kLiveItems];
+    [[maybe_unused]] uint32_t qn[kLiveItems];   // queued entries (with headers)
     bool send[kLiveItems];
     uint32_t n_leave = 0, n_orphan = 0, bad_map = 0;
     // every load of the tile first, independent of one another, then the arithmetic
@@ -4717,7 +4723,8 @@ __global__ __launch_bounds__(kBlock) void k_mig_pass(MigArgs A, unsigned long lo
             if constexpr (WRITE) s[k] = slot_load_nt(&A.table[id]);
             else s[k].t_us = ld_nt(&A.table[id].t_us);
             if (A.cls) cbyte[k] = A.cls[id];
-        }
+            if constexpr (sizeof...(QH) != 0) qn[k] = (uint32_t)(qh_widen((qh, ...)[id]) >> 16) & 0xFFFFu;
+        } else if constexpr (sizeof...(QH) != 0) qn[k] = 0;
     }
 #pragma unroll
     for (int k = 0; k < kLiveItems; ++k) {
@@ -4727,7 +4734,8 @@ __global__ __launch_bounds__(kBlock) void k_mig_pass(MigArgs A, unsigned long lo
         bool leave = false;
         if (i < A.count) {
             const int64_t exp_lt = A.by_class ? (A.x - A.par[cbyte[k]].ttl_ms) * 1000 : A.x;
-            const bool live = row_live(s[k].t_us, exp_lt);
+            bool live = row_live(s[k].t_us, exp_lt);
+            if constexpr (sizeof...(QH) != 0) live = live || qn[k] != 0;   // a queued key is never dead
             if (key[k] != kMigNoKey) {
                 const uint32_t d = mig_dest(A, key[k]);
                 if (d >= A.n_owners) bad_map = 1;
@@ -4785,7 +4793,9 @@ __global__ __launch_bounds__(kBlock) void k_mig_pass(MigArgs A, unsigned long lo
             if (pos < capacity) {
                 i64x2 *out = reinterpret_cast<i64x2 *>(rows + 4 * pos);
                 const i64x2 a = {(long long)key[k], (long long)__double_as_longlong(s[k].v)};
-                const i64x2 b = {(long long)s[k].t_us, (long long)cbyte[k]};
+                long long w3 = (long long)cbyte[k];
+                if constexpr (sizeof...(QH) != 0) w3 |= (long long)qn[k] << 8;
+                const i64x2 b = {(long long)s[k].t_us, w3};
                 st_nt(out, a);
                 st_nt(out + 1, b);
                 if (row_ids) row_ids[pos] = A.first + base + (uint64_t)k * kBlock + tid;
@@ -4878,6 +4888,304 @@ __global__ __launch_bounds__(kBlock) void k_mig_commit(MigArgs A, Slot *__restri
     if (st_ok) {
         st_ok[id] = 0;
         st_failed[id] = 0;
+    }
+}
+
+// ---- bulk queue export and import by id list (tbe_queue_export_ids_device /
+// tbe_queue_import_ids_device, DESIGN.md §7 "Migrating queued waits").  Both work on tiles of
+// kQxTile listed ids, kQxItems consecutive ids per thread, and in three steps like the export
+// of live rows: the tiles' entry counts, one workgroup that scans them, and a pass that scans
+// its own tile again and then spreads the tile's (id, j) pairs over the lanes -- entry e of the
+// tile belongs to the last id whose scanned start is <= e (a binary search in LDS), so
+// neighbouring lanes move neighbouring entries whatever the queues' lengths.  No workgroup
+// waits for another and no atomic touches an output position.
+//   export  k_qx_count, k_qx_scan, k_qx_write
+//   import  k_qi_count, k_qi_scan, k_qi_pass<false> (judges everything), k_qi_pass<true>
+constexpr int kQxItems = kLiveItems;
+constexpr int kQxTile = kBlock * kQxItems;   // 2048 ids per workgroup
+constexpr int kQxUnroll = 4;                 // entries per thread per round of the expansion
+
+template <int BLOCK>
+__device__ __forceinline__ unsigned long long block_excl_scan64(unsigned long long x, unsigned long long *wsum,
+                                                                unsigned long long *total) {
+    constexpr int W = BLOCK / 64;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned long long v = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long y = __shfl_up(v, o, 64);
+        if (lane >= o) v += y;
+    }
+    if (lane == 63) wsum[w] = v;
+    __syncthreads();
+    unsigned long long pre = 0, tot = 0;
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        const unsigned long long s = wsum[j];
+        pre += (j < w) ? s : 0ull;
+        tot += s;
+    }
+    *total = tot;
+    __syncthreads();
+    return pre + v - x;
+}
+
+// tile_n[j] becomes the entries of the tiles before j; returns their sum (every thread).
+__device__ __forceinline__ unsigned long long qx_scan_tiles(unsigned long long *__restrict__ tile_n, uint64_t ntiles,
+                                                            unsigned long long *wsum) {
+    unsigned long long carry = 0;
+    for (uint64_t j0 = 0; j0 < ntiles; j0 += kLiveScan) {
+        const uint64_t j = j0 + threadIdx.x;
+        const unsigned long long c = j < ntiles ? tile_n[j] : 0ull;
+        unsigned long long tot;
+        const unsigned long long pre = block_excl_scan64<kLiveScan>(c, wsum, &tot);
+        if (j < ntiles) tile_n[j] = carry + pre;
+        carry += tot;
+    }
+    return carry;
+}
+
+// The index of the last id of the tile whose start is <= e (start[0] = 0 <= e; the starts
+// never decrease, and ids past the list's end start at the tile's total).
+__device__ __forceinline__ uint32_t qx_owner(const uint32_t *start, uint32_t e) {
+    uint32_t lo = 0;
+#pragma unroll
+    for (uint32_t step = kQxTile / 2; step; step >>= 1)
+        if (start[lo + step] <= e) lo += step;
+    return lo;
+}
+
+// A thread's ids of the tile and their widened headers, every load issued before any is used.
+// An id past the list's end or >= n_keys reads nothing and gets header 0; returns whether any
+// listed id was >= n_keys.
+template <typename HW>
+__device__ __forceinline__ bool qx_load(const uint64_t *__restrict__ ids, uint64_t n, uint64_t n_keys,
+                                        const HW *__restrict__ qhdr, uint64_t (&id)[kQxItems],
+                                        uint64_t (&h)[kQxItems]) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * kQxTile + (uint64_t)threadIdx.x * kQxItems;
+#pragma unroll
+    for (int k = 0; k < kQxItems; ++k) id[k] = i0 + k < n ? ld_nt(ids + i0 + k) : ~0ull;
+    HW raw[kQxItems];
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < kQxItems; ++k) {
+        const bool ok = id[k] < n_keys;
+        bad |= i0 + k < n && !ok;
+        raw[k] = ok ? qhdr[id[k]] : (HW)0;
+    }
+#pragma unroll
+    for (int k = 0; k < kQxItems; ++k) h[k] = qh_widen(raw[k]);
+    return bad;
+}
+
+// flags[0]: an id >= n_keys (nothing is written); flags[1]: the clearing call is refused.
+template <typename HW>
+__global__ __launch_bounds__(kBlock) void k_qx_count(const uint64_t *__restrict__ ids, uint64_t n, uint64_t n_keys,
+                                                     const HW *__restrict__ qhdr,
+                                                     unsigned long long *__restrict__ tile_n,
+                                                     uint32_t *__restrict__ flags) {
+    __shared__ uint32_t wsum[kWaves];
+    uint64_t id[kQxItems], h[kQxItems];
+    if (qx_load(ids, n, n_keys, qhdr, id, h)) flags[0] = 1u;
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < kQxItems; ++k) c += (uint32_t)(h[k] >> 16) & 0xFFFFu;
+    uint32_t tot;   // <= kQxTile * 65535
+    (void)block_excl_scan<kBlock>(c, wsum, &tot);
+    if (threadIdx.x == 0) tile_n[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(kLiveScan) void k_qx_scan(unsigned long long *__restrict__ tile_n, uint64_t ntiles,
+                                                       unsigned long long *__restrict__ total, uint64_t capacity,
+                                                       int32_t clear, unsigned long long *__restrict__ n_entries,
+                                                       uint32_t *__restrict__ flags, uint32_t *__restrict__ sticky) {
+    __shared__ unsigned long long wsum[kLiveScan / 64];
+    const unsigned long long sum = qx_scan_tiles(tile_n, ntiles, wsum);
+    if (threadIdx.x == 0) {
+        *total = sum;
+        const bool refuse = flags[0] || (clear && sum > capacity);
+        flags[1] = refuse ? 1u : 0u;
+        if (refuse) *sticky = 1u;
+        if (!flags[0]) *n_entries = sum;
+    }
+}
+
+template <typename HW>
+__global__ __launch_bounds__(kBlock) void k_qx_write(const uint64_t *__restrict__ ids, uint64_t n, uint64_t n_keys,
+                                                     HW *__restrict__ qhdr, const uint64_t *__restrict__ ring,
+                                                     uint32_t cap, QClsView QC,
+                                                     const unsigned long long *__restrict__ tile_at,
+                                                     const unsigned long long *__restrict__ total,
+                                                     const uint32_t *__restrict__ flags, uint32_t *__restrict__ qcount,
+                                                     uint64_t *__restrict__ entry_start, uint64_t *__restrict__ entries,
+                                                     uint64_t capacity, int32_t clear) {
+    __shared__ uint32_t start[kQxTile];    // first entry of the id, relative to the tile
+    __shared__ uint64_t rbase[kQxTile];    // first ring word of the id
+    __shared__ uint32_t hl[kQxTile];       // head | ring length << 16
+    __shared__ uint32_t wsum[kWaves];
+    if (flags[0]) return;   // (the whole grid)
+    const int tid = threadIdx.x;
+    const uint64_t i0 = (uint64_t)blockIdx.x * kQxTile + (uint64_t)tid * kQxItems;
+    uint64_t id[kQxItems], h[kQxItems];
+    (void)qx_load(ids, n, n_keys, qhdr, id, h);
+    uint32_t len[kQxItems], sum = 0;
+#pragma unroll
+    for (int k = 0; k < kQxItems; ++k) {
+        const uint32_t c = (uint32_t)(h[k] >> 16) & 0xFFFFu;
+        len[k] = (c && QC.cls) ? QC.par[QC.cls[id[k]]].o.cap : cap;   // the key wraps at its class's ring length
+        sum += c;
+    }
+    uint32_t tot;
+    uint32_t run = block_excl_scan<kBlock>(sum, wsum, &tot);
+    const uint64_t at = tile_at[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < kQxItems; ++k) {
+        const uint32_t c = (uint32_t)(h[k] >> 16) & 0xFFFFu, e = tid * kQxItems + k;
+        start[e] = run;
+        rbase[e] = id[k] * (uint64_t)cap;
+        hl[e] = (uint32_t)(h[k] & 0xFFFFu) | (len[k] << 16);
+        if (i0 + k < n) {
+            qcount[i0 + k] = c;
+            if (entry_start) entry_start[i0 + k] = at + run;
+        }
+        run += c;
+    }
+    if (entry_start && blockIdx.x == gridDim.x - 1 && tid == 0) entry_start[n] = *total;
+    __syncthreads();
+    if (at < capacity) {
+        for (uint32_t e0 = tid; e0 < tot; e0 += kBlock * kQxUnroll) {
+            uint64_t x[kQxUnroll];
+#pragma unroll
+            for (int u = 0; u < kQxUnroll; ++u) {   // the round's ring loads, independent of one another
+                const uint32_t e = e0 + u * kBlock;
+                x[u] = 0;
+                if (e < tot && at + e < capacity) {
+                    const uint32_t o = qx_owner(start, e), w = hl[o];
+                    x[u] = ld_nt(ring + rbase[o] + ((w & 0xFFFFu) + (e - start[o])) % (w >> 16));
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kQxUnroll; ++u) {
+                const uint32_t e = e0 + u * kBlock;
+                if (e < tot && at + e < capacity) st_nt(entries + at + e, x[u]);
+            }
+        }
+    }
+    if (clear && !flags[1]) {   // the empty queue with head 0, as k_set_class_write leaves it
+#pragma unroll
+        for (int k = 0; k < kQxItems; ++k)
+            if (i0 + k < n) qhdr[id[k]] = (HW)0;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_qi_count(const uint32_t *__restrict__ qcount, uint64_t n,
+                                                     unsigned long long *__restrict__ tile_n) {
+    __shared__ unsigned long long wsum[kWaves];
+    const uint64_t i0 = (uint64_t)blockIdx.x * kQxTile + (uint64_t)threadIdx.x * kQxItems;
+    unsigned long long c = 0;
+#pragma unroll
+    for (int k = 0; k < kQxItems; ++k) c += i0 + k < n ? ld_nt(qcount + i0 + k) : 0u;
+    unsigned long long tot;
+    (void)block_excl_scan64<kBlock>(c, wsum, &tot);
+    if (threadIdx.x == 0) tile_n[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(kLiveScan) void k_qi_scan(unsigned long long *__restrict__ tile_n, uint64_t ntiles,
+                                                       uint64_t n_entries, uint32_t *__restrict__ bad) {
+    __shared__ unsigned long long wsum[kLiveScan / 64];
+    const unsigned long long sum = qx_scan_tiles(tile_n, ntiles, wsum);
+    if (threadIdx.x == 0 && sum != n_entries) *bad = 1u;
+}
+
+// WRITE = false judges every id and every entry of the tile and sets *bad; WRITE = true, after
+// it on the same stream, writes rings and headers, or nothing but the sticky flag when *bad.
+// Q: the engine's own options; QC.cls != NULL: each key's come from its class.
+template <bool WRITE, typename HW>
+__global__ __launch_bounds__(kBlock) void k_qi_pass(const uint64_t *__restrict__ ids, const uint32_t *__restrict__ qcount,
+                                                    uint64_t n, uint64_t n_keys, const uint64_t *__restrict__ entries,
+                                                    uint64_t n_entries, HW *__restrict__ qhdr, uint64_t *__restrict__ ring,
+                                                    uint32_t cap, QOpt Q, QClsView QC,
+                                                    const unsigned long long *__restrict__ tile_at,
+                                                    uint32_t *__restrict__ bad, uint32_t *__restrict__ sticky) {
+    __shared__ uint32_t start[kQxTile];
+    __shared__ uint64_t rbase[kQxTile];
+    __shared__ uint32_t psum[kQxTile];     // permits of the id's entries
+    __shared__ uint32_t tlim[kQxTile];     // TokenLimit of the id's class
+    __shared__ uint32_t wsum[kWaves];
+    if constexpr (WRITE) {
+        if (*bad) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) *sticky = 1u;
+            return;
+        }
+    }
+    const int tid = threadIdx.x;
+    const uint64_t i0 = (uint64_t)blockIdx.x * kQxTile + (uint64_t)tid * kQxItems;
+    const uint64_t at = tile_at[blockIdx.x];
+    uint64_t id[kQxItems], h[kQxItems];
+    uint32_t c[kQxItems];
+    bool wrong = qx_load(ids, n, n_keys, qhdr, id, h);
+#pragma unroll
+    for (int k = 0; k < kQxItems; ++k) c[k] = i0 + k < n ? ld_nt(qcount + i0 + k) : 0u;
+    int32_t qlim[kQxItems];
+    uint32_t sum = 0;
+#pragma unroll
+    for (int k = 0; k < kQxItems; ++k) {
+        const bool ok = id[k] < n_keys;
+        const QOpt &o = (ok && QC.cls) ? QC.par[QC.cls[id[k]]].o : Q;
+        qlim[k] = o.queue_limit;
+        tlim[tid * kQxItems + k] = (uint32_t)(o.token_limit > 0 ? o.token_limit : 0);
+        psum[tid * kQxItems + k] = 0;
+        if constexpr (!WRITE) {
+            // a wrong count moves no entry: the expansion below then stays inside both arrays
+            if (ok && ((h[k] >> 16) & 0xFFFFu) != 0) wrong = true;         // the target queue is not empty
+            if (c[k] > o.cap) wrong = true, c[k] = 0;                      // longer than the key's ring
+            if (!ok) c[k] = 0;
+        }
+        sum += c[k];
+    }
+    uint32_t tot;
+    uint32_t run = block_excl_scan<kBlock>(sum, wsum, &tot);
+    if constexpr (!WRITE) {
+        // entries are read below n_entries only, whatever the counts claim
+        if (at > n_entries || (unsigned long long)tot > n_entries - at) {
+            wrong = true;
+            tot = 0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kQxItems; ++k) {
+        start[tid * kQxItems + k] = run;
+        rbase[tid * kQxItems + k] = id[k] * (uint64_t)cap;
+        run += c[k];
+    }
+    __syncthreads();
+    for (uint32_t e0 = tid; e0 < tot; e0 += kBlock * kQxUnroll) {
+        uint64_t x[kQxUnroll];
+#pragma unroll
+        for (int u = 0; u < kQxUnroll; ++u) {   // the round's entry loads, independent of one another
+            const uint32_t e = e0 + u * kBlock;
+            x[u] = e < tot ? ld_nt(entries + at + e) : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < kQxUnroll; ++u) {
+            const uint32_t e = e0 + u * kBlock;
+            if (e >= tot) continue;
+            const uint32_t o = qx_owner(start, e), p = (uint32_t)(x[u] & 0xFFFFu);
+            if constexpr (WRITE) ring[rbase[o] + (e - start[o])] = x[u];
+            else if (p < 1u || p > tlim[o] || (x[u] >> 63) != 0) wrong = true;   // permits; request id >= 2^47
+            atomicAdd(&psum[o], p);   // (LDS; <= 65535 entries of <= 65535 permits)
+        }
+    }
+    __syncthreads();
+    if constexpr (WRITE) {
+#pragma unroll
+        for (int k = 0; k < kQxItems; ++k)
+            if (i0 + k < n) qhdr[id[k]] = qh_store<HW>(qh_pack(0u, c[k], (int64_t)psum[tid * kQxItems + k]));
+    } else {
+#pragma unroll
+        for (int k = 0; k < kQxItems; ++k)
+            if ((int64_t)psum[tid * kQxItems + k] > (int64_t)(qlim[k] > 0 ? qlim[k] : 0)) wrong = true;   // Q:92
+        if (wrong) *bad = 1u;
     }
 }
 
@@ -5313,6 +5621,10 @@ struct tbe_engine {
     // first call, grown by a larger one
     unsigned long long *mig_ws = nullptr;
     uint64_t mig_ws_cap = 0;
+    // tbe_queue_export_ids_device / tbe_queue_import_ids_device: [0] total entries, [1] the
+    // export's two flags (u32), then one entry count per kQxTile listed ids; grown on demand
+    unsigned long long *qx_ws = nullptr;
+    uint64_t qx_ws_cap = 0;
     // lease statistics (TBE_FLAG_STATS): ok[k] and failed[k] per key and the
     // engine's two totals, allocated at create on an engine with the flag and nowhere else
     unsigned long long *st_ok = nullptr, *st_failed = nullptr, *st_tot = nullptr;
@@ -6553,6 +6865,7 @@ void tbe_destroy(tbe_engine *e) {
     dfree(e->live_tiles);
     dfree(e->rows_bad);
     dfree(e->mig_ws);
+    dfree(e->qx_ws);
     dfree(e->st_ok);
     dfree(e->st_failed);
     dfree(e->st_tot);
@@ -6976,11 +7289,13 @@ tbe_status tbe_import_rows(tbe_engine *e, const uint64_t *ids, const double *v, 
 // stream is joined before and after.
 static tbe_status migrate_args_ok(tbe_engine *e, uint64_t first, uint64_t count, const void *key_of_id,
                                   uint32_t n_owners, uint32_t self, const void *rows, uint64_t capacity,
-                                  const void *counts) {
-    if (e->cfg.kind == TBE_KIND_QUEUEING)
+                                  const void *counts, bool queue = false) {
+    if (e->cfg.kind == TBE_KIND_QUEUEING && !queue)
         return fail(e, TBE_EINVAL, "the queueing kind's rings and request ids do not migrate");
     if (e->cfg.kind == TBE_KIND_APPROXIMATE)
         return fail(e, TBE_EINVAL, "the approximate kind's tier is replicated: there is nothing to migrate");
+    if (e->cfg.kind == TBE_KIND_TOKEN_BUCKET && queue)
+        return fail(e, TBE_EINVAL, "engine has no queues: tbe_migrate_out_ids_device moves its rows");
     if (n_owners < 1 || n_owners > 256 || self >= n_owners) return fail(e, TBE_EINVAL, "n_owners in 1..256, self < n_owners");
     if (first > e->cfg.n_keys || count > e->cfg.n_keys - first)
         return fail(e, TBE_EINVAL, "range out of bounds");
@@ -6988,12 +7303,14 @@ static tbe_status migrate_args_ok(tbe_engine *e, uint64_t first, uint64_t count,
     return TBE_OK;
 }
 
-tbe_status tbe_migrate_out_ids_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count,
-                                      const uint64_t *d_key_of_id, const uint8_t *d_owner_map, uint32_t n_owners,
-                                      uint32_t self, int64_t *d_rows, uint64_t capacity, uint64_t *d_counts,
-                                      uint8_t *d_leaving, int32_t commit, uint64_t *d_row_ids, void *stream) {
+// queue: the queueing kind's form (tbe_queue_migrate_out_ids_device), k_mig_pass with the headers.
+static tbe_status migrate_out_ids_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count,
+                                         const uint64_t *d_key_of_id, const uint8_t *d_owner_map, uint32_t n_owners,
+                                         uint32_t self, int64_t *d_rows, uint64_t capacity, uint64_t *d_counts,
+                                         uint8_t *d_leaving, int32_t commit, uint64_t *d_row_ids, void *stream,
+                                         bool queue) {
     if (!e) return TBE_EINVAL;
-    if (tbe_status rc = migrate_args_ok(e, first, count, d_key_of_id, n_owners, self, d_rows, capacity, d_counts))
+    if (tbe_status rc = migrate_args_ok(e, first, count, d_key_of_id, n_owners, self, d_rows, capacity, d_counts, queue))
         return rc;
     HIP_TRY(e, hipSetDevice(e->device));
     const uint64_t ntiles = (count + kLiveTile - 1) / kLiveTile;
@@ -7033,12 +7350,19 @@ tbe_status tbe_migrate_out_ids_device(tbe_engine *e, int64_t ts_us, uint64_t fir
         A.x = A.by_class ? ts_us / 1000 : (ts_us < 0 ? kAbsent : (ts_us / 1000 - e->params.ttl_ms) * 1000);
         A.n_owners = n_owners;
         A.self = self;
-        k_mig_pass<false><<<(unsigned)ntiles, kBlock, 0, st>>>(A, tile_n, d_leaving, flags, nullptr, 0, nullptr);
-        k_mig_scan<<<1, kLiveScan, 0, st>>>(tile_n, (uint64_t)n_owners * ntiles, total);
-        k_mig_finish<<<1, kBlock, 0, st>>>(tile_n, ntiles, total, n_owners, capacity, commit, counts, flags, e->sticky);
-        if (capacity)
-            k_mig_pass<true><<<(unsigned)ntiles, kBlock, 0, st>>>(A, tile_n, nullptr, flags, d_rows, capacity,
-                                                                  d_row_ids);
+        auto pass = [&](auto write, uint8_t *leave, int64_t *rows, uint64_t cap, uint64_t *rids, auto... qh) {
+            k_mig_pass<decltype(write)::value><<<(unsigned)ntiles, kBlock, 0, st>>>(A, tile_n, leave, flags, rows, cap,
+                                                                                    rids, qh...);
+        };
+        auto passes = [&](auto... qh) {   // qh: the queue headers, or none
+            pass(std::false_type{}, d_leaving, (int64_t *)nullptr, 0, (uint64_t *)nullptr, qh...);
+            k_mig_scan<<<1, kLiveScan, 0, st>>>(tile_n, (uint64_t)n_owners * ntiles, total);
+            k_mig_finish<<<1, kBlock, 0, st>>>(tile_n, ntiles, total, n_owners, capacity, commit, counts, flags,
+                                               e->sticky);
+            if (capacity) pass(std::true_type{}, (uint8_t *)nullptr, d_rows, capacity, d_row_ids, qh...);
+        };
+        if (queue) with_qhdr(e, [&](auto *qh) { passes(static_cast<const std::remove_pointer_t<decltype(qh)> *>(qh)); });
+        else passes();
         if (commit)
             k_mig_commit<<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, st>>>(A, e->table, e->params.cap, flags,
                                                                                        e->st_ok, e->st_failed);
@@ -7051,6 +7375,23 @@ tbe_status tbe_migrate_out_ids_device(tbe_engine *e, int64_t ts_us, uint64_t fir
     return TBE_OK;
 }
 
+tbe_status tbe_migrate_out_ids_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count,
+                                      const uint64_t *d_key_of_id, const uint8_t *d_owner_map, uint32_t n_owners,
+                                      uint32_t self, int64_t *d_rows, uint64_t capacity, uint64_t *d_counts,
+                                      uint8_t *d_leaving, int32_t commit, uint64_t *d_row_ids, void *stream) {
+    return migrate_out_ids_device(e, ts_us, first, count, d_key_of_id, d_owner_map, n_owners, self, d_rows, capacity,
+                                  d_counts, d_leaving, commit, d_row_ids, stream, false);
+}
+
+tbe_status tbe_queue_migrate_out_ids_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count,
+                                            const uint64_t *d_key_of_id, const uint8_t *d_owner_map,
+                                            uint32_t n_owners, uint32_t self, int64_t *d_rows, uint64_t capacity,
+                                            uint64_t *d_counts, uint8_t *d_leaving, int32_t commit,
+                                            uint64_t *d_row_ids, void *stream) {
+    return migrate_out_ids_device(e, ts_us, first, count, d_key_of_id, d_owner_map, n_owners, self, d_rows, capacity,
+                                  d_counts, d_leaving, commit, d_row_ids, stream, true);
+}
+
 tbe_status tbe_migrate_out_device(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count,
                                   const uint64_t *d_key_of_id, const uint8_t *d_owner_map, uint32_t n_owners,
                                   uint32_t self, int64_t *d_rows, uint64_t capacity, uint64_t *d_counts,
@@ -7059,12 +7400,13 @@ tbe_status tbe_migrate_out_device(tbe_engine *e, int64_t ts_us, uint64_t first, 
                                       d_counts, d_leaving, commit, nullptr, stream);
 }
 
-tbe_status tbe_migrate_out_ids(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, const uint64_t *key_of_id,
-                               const uint8_t *owner_map, uint32_t n_owners, uint32_t self, int64_t *rows,
-                               uint64_t capacity, uint64_t *counts, uint8_t *leaving, int32_t commit,
-                               uint64_t *row_ids) {
+static tbe_status migrate_out_ids(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, const uint64_t *key_of_id,
+                                  const uint8_t *owner_map, uint32_t n_owners, uint32_t self, int64_t *rows,
+                                  uint64_t capacity, uint64_t *counts, uint8_t *leaving, int32_t commit,
+                                  uint64_t *row_ids, bool queue) {
     if (!e) return TBE_EINVAL;
-    if (tbe_status rc = migrate_args_ok(e, first, count, key_of_id, n_owners, self, rows, capacity, counts)) return rc;
+    if (tbe_status rc = migrate_args_ok(e, first, count, key_of_id, n_owners, self, rows, capacity, counts, queue))
+        return rc;
     for (uint32_t v = 0; owner_map && v < kOwnerMapSize; ++v)
         if (owner_map[v] >= n_owners) return fail(e, TBE_EINVAL, "owner map entry >= n_owners");
     HIP_TRY(e, hipSetDevice(e->device));
@@ -7084,8 +7426,8 @@ tbe_status tbe_migrate_out_ids(tbe_engine *e, int64_t ts_us, uint64_t first, uin
     if (hrc == hipSuccess && owner_map) hrc = hipMemcpy(d_map, owner_map, kOwnerMapSize, hipMemcpyHostToDevice);
     tbe_status rc = TBE_OK;
     auto run = [&](uint64_t c, int32_t cm) {
-        rc = tbe_migrate_out_ids_device(e, ts_us, first, count, d_keys, owner_map ? d_map : nullptr, n_owners, self,
-                                        c ? d_rows : nullptr, c, d_counts, d_leave, cm, c ? d_ids : nullptr, nullptr);
+        rc = migrate_out_ids_device(e, ts_us, first, count, d_keys, owner_map ? d_map : nullptr, n_owners, self,
+                                    c ? d_rows : nullptr, c, d_counts, d_leave, cm, c ? d_ids : nullptr, nullptr, queue);
         if (rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
         if (rc == TBE_OK && hrc == hipSuccess) hrc = hipMemcpy(counts, d_counts, nc * 8, hipMemcpyDeviceToHost);
     };
@@ -7097,7 +7439,8 @@ tbe_status tbe_migrate_out_ids(tbe_engine *e, int64_t ts_us, uint64_t first, uin
         if (rc == TBE_OK && hrc == hipSuccess) {
             uint64_t total = 0;
             for (uint32_t o = 0; o < n_owners; ++o) total += counts[o];
-            if (counts[n_owners + 1]) refused = "a live row's id is held by no key";
+            if (counts[n_owners + 1]) refused = queue ? "a live row or a queue belongs to an id no key holds"
+                                                      : "a live row's id is held by no key";
             else if (total > capacity) refused = "rows do not fit in capacity";
         }
     }
@@ -7118,11 +7461,234 @@ tbe_status tbe_migrate_out_ids(tbe_engine *e, int64_t ts_us, uint64_t first, uin
     return TBE_OK;
 }
 
+tbe_status tbe_migrate_out_ids(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, const uint64_t *key_of_id,
+                               const uint8_t *owner_map, uint32_t n_owners, uint32_t self, int64_t *rows,
+                               uint64_t capacity, uint64_t *counts, uint8_t *leaving, int32_t commit,
+                               uint64_t *row_ids) {
+    return migrate_out_ids(e, ts_us, first, count, key_of_id, owner_map, n_owners, self, rows, capacity, counts, leaving,
+                           commit, row_ids, false);
+}
+
+tbe_status tbe_queue_migrate_out_ids(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count,
+                                     const uint64_t *key_of_id, const uint8_t *owner_map, uint32_t n_owners,
+                                     uint32_t self, int64_t *rows, uint64_t capacity, uint64_t *counts,
+                                     uint8_t *leaving, int32_t commit, uint64_t *row_ids) {
+    return migrate_out_ids(e, ts_us, first, count, key_of_id, owner_map, n_owners, self, rows, capacity, counts, leaving,
+                           commit, row_ids, true);
+}
+
 tbe_status tbe_migrate_out(tbe_engine *e, int64_t ts_us, uint64_t first, uint64_t count, const uint64_t *key_of_id,
                            const uint8_t *owner_map, uint32_t n_owners, uint32_t self, int64_t *rows,
                            uint64_t capacity, uint64_t *counts, uint8_t *leaving, int32_t commit) {
     return tbe_migrate_out_ids(e, ts_us, first, count, key_of_id, owner_map, n_owners, self, rows, capacity, counts,
                                leaving, commit, nullptr);
+}
+
+// ---- bulk queue export and import by id list (DESIGN.md §7 "Migrating queued waits").  Stream
+// ordering is tbe_expired_device's: the kernels run on the engine's stream, a caller's stream
+// is joined before and after.
+static const char *kQueueingOnly = "queueing kind only";
+static uint64_t ring_entries(const tbe_engine *e);
+
+static tbe_status qx_workspace(tbe_engine *e, uint64_t ntiles) {
+    const uint64_t need = 2 + ntiles;
+    if (need <= e->qx_ws_cap) return TBE_OK;
+    if (e->qx_ws) HIP_TRY(e, hipFree(e->qx_ws));   // (waits for the kernels that use it)
+    e->qx_ws = nullptr;
+    e->qx_ws_cap = 0;
+    if (hipMalloc(&e->qx_ws, need * sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e, TBE_ENOMEM, "queue export workspace");
+    }
+    e->qx_ws_cap = need;
+    return TBE_OK;
+}
+
+tbe_status tbe_queue_export_ids_device(tbe_engine *e, const uint64_t *d_ids, uint64_t n, uint32_t *d_qcount,
+                                       uint64_t *d_entry_start, uint64_t *d_entries, uint64_t capacity,
+                                       uint64_t *d_n_entries, int32_t clear, void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_QUEUEING) return fail(e, TBE_EINVAL, kQueueingOnly);
+    if (!d_n_entries || (n && (!d_ids || !d_qcount)) || (capacity && !d_entries))
+        return fail(e, TBE_EINVAL, "null buffer");
+    HIP_TRY(e, hipSetDevice(e->device));
+    const uint64_t ntiles = (n + kQxTile - 1) / kQxTile;
+    if (tbe_status rc = qx_workspace(e, ntiles)) return rc;
+    hipStream_t st = e->stream, caller = (hipStream_t)stream;
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_in, caller));
+        HIP_TRY(e, hipStreamWaitEvent(st, e->ev_in, 0));
+    }
+    if (n == 0) {
+        HIP_TRY(e, hipMemsetAsync(d_n_entries, 0, sizeof(uint64_t), st));
+        if (d_entry_start) HIP_TRY(e, hipMemsetAsync(d_entry_start, 0, sizeof(uint64_t), st));
+    } else {
+        unsigned long long *total = e->qx_ws, *tile_n = e->qx_ws + 2;
+        uint32_t *flags = reinterpret_cast<uint32_t *>(e->qx_ws + 1);
+        HIP_TRY(e, hipMemsetAsync(flags, 0, 2 * sizeof(uint32_t), st));
+        with_qhdr(e, [&](auto *qh) {
+            k_qx_count<<<(unsigned)ntiles, kBlock, 0, st>>>(d_ids, n, e->cfg.n_keys, qh, tile_n, flags);
+            k_qx_scan<<<1, kLiveScan, 0, st>>>(tile_n, ntiles, total, capacity, clear,
+                                               reinterpret_cast<unsigned long long *>(d_n_entries), flags, e->sticky);
+            k_qx_write<<<(unsigned)ntiles, kBlock, 0, st>>>(d_ids, n, e->cfg.n_keys, qh, e->ring, e->qp.cap,
+                                                            e->qcls_par ? e->qcls_view() : QClsView{nullptr, nullptr},
+                                                            tile_n, total, flags, d_qcount, d_entry_start, d_entries,
+                                                            capacity, clear);
+        });
+        HIP_TRY(e, hipGetLastError());
+        if (clear) e->queued_exact = false;   // queued_total stays an upper bound
+    }
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_out, st));
+        HIP_TRY(e, hipStreamWaitEvent(caller, e->ev_out, 0));
+    }
+    return TBE_OK;
+}
+
+tbe_status tbe_queue_export_ids(tbe_engine *e, const uint64_t *ids, uint64_t n, uint32_t *qcount,
+                                uint64_t *entry_start, uint64_t *entries, uint64_t capacity, uint64_t *n_entries,
+                                int32_t clear) {
+    if (!e || !n_entries) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_QUEUEING) return fail(e, TBE_EINVAL, kQueueingOnly);
+    if ((n && (!ids || !qcount)) || (capacity && !entries)) return fail(e, TBE_EINVAL, "null buffer");
+    for (uint64_t i = 0; i < n; ++i)
+        if (ids[i] >= e->cfg.n_keys) return fail(e, TBE_EINVAL, "id out of range");
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch, whatever its stream
+    *n_entries = 0;
+    if (n == 0) {
+        if (entry_start) entry_start[0] = 0;
+        return TBE_OK;
+    }
+    // [n entries | ids | starts | entries | counts]
+    char *buf = nullptr;
+    HIP_TRY(e, hipMalloc(&buf, 8 + n * 8 + (n + 1) * 8));
+    uint64_t *d_n = reinterpret_cast<uint64_t *>(buf), *d_ids = d_n + 1, *d_start = d_ids + n;
+    uint32_t *d_cnt = nullptr;
+    uint64_t *d_ent = nullptr;
+    hipError_t hrc = hipMalloc(&d_cnt, n * sizeof(uint32_t));
+    if (hrc == hipSuccess) hrc = hipMemcpy(d_ids, ids, n * 8, hipMemcpyHostToDevice);
+    tbe_status rc = TBE_OK;
+    // the counting call first: it sizes the entry buffer, and a clearing call that would be
+    // refused returns TBE_EINVAL here and leaves the sticky flag of earlier batches as it is
+    if (hrc == hipSuccess) rc = tbe_queue_export_ids_device(e, d_ids, n, d_cnt, d_start, nullptr, 0, d_n, 0, nullptr);
+    if (hrc == hipSuccess && rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
+    if (hrc == hipSuccess && rc == TBE_OK) hrc = hipMemcpy(n_entries, d_n, 8, hipMemcpyDeviceToHost);
+    const bool refused = hrc == hipSuccess && rc == TBE_OK && clear && *n_entries > capacity;
+    const uint64_t m = hrc == hipSuccess && rc == TBE_OK ? std::min(*n_entries, capacity) : 0;
+    if (hrc == hipSuccess && rc == TBE_OK && !refused && (m || clear)) {
+        if (m) hrc = hipMalloc(&d_ent, m * 8);
+        if (hrc == hipSuccess)
+            rc = tbe_queue_export_ids_device(e, d_ids, n, d_cnt, d_start, d_ent, m, d_n, clear, nullptr);
+        if (hrc == hipSuccess && rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
+        if (hrc == hipSuccess && rc == TBE_OK && m) hrc = hipMemcpy(entries, d_ent, m * 8, hipMemcpyDeviceToHost);
+    }
+    if (hrc == hipSuccess && rc == TBE_OK) hrc = hipMemcpy(qcount, d_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (hrc == hipSuccess && rc == TBE_OK && entry_start)
+        hrc = hipMemcpy(entry_start, d_start, (n + 1) * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d_ent);
+    (void)hipFree(d_cnt);
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
+    if (refused) return fail(e, TBE_EINVAL, "entries do not fit in capacity");
+    return TBE_OK;
+}
+
+// The import's judging passes on `st`, into e->rows_bad (zeroed here).
+static void launch_queue_import_check(tbe_engine *e, const uint64_t *d_ids, const uint32_t *d_qcount, uint64_t n,
+                                      const uint64_t *d_entries, uint64_t n_entries, uint64_t ntiles,
+                                      hipStream_t st) {
+    unsigned long long *tile_n = e->qx_ws + 2;
+    (void)hipMemsetAsync(e->rows_bad, 0, sizeof(uint32_t), st);
+    k_qi_count<<<(unsigned)ntiles, kBlock, 0, st>>>(d_qcount, n, tile_n);
+    k_qi_scan<<<1, kLiveScan, 0, st>>>(tile_n, ntiles, n_entries, e->rows_bad);
+    with_qhdr(e, [&](auto *qh) {
+        k_qi_pass<false><<<(unsigned)ntiles, kBlock, 0, st>>>(
+            d_ids, d_qcount, n, e->cfg.n_keys, d_entries, n_entries, qh, e->ring, e->qp.cap, (QOpt)e->qp,
+            e->qcls_par ? e->qcls_view() : QClsView{nullptr, nullptr}, tile_n, e->rows_bad, e->sticky);
+    });
+}
+
+tbe_status tbe_queue_import_ids_device(tbe_engine *e, const uint64_t *d_ids, const uint32_t *d_qcount, uint64_t n,
+                                       const uint64_t *d_entries, uint64_t n_entries, void *stream) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_QUEUEING) return fail(e, TBE_EINVAL, kQueueingOnly);
+    if ((n && (!d_ids || !d_qcount)) || (n_entries && !d_entries)) return fail(e, TBE_EINVAL, "null buffer");
+    if (n == 0 && n_entries == 0) return TBE_OK;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (!e->rows_bad) HIP_TRY(e, hipMalloc(&e->rows_bad, sizeof(uint32_t)));
+    const uint64_t ntiles = (n + kQxTile - 1) / kQxTile;
+    if (tbe_status rc = qx_workspace(e, ntiles)) return rc;
+    hipStream_t st = e->stream, caller = (hipStream_t)stream;
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_in, caller));
+        HIP_TRY(e, hipStreamWaitEvent(st, e->ev_in, 0));
+    }
+    if (n == 0) {   // entries without ids: the counts' sum differs from n_entries
+        HIP_TRY(e, hipMemsetAsync(e->sticky, 1, 1, st));
+    } else {
+        // the judging passes end before the first word is written (one stream)
+        launch_queue_import_check(e, d_ids, d_qcount, n, d_entries, n_entries, ntiles, st);
+        with_qhdr(e, [&](auto *qh) {
+            k_qi_pass<true><<<(unsigned)ntiles, kBlock, 0, st>>>(
+                d_ids, d_qcount, n, e->cfg.n_keys, d_entries, n_entries, qh, e->ring, e->qp.cap, (QOpt)e->qp,
+                e->qcls_par ? e->qcls_view() : QClsView{nullptr, nullptr}, e->qx_ws + 2, e->rows_bad, e->sticky);
+        });
+        HIP_TRY(e, hipGetLastError());
+        // the host cannot see whether the call took effect: an upper bound either way
+        e->queued_total = std::min<uint64_t>(e->queued_total + n_entries, ring_entries(e));
+        e->queued_exact = false;
+    }
+    if (caller && caller != st) {
+        HIP_TRY(e, hipEventRecord(e->ev_out, st));
+        HIP_TRY(e, hipStreamWaitEvent(caller, e->ev_out, 0));
+    }
+    return TBE_OK;
+}
+
+tbe_status tbe_queue_import_ids(tbe_engine *e, const uint64_t *ids, const uint32_t *qcount, uint64_t n,
+                                const uint64_t *entries, uint64_t n_entries) {
+    if (!e) return TBE_EINVAL;
+    if (e->cfg.kind != TBE_KIND_QUEUEING) return fail(e, TBE_EINVAL, kQueueingOnly);
+    if ((n && (!ids || !qcount)) || (n_entries && !entries)) return fail(e, TBE_EINVAL, "null buffer");
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (ids[i] >= e->cfg.n_keys) return fail(e, TBE_EINVAL, "id out of range");
+        sum += qcount[i];
+    }
+    if (sum != n_entries) return fail(e, TBE_EINVAL, "the counts do not sum to n_entries");
+    if (n == 0) return TBE_OK;
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipDeviceSynchronize());   // after every enqueued batch, whatever its stream
+    if (!e->rows_bad) HIP_TRY(e, hipMalloc(&e->rows_bad, sizeof(uint32_t)));
+    const uint64_t ntiles = (n + kQxTile - 1) / kQxTile;
+    if (tbe_status rc = qx_workspace(e, ntiles)) return rc;
+    char *buf = nullptr;   // [ids | entries | counts]
+    HIP_TRY(e, hipMalloc(&buf, n * 8 + n_entries * 8 + n * 4 + 8));
+    uint64_t *d_ids = reinterpret_cast<uint64_t *>(buf), *d_ent = d_ids + n;
+    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(d_ent + n_entries);
+    hipError_t hrc = hipMemcpy(d_ids, ids, n * 8, hipMemcpyHostToDevice);
+    if (hrc == hipSuccess && n_entries) hrc = hipMemcpy(d_ent, entries, n_entries * 8, hipMemcpyHostToDevice);
+    if (hrc == hipSuccess) hrc = hipMemcpy(d_cnt, qcount, n * 4, hipMemcpyHostToDevice);
+    // The rules only the device can judge (a queue that is not empty, the keys' classes): the
+    // judging passes alone first, so a void call returns TBE_EINVAL and leaves the sticky flag
+    // of earlier device batches as it is, as tbe_set_class does.
+    uint32_t bad = 0;
+    if (hrc == hipSuccess) {
+        launch_queue_import_check(e, d_ids, d_cnt, n, d_ent, n_entries, ntiles, e->stream);
+        hrc = hipGetLastError();
+    }
+    if (hrc == hipSuccess) hrc = hipMemcpyAsync(&bad, e->rows_bad, sizeof bad, hipMemcpyDeviceToHost, e->stream);
+    if (hrc == hipSuccess) hrc = hipStreamSynchronize(e->stream);
+    tbe_status rc = TBE_OK;
+    if (hrc == hipSuccess && !bad) rc = tbe_queue_import_ids_device(e, d_ids, d_cnt, n, d_ent, n_entries, nullptr);
+    if (hrc == hipSuccess && !bad && rc == TBE_OK) hrc = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    if (rc != TBE_OK) return rc;
+    HIP_TRY(e, hrc);
+    if (bad) return fail(e, TBE_EINVAL, "an id's queue is not empty, or its entries break its class's limits");
+    return TBE_OK;
 }
 
 // ---- limit classes

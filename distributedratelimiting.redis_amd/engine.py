@@ -279,6 +279,12 @@ class TokenBucketEngine:
         rewrites the leaving rows absent.  row_ids (int64 device tensor of at least capacity
         entries, optional): row_ids[j] = the id whose row is d_rows[j] (tbe_migrate_out_ids_device).
         Enqueued; a refused call raises at ``synchronize()``."""
+        self._migrate_out_device(self._lib.tbe_migrate_out_ids_device, ts_us, d_key_of_id, d_owner_map, n_owners,
+                                 self_rank, d_rows, d_counts, d_leaving, commit, first, capacity, stream, row_ids)
+
+    def _migrate_out_device(self, fn, ts_us, d_key_of_id, d_owner_map, n_owners, self_rank, d_rows, d_counts,
+                            d_leaving, commit, first, capacity, stream, row_ids) -> None:
+        # fn: tbe_migrate_out_ids_device, or the queueing kind's entry point of the same signature
         count = d_key_of_id.numel()
         if capacity is None:
             capacity = 0 if d_rows is None else d_rows.numel() // 4
@@ -296,7 +302,7 @@ class TokenBucketEngine:
                                     or not row_ids.is_contiguous()):
             raise ValueError("row_ids must be a contiguous 64-bit tensor of at least capacity entries")
         ptr = (lambda t: None if t is None else t.data_ptr())
-        self._check(self._lib.tbe_migrate_out_ids_device(
+        self._check(fn(
             self.handle, ts_us, first, count, d_key_of_id.data_ptr(), ptr(d_owner_map), n_owners, self_rank,
             ptr(d_rows) if capacity else None, capacity, d_counts.data_ptr(), ptr(d_leaving), 1 if commit else 0,
             ptr(row_ids) if capacity else None, stream))
@@ -309,6 +315,10 @@ class TokenBucketEngine:
         [n_owners + 2], leaving uint8 [count]).  capacity defaults to the number of ids.
         row_ids=True (tbe_migrate_out_ids) appends the rows' ids, uint64 [capacity], written as
         far as the rows are."""
+        return self._migrate_out(self._lib.tbe_migrate_out_ids, ts_us, key_of_id, owner_map, n_owners, self_rank,
+                                 commit, first, capacity, row_ids)
+
+    def _migrate_out(self, fn, ts_us, key_of_id, owner_map, n_owners, self_rank, commit, first, capacity, row_ids):
         key_of_id = np.ascontiguousarray(key_of_id, dtype=np.uint64)
         count = key_of_id.shape[0]
         if owner_map is not None:
@@ -321,7 +331,7 @@ class TokenBucketEngine:
         counts = np.zeros(n_owners + 2, dtype=np.uint64)
         leaving = np.zeros(count, dtype=np.uint8)
         ids = np.zeros(capacity, dtype=np.uint64) if row_ids else None
-        self._check(self._lib.tbe_migrate_out_ids(
+        self._check(fn(
             self.handle, ts_us, first, count, key_of_id.ctypes.data,
             None if owner_map is None else owner_map.ctypes.data, n_owners, self_rank,
             rows.ctypes.data if capacity else None, capacity, counts.ctypes.data, leaving.ctypes.data,
@@ -617,6 +627,108 @@ class QueueingTokenBucketEngine(TokenBucketEngine):
         self._check(self._lib.tbe_queue_cancel(self.handle, keys.ctypes.data, request_ids.ctypes.data,
                                                n, out.ctypes.data, byref(m)))
         return out
+
+    # ------------------------------------------------------------------ bulk queue export / import
+    def queue_export_ids_device(self, d_ids, d_qcount, d_entry_start, d_entries, d_n_entries, clear: bool = False,
+                                capacity: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """One tbe_queue_export_ids_device call: the queues of the listed ids (64-bit device
+        tensor) into d_qcount (int32/uint32, one per id), d_entry_start (64-bit, one per id and
+        one more, or None), d_entries (64-bit ``request_id << 16 | permits`` words, oldest
+        first, or None with capacity 0: only count) and d_n_entries (one 64-bit word).
+        capacity (entries) defaults to what d_entries holds.  clear=True also empties the listed
+        queues; a clearing call whose entries do not fit changes nothing.  Enqueued; a refused
+        call raises at ``synchronize()``."""
+        n = d_ids.numel()
+        if capacity is None:
+            capacity = 0 if d_entries is None else d_entries.numel()
+        if capacity and (d_entries is None or d_entries.numel() < capacity or d_entries.element_size() != 8
+                         or not d_entries.is_contiguous()):
+            raise ValueError("capacity exceeds d_entries")
+        if not d_ids.is_contiguous() or d_ids.element_size() != 8:
+            raise ValueError("d_ids must be a contiguous 64-bit tensor")
+        if d_qcount.numel() < n or d_qcount.element_size() != 4 or not d_qcount.is_contiguous():
+            raise ValueError("d_qcount must hold one 32-bit count per id")
+        if d_entry_start is not None and (d_entry_start.numel() < n + 1 or d_entry_start.element_size() != 8
+                                          or not d_entry_start.is_contiguous()):
+            raise ValueError("d_entry_start must hold n + 1 64-bit entries")
+        if d_n_entries.numel() < 1 or d_n_entries.element_size() != 8:
+            raise ValueError("d_n_entries must hold one 64-bit word")
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        self._check(self._lib.tbe_queue_export_ids_device(
+            self.handle, d_ids.data_ptr(), n, d_qcount.data_ptr(), ptr(d_entry_start),
+            ptr(d_entries) if capacity else None, capacity, d_n_entries.data_ptr(), 1 if clear else 0, stream))
+        self._queue_in_flight = (d_ids,)   # read by the enqueued kernels
+
+    def queue_export_ids(self, ids, clear: bool = False, capacity: Optional[int] = None):
+        """The same with host arrays (tbe_queue_export_ids; synchronous): returns (qcount uint32
+        [n], entry_start uint64 [n + 1], entries uint64 [min(total, capacity)], total).  capacity
+        defaults to every entry (a counting call sizes the buffer)."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        n = ids.shape[0]
+        qcount = np.zeros(n, dtype=np.uint32)
+        start = np.zeros(n + 1, dtype=np.uint64)
+        total = ctypes.c_uint64()
+        if capacity is None:
+            self._check(self._lib.tbe_queue_export_ids(self.handle, ids.ctypes.data, n, qcount.ctypes.data,
+                                                       start.ctypes.data, None, 0, byref(total), 0))
+            capacity = total.value
+        entries = np.zeros(capacity, dtype=np.uint64)
+        self._check(self._lib.tbe_queue_export_ids(self.handle, ids.ctypes.data, n, qcount.ctypes.data,
+                                                   start.ctypes.data, entries.ctypes.data if capacity else None,
+                                                   capacity, byref(total), 1 if clear else 0))
+        return qcount, start, entries[: min(total.value, capacity)], total.value
+
+    def queue_import_ids_device(self, d_ids, d_qcount, d_entries, n_entries: Optional[int] = None,
+                                stream: Optional[int] = None) -> None:
+        """One tbe_queue_import_ids_device call: id i takes the next d_qcount[i] of d_entries
+        (64-bit ``request_id << 16 | permits`` words; n_entries defaults to d_entries.numel()).
+        Every id and entry is judged first; a void call writes nothing and raises at
+        ``synchronize()``.  Set a moved key's class and row before its queue."""
+        n = d_ids.numel()
+        if n_entries is None:
+            n_entries = 0 if d_entries is None else d_entries.numel()
+        if not d_ids.is_contiguous() or d_ids.element_size() != 8:
+            raise ValueError("d_ids must be a contiguous 64-bit tensor")
+        if d_qcount.numel() != n or d_qcount.element_size() != 4 or not d_qcount.is_contiguous():
+            raise ValueError("d_qcount must hold one 32-bit count per id")
+        if n_entries and (d_entries is None or d_entries.numel() < n_entries or d_entries.element_size() != 8
+                          or not d_entries.is_contiguous()):
+            raise ValueError("n_entries exceeds d_entries")
+        self._check(self._lib.tbe_queue_import_ids_device(
+            self.handle, d_ids.data_ptr(), d_qcount.data_ptr(), n,
+            d_entries.data_ptr() if n_entries else None, n_entries, stream))
+        self._queue_in_flight = (d_ids, d_qcount, d_entries)   # read by the enqueued kernels
+
+    def queue_import_ids(self, ids, qcount, entries) -> None:
+        """The same from host arrays (tbe_queue_import_ids; synchronous): a void call raises and
+        changes nothing."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        qcount = np.ascontiguousarray(qcount, dtype=np.uint32)
+        entries = np.ascontiguousarray(entries, dtype=np.uint64)
+        if ids.shape != qcount.shape:
+            raise ValueError("ids and qcount must have the same length")
+        self._check(self._lib.tbe_queue_import_ids(self.handle, ids.ctypes.data, qcount.ctypes.data, ids.shape[0],
+                                                   entries.ctypes.data if entries.shape[0] else None,
+                                                   entries.shape[0]))
+
+    def queue_migrate_out_device(self, ts_us: int, d_key_of_id, d_owner_map, n_owners: int, self_rank: int, d_rows,
+                                 d_counts, d_leaving=None, commit: bool = False, first: int = 0,
+                                 capacity: Optional[int] = None, stream: Optional[int] = None, row_ids=None) -> None:
+        """``migrate_out_device`` for a queueing engine (tbe_queue_migrate_out_ids_device): a
+        leaving id sends a row when its bucket row is live or its queue is not empty, word 3 of
+        a row is ``class | queue entries << 8``, and commit=True leaves the queue headers alone:
+        ``queue_export_ids_device(row_ids, ..., clear=True)`` takes the queues, next and with
+        nothing in between."""
+        self._migrate_out_device(self._lib.tbe_queue_migrate_out_ids_device, ts_us, d_key_of_id, d_owner_map,
+                                 n_owners, self_rank, d_rows, d_counts, d_leaving, commit, first, capacity, stream,
+                                 row_ids)
+
+    def queue_migrate_out(self, ts_us: int, key_of_id, owner_map, n_owners: int, self_rank: int,
+                          commit: bool = False, first: int = 0, capacity: Optional[int] = None):
+        """The same with host arrays (tbe_queue_migrate_out_ids; synchronous): returns (rows,
+        counts, leaving, row_ids) as ``migrate_out(row_ids=True)`` does."""
+        return self._migrate_out(self._lib.tbe_queue_migrate_out_ids, ts_us, key_of_id, owner_map, n_owners,
+                                 self_rank, commit, first, capacity, True)
 
 
 class ApproximateEngine(QueueingTokenBucketEngine):

@@ -577,6 +577,83 @@ tbe_status tbe_queue_of(tbe_engine *engine, uint64_t key, int64_t *request_id, i
 tbe_status tbe_queue_cancel(tbe_engine *engine, const uint64_t *keys, const int64_t *request_ids,
                             uint64_t n, uint8_t *cancelled, uint64_t *n_cancelled);
 
+/* ---- Bulk queue export and import by id list (DESIGN.md §7 "Migrating queued waits").
+ * Queueing kind only, plain or with queueing classes; token-bucket and approximate engines:
+ * TBE_EINVAL (the approximate kind's queue lives beside its local tier, with zero-permit
+ * registrations, and does not travel).  Both device forms only enqueue: ordered after every
+ * batch enqueued before the call (pipelined ones included) and before every batch enqueued
+ * after it; `stream` as in tbe_expired_device.
+ *
+ * Export: d_qcount[i] (device u32, n entries) = entries queued on d_ids[i], 0 included;
+ * d_entry_start (device u64, n + 1 entries, may be NULL) = the exclusive prefix of the counts,
+ * [n] the total; *d_n_entries (device u64) = the total.  The entries of id i land at
+ * d_entries[d_entry_start[i] + j], j < d_qcount[i], oldest first (Deque enumeration order,
+ * DQ:116-125, as tbe_queue_of reports them) in the ring's own format request_id << 16 | permits:
+ * the walk starts at the header's head and wraps at the key's own ring length, max(1,
+ * QueueLimit) of its class on a classed engine.  Nothing at or past `capacity` (entries) is
+ * touched; capacity == 0 (d_entries may be NULL) only counts.  clear != 0: afterwards every
+ * listed id's header holds the empty queue with head 0, as tbe_set_class_device leaves it (ring
+ * words are not scrubbed); ids must then be unique (the result for an id given twice is
+ * unspecified).  A clearing call whose entries do not all fit in capacity changes no header
+ * (counts, starts, the total and the entries below capacity are still written); any call that
+ * meets an id >= n_keys writes nothing at all, *d_n_entries included.  Both are reported like an
+ * invalid device batch: by tbe_synchronize.  The engine keeps 8 bytes of workspace per 2048
+ * listed ids.
+ *
+ * Import: id i takes the next d_qcount[i] entries of d_entries (the call scans the counts
+ * itself).  Every id and every entry is judged before anything is written; the call is a no-op,
+ * reported by tbe_synchronize, when an id is >= n_keys, a target queue is not empty, a count
+ * exceeds the key's ring length (its current class), an entry holds permits < 1 or more than
+ * the TokenLimit of the key's class, a key's entries sum to more permits than its class's
+ * QueueLimit (Q:92, Q:153), a request id is >= 2^47, or the counts do not sum to n_entries.
+ * On success the ring of id i holds its entries at slots 0 .. count - 1 and its header is
+ * {head 0, count, sum of permits}.  Ids must be unique.  Bucket rows, class bytes and lease
+ * counters are not touched: a caller that moves a key sets its class first (tbe_set_class_device
+ * requires an empty queue and resets the header), then its row, then its queue.  The engine's
+ * count of queued entries grows by n_entries and stays an upper bound; tbe_refresh_bound and
+ * the host tbe_refresh cover the imported entries.
+ *
+ * Request ids travel verbatim.  A queue that was filled on one engine and imported into
+ * another then mixes ids minted by both, so callers that move queues between owners mint ids
+ * that are unique across owners, e.g. id_base = (owner << 40) + counter, which stays below
+ * 2^47 for 128 owners. */
+tbe_status tbe_queue_export_ids_device(tbe_engine *engine, const uint64_t *d_ids, uint64_t n, uint32_t *d_qcount,
+                                       uint64_t *d_entry_start, uint64_t *d_entries, uint64_t capacity,
+                                       uint64_t *d_n_entries, int32_t clear, void *stream);
+/* The same with host buffers; synchronous.  An id >= n_keys, or a clearing call whose entries
+ * do not fit: TBE_EINVAL, no header changed (*n_entries is set in the second case). */
+tbe_status tbe_queue_export_ids(tbe_engine *engine, const uint64_t *ids, uint64_t n, uint32_t *qcount,
+                                uint64_t *entry_start, uint64_t *entries, uint64_t capacity, uint64_t *n_entries,
+                                int32_t clear);
+tbe_status tbe_queue_import_ids_device(tbe_engine *engine, const uint64_t *d_ids, const uint32_t *d_qcount,
+                                       uint64_t n, const uint64_t *d_entries, uint64_t n_entries, void *stream);
+/* The same from host buffers; synchronous; a void call: TBE_EINVAL, nothing changed. */
+tbe_status tbe_queue_import_ids(tbe_engine *engine, const uint64_t *ids, const uint32_t *qcount, uint64_t n,
+                                const uint64_t *entries, uint64_t n_entries);
+
+/* Live owner-map change of a queueing engine, the source side: tbe_migrate_out_ids_device /
+ * tbe_migrate_out_ids (above) with these differences.  Queueing kind only, plain or with
+ * queueing classes; other kinds: TBE_EINVAL.  A leaving id contributes a row when its bucket
+ * row is live at ts_us OR its queue is not empty (tbe_expired_device's rule: a key with queued
+ * requests is never dead); a queued key's row travels verbatim, a lapsed t_us or INT64_MIN
+ * included.  Row word 3 is class | (queue entries << 8).  An orphan is an id no key holds whose
+ * row is live or whose queue is not empty.  commit != 0 rewrites the leaving ids' bucket rows
+ * absent and zeroes their lease counters as above; it does NOT touch queue headers.  The
+ * leaving ids' queues are taken by tbe_queue_export_ids_device(d_row_ids, clear = 1), which the
+ * caller issues next with nothing in between: every id with queued entries has a row, so the
+ * rows' ids cover every queue that leaves.  NewestFirst evictions of the last wait batch
+ * (tbe_evicted) are fetched before a migration.  The collective around it is
+ * cluster.migrate_queueing. */
+tbe_status tbe_queue_migrate_out_ids_device(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                                            const uint64_t *d_key_of_id, const uint8_t *d_owner_map,
+                                            uint32_t n_owners, uint32_t self, int64_t *d_rows, uint64_t capacity,
+                                            uint64_t *d_counts, uint8_t *d_leaving, int32_t commit,
+                                            uint64_t *d_row_ids, void *stream);
+tbe_status tbe_queue_migrate_out_ids(tbe_engine *engine, int64_t ts_us, uint64_t first, uint64_t count,
+                                     const uint64_t *key_of_id, const uint8_t *owner_map, uint32_t n_owners,
+                                     uint32_t self, int64_t *rows, uint64_t capacity, uint64_t *counts,
+                                     uint8_t *leaving, int32_t commit, uint64_t *row_ids);
+
 /* ---------------------------------------------------------------- ApproximateTokenBucket
  * Engines created with kind = TBE_KIND_APPROXIMATE hold ONE client's local tier for every
  * key (ApproximateTokenBucket/RedisApproximateTokenBucketRateLimiter.cs, "A") plus a

@@ -45,6 +45,24 @@ table.  Bytes: what each step must read and write at least (see the code); `of_c
 above.  Single-GPU local steps only: the three exchanges need more than one GPU.
 
     python tools/migrate_time.py --text [--keys 67108864] [--repeats 5] [--out profiles/migrate_text_time.json]
+
+--queue: the same change for a queueing engine (cluster.migrate_queueing's local steps): a
+QueueingTokenBucketEngine with QueueLimit 16 whose --keys queues are all saturated (sixteen
+one-permit entries each, put there with queue_import_ids_device), every row live.  Each of the
+--repeats rounds runs one rank's local steps once, each between HIP events; medians are reported:
+
+  count    queue_migrate_out_device, counting and flagging only
+  commit   queue_migrate_out_device(commit) with the rows' ids
+  export   queue_export_ids_device(row ids, clear) into a buffer of 16 entries per row
+  reclaim  reclaim_device(leaving flags)
+  install  the receiver's side, on the same directory and engine: assign (into the ids the
+           reclaim freed) + import_rows + queue_import_ids_device
+
+The install puts every key, row and queue back, so the next round finds the same table.  The
+token-bucket figures of the default mode at the same --keys (without the snapshot route) are
+measured in the same run and stored under "token_bucket".
+
+    python tools/migrate_time.py --queue [--keys 4194304] [--repeats 5] [--out profiles/migrate_queue_time.json]
 """
 import argparse
 import json
@@ -67,6 +85,7 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--no-snapshot", action="store_true")
     ap.add_argument("--text", action="store_true", help="text-keyed buckets behind a StringDirectory")
+    ap.add_argument("--queue", action="store_true", help="a queueing engine with saturated queues")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -251,8 +270,93 @@ def main() -> None:
         directory.close()
         return res
 
+    QL = 16
+
+    def run_queue(n: int, repeats: int) -> dict:
+        from distributedratelimiting.redis_amd import QueueingTokenBucketEngine
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        eng, directory = QueueingTokenBucketEngine(n, *OPTS, QL, 0, device=0), cluster.DeviceDirectory(n, device=0)
+        keys = torch.arange(n, dtype=torch.int64, device=dev)
+        g = torch.Generator(device=dev).manual_seed(7)
+        v = torch.rand(n, dtype=torch.float64, device=dev, generator=g) * OPTS[0]
+        t = TS - torch.randint(0, 2_000_000, (n,), dtype=torch.int64, device=dev, generator=g)   # every row live
+        ids = directory.assign(keys)
+        directory.check()
+        eng.import_rows(ids, v, t, stream=cur)
+        full = torch.full((n,), QL, dtype=torch.int32, device=dev)
+        words = (torch.arange(n * QL, dtype=torch.int64, device=dev) << 16) | 1
+        eng.queue_import_ids_device(ids, full, words, stream=cur)
+        eng.synchronize()
+        del keys, v, t, words
+        dmap = torch.from_numpy(map_b).to(dev)
+        counts = torch.zeros(world + 2, dtype=torch.int64, device=dev)
+        leaving = torch.empty(n, dtype=torch.uint8, device=dev)
+        n_out = torch.zeros(1, dtype=torch.int64, device=dev)
+        steps = ("count", "commit", "export", "reclaim", "install")
+        ms = {k: [] for k in steps}
+        for _ in range(repeats):
+            kof = directory.keys_of(torch.arange(n, dtype=torch.int64, device=dev))
+            ms["count"].append(timed(lambda: eng.queue_migrate_out_device(TS, kof, dmap, world, me, None, counts,
+                                                                          leaving, stream=cur))[0])
+            c = counts.tolist()
+            n_rows, n_leave = sum(c[:world]), c[world]
+            assert c[world + 1] == 0 and n_rows == n_leave
+            rows = torch.empty((n_rows, 4), dtype=torch.int64, device=dev)
+            row_ids = torch.empty(n_rows, dtype=torch.int64, device=dev)
+            qcount = torch.empty(n_rows, dtype=torch.int32, device=dev)
+            entries = torch.empty(n_rows * QL, dtype=torch.int64, device=dev)
+            ms["commit"].append(timed(lambda: eng.queue_migrate_out_device(
+                TS, kof, dmap, world, me, rows, counts, leaving, commit=True, capacity=n_rows, stream=cur,
+                row_ids=row_ids))[0])
+            ms["export"].append(timed(lambda: eng.queue_export_ids_device(row_ids, qcount, None, entries, n_out,
+                                                                          clear=True, stream=cur))[0])
+            eng.synchronize()
+            n_ent = int(n_out.item())
+            assert n_ent == n_rows * QL
+            ms["reclaim"].append(timed(lambda: directory.reclaim_device(leaving))[0])
+            assert directory.size() == n - n_leave
+
+            def install():
+                rid = directory.assign(rows[:, 0].contiguous())
+                eng.import_rows(rid, rows[:, 1].contiguous().view(torch.float64), rows[:, 2].contiguous(), stream=cur)
+                eng.queue_import_ids_device(rid, qcount, entries, stream=cur)
+            ms["install"].append(timed(install)[0])
+            eng.synchronize()
+            assert directory.size() == n
+            del kof, rows, row_ids, qcount, entries
+        hdr = 4                                                       # QueueLimit 16: 32-bit headers
+        count_bytes = (24 + hdr + 1) * n
+        # at least: per step, the arrays it must read and write once per pass
+        nbytes = {
+            "count": count_bytes,
+            "commit": count_bytes + (24 + hdr) * n + 40 * n_rows + 8 * n + 16 * n_leave,
+            # ids and headers in two passes, counts out, ring words in, entries out, headers cleared
+            "export": 2 * (8 + hdr) * n_rows + 4 * n_rows + 16 * n_ent + hdr * n_rows,
+            "reclaim": 9 * n + 8 * n_leave,
+            # assign (keys in, ids out), import_rows (ids, v, t in; rows out), queue import: counts in three
+            # passes, ids and headers in two, entries in twice, ring words and headers out
+            "install": 16 * n_rows + 40 * n_rows + 12 * n_rows + 2 * (8 + hdr) * n_rows + 16 * n_ent + 8 * n_ent
+                       + hdr * n_rows,
+        }
+        res = {"keys": n, "queue_limit": QL, "rows_sent": n_rows, "entries_sent": n_ent}
+        for k in steps:
+            med = statistics.median(ms[k])
+            res[f"{k}_ms"] = round(med, 4)
+            res[f"{k}_all_ms"] = [round(x, 4) for x in ms[k]]
+            res[f"{k}_bytes"] = nbytes[k]
+            res[f"{k}_of_copy_rate"] = round(nbytes[k] / (med * 1e-3) / COPY_RATE, 4)
+        res["migrate_local_ms"] = round(sum(res[f"{k}_ms"] for k in steps), 4)
+        eng.close()
+        directory.close()
+        return res
+
     with torch.cuda.stream(torch.cuda.Stream(dev)):
-        if args.text:
+        if args.queue:
+            run_queue(1 << 14, 2)                      # warm-up: every call at a small size
+            line = run_queue(args.keys, args.repeats)
+            run(1 << 16, 2, False)
+            line["token_bucket"] = run(args.keys, args.repeats, False)
+        elif args.text:
             run_text(1 << 16, 2)                       # warm-up: every call at a small size
             line = run_text(args.keys, args.repeats)
         else:
